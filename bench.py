@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- grid-point-updates/s of the implicit Keller-Segel step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1 without a launcher: this script starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
    --master-addr 127.0.0.1 ... bench.py ...` itself, before anything touches the GPU, and relays rank 0's line)
 
@@ -21,6 +21,11 @@ over a run, and a step at h = 1 costs several times a step at h = 1e-3):
       checkpoint (ksfd_checkpoint restore at every wrap-around: one device copy, inside the timed region).  Every
       window is the same work, so any K that is a multiple of the window gives the same number; W warm-up steps walk the
       same window first.  value = N_grid * K / wall.
+
+A plain run does only that: ramp, (N > 1: the stage-solver choice), warm-up, K timed steps, the outputs (--dump-outputs)
+and the result line.  `roofline` and `kernels` come from HIP events in those same steps (roofline.traffic from the
+committed PMC summary).  --full adds the side measurements below, each in a leg or run of its own:
+
   `fixed_h`: 100 steps at h = 1e-3 from the start values (SURVEY.md 8d's second run), its own rate.
   `aggregated`: the late phase of a production run, where the wall clock of a long run goes (aggregates have formed, the
       constant-coefficient inverse no longer contracts, the multigrid-preconditioned GMRES takes over): a 256^2 run with
@@ -28,9 +33,15 @@ over a run, and a step at h = 1 costs several times a step at h = 1e-3):
       problem), then a few adaptive steps timed there.  Its own rate, never part of `value`.
 
 One JSON line on rank 0, with `roofline` for the dominant kernel class of the timed region (HIP events on the library's
-compute stream), `cpu_baseline` (the oracle's restatement of the same step with unpreconditioned GMRES, OpenMP over the host
+compute stream; with --full its `traffic` is measured live in two rocprofv3 --pmc child runs) and, with --full,
+`cpu_baseline` (the oracle's restatement of the same step with unpreconditioned GMRES, OpenMP over the host
 cores, bounded sample) and `cpu_baseline_lu` (the REFERENCE's algorithm -- assembled Jacobian, one sparse LU per step, four
 back-substitutions, options84:58-60 -- from the oracle's operators + scipy's SuperLU on a bounded sample).
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as float64 .npy files: the state
+(`state.npy`, or above 4M values a fixed seeded sample `state_sample.npy` + its flat indices `state_sample_index.npy`),
+`step_scalars.npy` = [t, proposed next h, h used, wrms error] and `velocity_max.npy` (the CFL check's maxima per axis).
+The start values are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -75,7 +86,14 @@ def parse_args(argv=None):
     ap.add_argument('--agg-n', type=int, default=2048, help='grid the aggregated state is tiled to')
     ap.add_argument('--agg-steps', type=int, default=5)
     ap.add_argument('--yseg', type=int, default=0)
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side measurements: fixed-h and aggregated legs, live PMC traffic of the roofline, CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)')
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def self_launch(args):
@@ -166,10 +184,12 @@ def main():
         return o
 
     spacing = cfg.spacing
+    last = {}                                                 # what the latest step returned (--dump-outputs)
 
     def one_step(t, h, opts):
         t, h, st, rc = ks.step(t, h, opts)                   # groom + ROSW/GMRES step (+ rejections)
         vmax = ks.velocity_max()                              # CFL_check, KSFD/ksfdts.py:287-319
+        last.update(t=t, h=h, st=st, vmax=vmax)
         cfl = min(s * 2 / v if v > 0 else float('inf') for s, v in zip(spacing, vmax[:cfg.dim]))
         return t, h, st, cfl
 
@@ -215,7 +235,7 @@ def main():
 
     # ---------------- fixed-h leg: 100 steps at h = 1e-3 from the start values
     fixed = None
-    if args.fixed_h > 0 and args.fixed_steps > 0:
+    if args.full and args.fixed_h > 0 and args.fixed_steps > 0:
         ks.set_state_random(zc, 9000.0)
         o = opts_for(0)
         t, h = 0.0, args.fixed_h
@@ -309,8 +329,11 @@ def main():
     prof = ks.profile()
     ks.set_profiling(False)
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ks, cfg, last, rank, world, host_group)
+
     aggregated = None
-    if world == 1 and args.dim == 2 and args.agg_tile > 0 and args.agg_steps > 0:
+    if args.full and world == 1 and args.dim == 2 and args.agg_tile > 0 and args.agg_steps > 0:
         ks.close()                                            # its memory is not needed any more
         ks = None
         aggregated = aggregated_leg(args, klib, np)
@@ -334,7 +357,7 @@ def main():
         default_workload = world == 1 and args.n == 4096 and args.dim == 2 and args.nlig == 1
         traffic, traffic_src = pmc_traffic(dom) if default_workload else (None, None)
         live_err = None
-        if default_workload and not args.no_live_pmc:
+        if default_workload and args.full and not args.no_live_pmc:
             lt, live_err = live_pmc(args, dom)
             if lt:
                 traffic, traffic_src, live_err = lt, 'live: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE child runs of this command (ramp + 7 steps of the window), 2*FETCH_SIZE + WRITE_SIZE', None
@@ -375,7 +398,7 @@ def main():
             'ramp': ramp, 'fixed_h': fixed, 'aggregated': aggregated,
             'kernels': kern, 'kernels_region': 'warmup steps (events on every launch)' if args.warmup > 0 else 'timed steps',
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args, float(np.mean(tal.hs)))
             if args.cpu_lu_n > 0 and args.dim == 2:
                 out['cpu_baseline_lu'] = cpu_baseline_lu(args, float(np.mean(tal.hs)))
@@ -385,6 +408,34 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_FULL_MAX = 1 << 22          # values of the state written whole (32 MB of float64)
+DUMP_SAMPLE = 1 << 21            # else this many, at seeded random positions (16 MB + 16 MB of indices)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(outdir, ks, cfg, last, rank, world, host_group):
+    """--dump-outputs: the last timed step's results as float64 .npy files (module docstring).  Every rank takes part in the
+    gather of the state; rank 0 writes."""
+    import numpy as np
+    u = ks.get_state()
+    if world > 1:
+        from ksfd_amd.dist import gather_slabs
+        u = gather_slabs(u, cfg, group=host_group)
+    if rank != 0:
+        return
+    os.makedirs(outdir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(outdir, name + '.npy'), np.asarray(a, dtype=np.float64))
+    if u.size <= DUMP_FULL_MAX:
+        save('state', u)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(u.size, DUMP_SAMPLE, replace=False))
+        save('state_sample', u[idx])
+        save('state_sample_index', idx)
+    st = last['st']
+    save('step_scalars', [last['t'], last['h'], st.h_used, st.wrms])
+    save('velocity_max', last['vmax'])
 
 
 def aggregated_leg(args, klib, np):

@@ -81,15 +81,22 @@ int main(void) {
     assert 'class1=jvp rtol=1e-06 pc=2' in r.stdout and 'rc=1' in r.stdout and 'dim must be' in r.stdout
 
 
-def test_live_pmc_of_the_bench_never_raises_without_a_gpu():
-    """bench.py measures roofline.traffic in two rocprofv3 --pmc child runs of itself; whatever goes wrong there (no profiler, no GPU, a
-    crash of the child) must come back as (None, reason) -- the bench line then falls back to the committed summary and says so."""
+def test_live_pmc_of_the_bench_never_raises_without_a_gpu(monkeypatch):
+    """bench.py --full measures roofline.traffic in two rocprofv3 --pmc child runs of itself; whatever goes wrong there (no profiler, no GPU,
+    a crash of the child) must come back as (None, reason) -- the bench line then falls back to the committed summary and says so.
+    With a GPU present the real child runs would succeed (and use the GPU), so there only a crash of the child is simulated."""
     import argparse
     import os
+    import subprocess
     import sys
+    import torch
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
     import bench
     args = argparse.Namespace(n=64, nlig=1, dim=2)
+    if not torch.cuda.is_available():
+        val, err = bench.live_pmc(args, 'spectral')
+        assert val is None and isinstance(err, str) and err
+    monkeypatch.setattr(subprocess, 'run', lambda cmd, **kw: subprocess.CompletedProcess(cmd, 134, b'', b'Aborted'))
     val, err = bench.live_pmc(args, 'spectral')
     assert val is None and isinstance(err, str) and err
     val, err = bench.live_pmc(args, 'no-such-class')
