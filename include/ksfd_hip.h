@@ -25,6 +25,7 @@
 extern "C" {
 #endif
 
+#define KSFD_DIRECT_MAX 32768  /* largest F * local points the direct solver (pc_type 5) takes: 8 * 32768^2 B = 8.6 GB of dense factors */
 #define KSFD_MAX_LIG 12  /* ligand fields after the reference's fourier_series() expansion (KSFD/ksfdligand.py:315-388 has no cap;
                           * 12 = the dispatch width of the kernels, params.h: KSFD_MAXL) */
 
@@ -100,7 +101,9 @@ typedef struct ksfd_step_opts {
                                  * (constant-coefficient part of shift*I - J inverted by FFT; 2-D and 3-D, extents 2^k or 3*2^k, on 1, 2,
                                  * 4 or 8 slab ranks) while it converges in a few sweeps, else multigrid when the step is stiff,
                                  * Chebyshev polynomial + flexible GMRES when mildly stiff, none when not; 3 polynomial only;
-                                 * 4 spectral always */
+                                 * 4 spectral always; 5 direct: dense LU of shift*I - J on the device, factored once per step attempt, every
+                                 * stage solve checked by its true residual against max(ksp_rtol*||b||, ksp_atol) with at most two refinement
+                                 * steps (single rank, at most KSFD_DIRECT_MAX unknowns, else KSFD_EINVAL before anything is touched) */
     int32_t reserved;           /* flags.  bit 0: classic two-pass CGS2 instead of CGS2 with the algebraic second projection;
                                  * bit 1: single attempt per call -- a rejected step returns with accepted = 0 and *hstep = the
                                  * controller's proposal (callers that must refresh stage-time data per attempt);
@@ -116,7 +119,7 @@ typedef struct ksfd_step_stats {
                                  * inverse (sweeps of the defect correction) where pc_used has bit 8 */
     int32_t rhs_evals, jvp_evals;
     int32_t pc_used;            /* preconditioners the stage solves of this call ran with, OR of: 1 none, 2 multigrid V cycle,
-                                 * 4 Chebyshev polynomial, 8 spectral (constant-coefficient FFT) */
+                                 * 4 Chebyshev polynomial, 8 spectral (constant-coefficient FFT), 16 direct (dense LU, pc_type 5) */
     double wrms;                /* error norm of the last attempt */
     double h_used;              /* step actually taken (valid when accepted) */
     double ksp_resid;           /* last relative residual */
@@ -124,7 +127,8 @@ typedef struct ksfd_step_stats {
     int32_t launches;           /* kernels / device copies the call enqueued on the compute stream */
     int32_t host_syncs;         /* times the host waited for a device result inside the call (reduction hand-overs, stream
                                  * synchronisations): the latency-bound part of a step on many slab ranks */
-    int32_t residual_evals;     /* true residuals b - A x evaluated by the spectral defect correction (one Jacobian action each) */
+    int32_t residual_evals;     /* true residuals b - A x evaluated by the spectral defect correction or the direct solver (one Jacobian
+                                 * action each) */
     int32_t predicted_final;    /* stage solves whose LAST sweep was applied on the measured contraction of the earlier sweeps
                                  * instead of a residual evaluation (ksp_rtol >= 1e-8 only; opts.reserved bit 3 switches it off) */
 } ksfd_step_stats;
@@ -268,6 +272,11 @@ int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, doub
  * elsewhere; <= 0 keeps) and enable (0 = never pick it automatically, 1 = default, < 0 keeps). */
 int ksfd_spectral_apply(ksfd_handle *h, double shift, const double *v_host, double *out_host, int32_t layout);
 int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enable);
+/* Direct solver (pc_type 5): out = (shift*I - J)^-1 v with J the assembled Jacobian at the resident state, by the same assembly, LU
+ * factorization with partial pivoting and triangular solves ksfd_step uses (no refinement here).  Parity/test entry like
+ * ksfd_spectral_apply; KSFD_EINVAL on a handle with a halo transport or more than KSFD_DIRECT_MAX unknowns, KSFD_ELINEAR on a zero or
+ * non-finite pivot.  The state and what the stepper remembers are not changed. */
+int ksfd_direct_apply(ksfd_handle *h, double shift, const double *v, double *out, int32_t layout);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,19 @@ struct SpecState {
     double rho_step = 0.0, rho_prev = 0.0;
 };
 
+// dense direct solver, pc_type 5 (lu.hip.h / lu_host.hip.h): buffers allocated on first use, factors rebuilt every step attempt
+struct LUState {
+    int64_t n = 0, nnz = 0;
+    double *A = nullptr;                     // n x n factors, column-major (L unit-lower below the diagonal, U on and above)
+    int *piv = nullptr, *perm = nullptr, *info = nullptr;
+    long long *col = nullptr;                // Jacobian entries staged by k_jac_csr
+    double *val = nullptr;
+    double *y = nullptr, *z = nullptr;       // triangular-solve work vectors
+    std::vector<int> piv_h, perm_h;
+    bool valid = false;                      // A holds the factors of shift*I - J at the resident coefficient planes
+    double shift = 0.0;
+};
+
 struct ksfd_handle {
     ksfd_config cfg;
     int32_t lig_group[KSFD_MAXL];
@@ -179,6 +192,8 @@ struct ksfd_handle {
     int rec_keep = 3;                // leading vectors kept per stage (<= 4)
     bool rhs_dots = true;            // inner products for the stage guesses from the RHS kernel's store epilogue (KSFD_TUNE bit 21 clears)
     bool rec_mg = false;             // multigrid-preconditioned solves: the WHOLE first cycle of every stage is kept for the later stages of the step (KSFD_TUNE bit 20 sets; measured: no gain, see gmres)
+
+    LUState lu;
 
     // multigrid preconditioner
     std::vector<MGLevel> mg;

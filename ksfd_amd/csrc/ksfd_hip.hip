@@ -16,6 +16,7 @@
 #include "stencil.hip.h"
 #include "mg.hip.h"
 #include "spectral.hip.h"
+#include "lu.hip.h"
 #include "transport.h"
 
 
@@ -24,6 +25,7 @@
 #include "spectral_host.hip.h"
 #include "mg_host.hip.h"
 #include "krylov.hip.h"
+#include "lu_host.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -55,6 +57,7 @@ extern "C" void ksfd_destroy(ksfd_handle *h)
     }
     mg_free(h);
     spec_free(h);
+    direct_free(h);
     delete h->tr;
     if (h->ev_ready) hipEventDestroy(h->ev_ready);
     if (h->ev_halo) hipEventDestroy(h->ev_halo);
@@ -616,6 +619,13 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
 {
     if (!h || !t || !hstep || !opts) return KSFD_EINVAL;
     hipSetDevice(h->device);
+    // pc_type 5: dense LU of shift*I - J, factored once per attempt (lu_host.hip.h); no spectral / polynomial / multigrid / pipelined
+    // solver, no stage guesses.  Its limits are checked before the state or the step-to-step memory is touched.
+    const bool direct = opts->pc_type == 5;
+    if (direct) {
+        const int g = direct_guard(h);
+        if (g) return g;
+    }
     if (getenv("KSFD_PC_SIGMA")) { h->mg_shift_floor = atof(getenv("KSFD_PC_SIGMA")); h->sf_auto = false; }      // experiment knob: fixed floor
     ksfd_step_stats st;
     memset(&st, 0, sizeof st);
@@ -656,12 +666,12 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
         const double mg_from = h->mg_threshold * ((double)h->G.F * (double)h->G.nloc < 8.0e6 ? 3.0 : 1.0);
         // spectral preconditioner (constant-coefficient part of shift*I - J inverted by FFT): nearly exact while the state is a
         // smooth perturbation of a uniform one, at any stiffness; pc_type 2 uses it until it converges badly (see below), 4 always
-        bool use_spec = h->spec.ok && h->use_frozen && (opts->pc_type == 4 || (opts->pc_type == 2 && stiff >= (fused_ok(h) ? h->spec_from : std::max(h->spec_from, 0.3)) && h->nsteps > h->spec.bad_until && !h->spec.user_off));      // (without the fused 2-D residual kernel a sweep costs more: 3-D at X = 0.29, 80 ms plain GMRES against 83 ms)
+        bool use_spec = !direct && h->spec.ok && h->use_frozen && (opts->pc_type == 4 || (opts->pc_type == 2 && stiff >= (fused_ok(h) ? h->spec_from : std::max(h->spec_from, 0.3)) && h->nsteps > h->spec.bad_until && !h->spec.user_off));      // (without the fused 2-D residual kernel a sweep costs more: 3-D at X = 0.29, 80 ms plain GMRES against 83 ms)
         if (use_spec) {
             if (!h->Zb && alloc_d(h, &h->Zb, (int64_t)h->restart_alloc * h->vlen)) { rc = KSFD_ENOMEM; goto out; }
             if (!h->spec.means_valid && (rc = spec_means(h))) goto out;
         }
-        const bool use_pc = !use_spec && h->mg_ok && h->use_frozen && (opts->pc_type == 1 || (opts->pc_type == 2 && stiff > mg_from));
+        const bool use_pc = !direct && !use_spec && h->mg_ok && h->use_frozen && (opts->pc_type == 1 || (opts->pc_type == 2 && stiff > mg_from));
         // pipelined solver: latency-bound iterations only (small local problem), not in the tiny-h regime where the
         // Pythagorean norm update cancels heavily (|w|^2/h_n^2 ~ 1/stiff^2) and gmres() takes its explicit second pass
         // polynomial preconditioner in the mildly stiff regime (pc_type 2 = automatic, 3 = polynomial whenever useful)
@@ -683,7 +693,7 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
             use_poly = h->poly_deg >= 1 && h->poly_max_deg >= 1;
         }
         const bool small = (double)h->G.F * (double)h->G.nloc <= 6.0e6;
-        const bool use_async = !use_spec && !use_pc && !use_poly && h->use_frozen && !(opts->reserved & 1) && stiff >= 1e-3 &&
+        const bool use_async = !direct && !use_spec && !use_pc && !use_poly && h->use_frozen && !(opts->reserved & 1) && stiff >= 1e-3 &&
                                (!h->ring || h->tr->device_allreduce()) &&
                                (h->async_mode == 1 || (h->async_mode == 2 && small));
         h->mg_use32 = opts->ksp_rtol >= 1e-7;          // fp32 level vectors inside the V cycle (mg_vcycle32); tight tolerances keep fp64
@@ -696,6 +706,9 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
         // multi-dot.  The b_j are kept in bstore (three vectors, allocated on first use); gb = their Gram matrix.
         const bool guess_on = (use_spec || use_pc) && fuse_stage && h->spec_guess && h->bstore;
         double gb[4][4];
+        // direct: the factors of shift*I - J(u_n) serve the four stages of this attempt (the coefficient planes are those of u_n here
+        // also with use_frozen off: ensure_coef)
+        if (direct && !(rc = ensure_coef(h, true))) rc = direct_factor(h, shift);
         for (int i = 0; i < 4 && !rc; i++) {
             const double *zin = h->u;
             double bnorm2 = -1.0;                 // ||b||^2 when the RHS kernel's epilogue delivered it
@@ -780,7 +793,10 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
                     }
                 }
             }
-            if (use_spec) {
+            if (direct) {
+                rc = direct_stage(h, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls);
+                st.pc_used |= 16;
+            } else if (use_spec) {
                 // defect correction with M^-1 (no Krylov vectors), flexible GMRES for the rest if it contracts slowly; the attempt
                 // is capped so that a state it does not suit costs little, then the V cycle / plain GMRES takes over
                 // (automatic choice: once a stage of this step has failed, the remaining stages go straight to the fallback, and a
@@ -820,7 +836,7 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
                 static const bool stage_trace = getenv("KSFD_STAGE_TRACE") != nullptr;     // iterations per stage system (diagnostics)
                 if (stage_trace) fprintf(stderr, "[stage %d] its %d rel %.2e guess %d\n", i, ls.its, ls.rel, sg.n);
             }
-            if (rc == KSFD_ELINEAR && !use_pc && h->mg_ok && h->use_frozen && opts->pc_type) {
+            if (rc == KSFD_ELINEAR && !direct && !use_pc && h->mg_ok && h->use_frozen && opts->pc_type) {
                 // unpreconditioned GMRES ran out of iterations: the multigrid-preconditioned solve of the same system
                 // is the remedy (the stiffness estimate above only knows the diffusion part of J)
                 rc = gmres(h, h->u, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, 1);
@@ -999,6 +1015,18 @@ extern "C" int ksfd_spectral_apply(ksfd_handle *h, double shift, const double *v
     if ((rc = upload(h, vh, layout, h->t2))) return rc;
     if ((rc = ensure_coef(h))) return rc;
     if ((rc = spec_means(h)) || (rc = spec_apply(h, shift, h->t2, h->t3))) return rc;
+    return download(h, h->t3, layout, outh);
+}
+extern "C" int ksfd_direct_apply(ksfd_handle *h, double shift, const double *vh, double *outh, int32_t layout)
+{
+    if (!h || !vh || !outh) return KSFD_EINVAL;
+    if (!isfinite(shift)) return fail(h, KSFD_EINVAL, "direct_apply: non-finite shift");
+    if (layout < 0 || layout > 2) return fail(h, KSFD_EINVAL, "bad layout %d", layout);
+    hipSetDevice(h->device);
+    int rc;
+    if ((rc = direct_guard(h))) return rc;
+    if ((rc = ensure_coef(h)) || (rc = direct_factor(h, shift))) return rc;
+    if ((rc = upload(h, vh, layout, h->t2)) || (rc = direct_solve(h, h->t2, h->t3))) return rc;
     return download(h, h->t3, layout, outh);
 }
 extern "C" int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enable)

@@ -1,0 +1,185 @@
+// libksfd_hip.so -- dense direct stage solver (pc_type 5): assembly of shift*I - J(u), LU factorization and triangular solves on the
+// device (kernels in lu.hip.h), iterative refinement against the frozen-coefficient Jacobian action
+// (part of the single translation unit ksfd_hip.hip; included after krylov.hip.h)
+#pragma once
+
+// Checked before anything is allocated or the state is touched: the dense factors of F*nloc unknowns take 8 (F*nloc)^2 bytes
+static int direct_guard(ksfd_handle *h)
+{
+    const double n = (double)h->G.F * (double)h->G.nloc;
+    if (n > (double)KSFD_DIRECT_MAX)
+        return fail(h, KSFD_EINVAL, "direct solver (pc_type 5): %.0f unknowns exceed KSFD_DIRECT_MAX = %d (%.1f GB of dense factors); "
+                                    "use pc_type 2", n, KSFD_DIRECT_MAX, 8.0 * n * n / 1e9);
+    if (h->ring) return fail(h, KSFD_EINVAL, "direct solver (pc_type 5): single rank only (this handle has a halo transport)");
+    return KSFD_OK;
+}
+
+static void direct_free(ksfd_handle *h)
+{
+    LUState &S = h->lu;
+    void *bufs[] = { S.A, S.piv, S.perm, S.info, S.col, S.val, S.y, S.z };
+    for (void *b : bufs) if (b) hipFree(b);
+    S = LUState();
+}
+
+static int direct_alloc(ksfd_handle *h)
+{
+    LUState &S = h->lu;
+    if (S.A) return KSFD_OK;
+    const int64_t n = (int64_t)h->G.F * h->G.nloc;
+    int64_t nr, nnz;
+    ksfd_jacobian_nnz(h, &nr, &nnz);
+    bool ok = hipMalloc((void **)&S.A, sizeof(double) * (size_t)n * (size_t)n) == hipSuccess;
+    ok = ok && hipMalloc((void **)&S.piv, sizeof(int) * (size_t)n) == hipSuccess;
+    ok = ok && hipMalloc((void **)&S.perm, sizeof(int) * (size_t)n) == hipSuccess;
+    ok = ok && hipMalloc((void **)&S.info, sizeof(int)) == hipSuccess;
+    ok = ok && hipMalloc((void **)&S.col, sizeof(long long) * (size_t)nnz) == hipSuccess;
+    ok = ok && hipMalloc((void **)&S.val, sizeof(double) * (size_t)nnz) == hipSuccess;
+    ok = ok && hipMalloc((void **)&S.y, sizeof(double) * (size_t)n) == hipSuccess;
+    ok = ok && hipMalloc((void **)&S.z, sizeof(double) * (size_t)n) == hipSuccess;
+    if (!ok) {
+        direct_free(h);
+        return fail(h, KSFD_ENOMEM, "direct solver: hipMalloc of the %.2f GB of dense factors failed", 8.0 * (double)n * (double)n / 1e9);
+    }
+    S.n = n;
+    S.nnz = nnz;
+    S.piv_h.assign((size_t)n, 0);
+    S.perm_h.assign((size_t)n, 0);
+    return KSFD_OK;
+}
+
+// A = shift*I - J at the resident coefficient planes (ensure_coef first), factored in place: P A = L U
+static int direct_factor(ksfd_handle *h, double shift)
+{
+    int rc;
+    if ((rc = direct_alloc(h))) return rc;
+    LUState &S = h->lu;
+    const KGeom &G = h->G;
+    const long long n = S.n;
+    const double dn = (double)n;
+    S.valid = false;
+    const int nbp = (int)std::min<long long>((G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 65535);
+    {
+        Scope sc(h, KC_MISC, 16.0 * (double)S.nnz + 8.0 * (3 + h->P.nlig) * (double)G.nloc);
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jac_csr<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, h->P, (const double *)h->coef,
+                                                  (long long)h->cfg.n[G.dim - 1], (long long)h->slow0, S.col, S.val));
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        Scope sc(h, KC_MISC, 8.0 * dn * dn);
+        HIPCHK(h, hipMemsetAsync(S.A, 0, sizeof(double) * (size_t)n * (size_t)n, h->st));
+    }
+    {
+        Scope sc(h, KC_MISC, 4.0);
+        HIPCHK(h, hipMemsetAsync(S.info, 0, sizeof(int), h->st));
+    }
+    {
+        Scope sc(h, KC_MISC, 32.0 * (double)S.nnz + 16.0 * dn);     // entries read, A entries read and written (strided)
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_lu_scatter<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, (long long)G.nloc, G.dim,
+                                                  (const long long *)S.col, (const double *)S.val, shift, S.A));
+    }
+    HIPCHK(h, hipGetLastError());
+    constexpr int NB = KSFD_LU_NB;
+    for (long long k0 = 0; k0 < n; k0 += NB) {
+        const long long k1 = std::min<long long>(k0 + NB, n), kw = k1 - k0;
+        for (long long j = k0; j < k1; j++) {
+            {
+                Scope sc(h, KC_MISC, 8.0 * (double)(n - j) + 32.0 * (double)kw);
+                hipLaunchKernelGGL(k_lu_pivot, dim3(1), dim3(KSFD_LU_PIVT), 0, h->st, S.A, n, j, k0, k1, S.piv, S.info);
+            }
+            if (j + 1 < n) {
+                const long long rows = n - j - 1;
+                Scope sc(h, KC_MISC, 8.0 * (double)rows * (1.0 + 2.0 * (double)(k1 - j - 1)));
+                hipLaunchKernelGGL(k_lu_panel_col, dim3((unsigned)((rows + KSFD_LU_ROWS - 1) / KSFD_LU_ROWS)), dim3(KSFD_LU_ROWS), 0, h->st,
+                                   S.A, n, j, k1, (const int *)S.info);
+            }
+        }
+        if (n > kw) {
+            Scope sc(h, KC_MISC, 32.0 * (double)kw * (double)(n - kw));
+            hipLaunchKernelGGL(k_lu_laswp, dim3((unsigned)((n - kw + KSFD_BLOCK - 1) / KSFD_BLOCK)), dim3(KSFD_BLOCK), 0, h->st,
+                               S.A, n, k0, k1, (const int *)S.piv, (const int *)S.info);
+        }
+        const long long m = n - k1;
+        if (m > 0) {
+            const int tiles = (int)((m + NB - 1) / NB);
+            {
+                Scope sc(h, KC_MISC, 8.0 * NB * NB * tiles + 16.0 * NB * (double)m);
+                hipLaunchKernelGGL(k_lu_trsm, dim3(tiles), dim3(KSFD_BLOCK), 0, h->st, S.A, n, k0, (const int *)S.info);
+            }
+            {
+                Scope sc(h, KC_MISC, 16.0 * (double)m * (double)m + 16.0 * NB * (double)m);   // A22 read + written, L21 and U12 read
+                hipLaunchKernelGGL(k_lu_gemm, dim3((unsigned)tiles * (unsigned)tiles), dim3(KSFD_BLOCK), 0, h->st, S.A, n, k0, tiles, (const int *)S.info);
+            }
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    int info = 0;
+    HIPCHK(h, hipMemcpyAsync(S.piv_h.data(), S.piv, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipMemcpyAsync(&info, S.info, sizeof(int), hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    h->n_host_sync++;
+    if (info) return fail(h, KSFD_ELINEAR, "direct solve: zero or non-finite pivot in column %d of shift*I - J (shift %.6g, %lld unknowns)", info - 1, shift, n);
+    // P b = the interchanges in order; as a gather: (P b)_i = b[perm[i]]
+    for (long long i = 0; i < n; i++) S.perm_h[i] = (int)i;
+    for (long long j = 0; j < n; j++) std::swap(S.perm_h[j], S.perm_h[S.piv_h[j]]);
+    HIPCHK(h, hipMemcpyAsync(S.perm, S.perm_h.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    S.valid = true;
+    S.shift = shift;
+    return KSFD_OK;
+}
+
+// x = U^-1 L^-1 P b; b and x in the ghosted SoA layout (distinct vectors)
+static int direct_solve(ksfd_handle *h, const double *b, double *x)
+{
+    LUState &S = h->lu;
+    if (!S.valid) return fail(h, KSFD_EINVAL, "direct solve without a factorization");
+    const KGeom &G = h->G;
+    const long long n = S.n;
+    constexpr int NB = KSFD_LU_NB;
+    const KLUVec V{ G.nloc, G.plane, (long long)G.ng * G.inner };
+    const long long nbk = (n + NB - 1) / NB;
+    for (long long kb = 0; kb < nbk; kb++) {
+        const long long k0 = kb * NB, kw = std::min<long long>(NB, n - k0), rows = n - k0 - kw;
+        const unsigned nblk = (unsigned)std::max<long long>(1, (rows + KSFD_LU_ROWS - 1) / KSFD_LU_ROWS);
+        Scope sc(h, KC_MISC, 8.0 * (double)(rows + kw) * (double)kw + 16.0 * (double)(rows + kw));
+        hipLaunchKernelGGL(k_lu_fwd, dim3(nblk), dim3(KSFD_LU_ROWS), 0, h->st, (const double *)S.A, n, k0, kb == 0 ? 1 : 0, V, b,
+                           (const int *)S.perm, S.y, S.z);
+    }
+    for (long long kb = nbk - 1; kb >= 0; kb--) {
+        const long long k0 = kb * NB, kw = std::min<long long>(NB, n - k0);
+        const unsigned nblk = (unsigned)std::max<long long>(1, (k0 + KSFD_LU_ROWS - 1) / KSFD_LU_ROWS);
+        Scope sc(h, KC_MISC, 8.0 * (double)(k0 + kw) * (double)kw + 16.0 * (double)(k0 + kw));
+        hipLaunchKernelGGL(k_lu_bwd, dim3(nblk), dim3(KSFD_LU_ROWS), 0, h->st, (const double *)S.A, n, k0, V, S.z, x);
+    }
+    HIPCHK(h, hipGetLastError());
+    return KSFD_OK;
+}
+
+// One stage system (shift*I - J) x = b of ksfd_step: solve, then the true residual b - A x from the frozen-coefficient Jacobian action
+// against max(ksp_rtol*||b||, ksp_atol) -- the test of every other solver -- with at most two refinement steps x += A^-1 r.
+// ls->its counts the solves (refinements included), ls->rel is the last true relative residual.
+static int direct_stage(ksfd_handle *h, double shift, const double *b, double *x, const ksfd_step_opts *opts, LinStats *ls)
+{
+    int rc;
+    ls->its = 0;
+    ls->rel = 0.0;
+    if ((rc = op_multidot(h, b, b, 0))) return rc;
+    const double bn = sqrt(h->hres[0]);
+    const double tol = std::max(opts->ksp_rtol * bn, opts->ksp_atol);
+    if ((rc = direct_solve(h, b, x))) return rc;
+    ls->its = 1;
+    for (int ref = 0;; ref++) {
+        if ((rc = halo(h, x)) || (rc = op_jvp_frozen(h, x, 2, shift, h->t3, b)) || (rc = op_multidot(h, h->t3, h->t3, 0))) return rc;
+        h->n_residual++;
+        const double rn = sqrt(h->hres[0]);
+        ls->rel = bn > 0.0 ? rn / bn : rn;
+        if (rn <= tol) return KSFD_OK;
+        if (ref == 2) return fail(h, KSFD_ELINEAR, "direct solve: true residual %.3e above %.3e after two refinement steps", rn, tol);
+        if ((rc = direct_solve(h, h->t3, h->t2))) return rc;
+        const double *xs[2] = { x, h->t2 };
+        const double a[2] = { 1.0, 1.0 };
+        if ((rc = op_lincomb(h, 2, xs, a, x))) return rc;
+        ls->its++;
+    }
+}

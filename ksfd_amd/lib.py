@@ -20,7 +20,8 @@ OK, EINVAL, EHIP, ENOMEM, ELINEAR, ENAN, EREJECT, ECOMM = range(8)
 # kernel classes of ksfd_profile / ksfd_bench_kernel
 KC_RHS, KC_JVP, KC_MULTIDOT, KC_GSUPDATE, KC_LINCOMB, KC_BASISAXPY, KC_FINISH, KC_REDUCE, \
     KC_GFIELD, KC_VELOCITY, KC_MISC, KC_HALO, KC_MG, KC_SPECTRAL = range(14)
-PC_NONE, PC_MULTIGRID, PC_POLYNOMIAL, PC_SPECTRAL = 1, 2, 4, 8      # bits of StepStats.pc_used
+PC_NONE, PC_MULTIGRID, PC_POLYNOMIAL, PC_SPECTRAL, PC_DIRECT = 1, 2, 4, 8, 16      # bits of StepStats.pc_used
+DIRECT_MAX = 32768      # KSFD_DIRECT_MAX: largest F * local points of the direct solver (pc_type 5)
 
 
 class KSFDError(RuntimeError):
@@ -73,7 +74,7 @@ ABI_SYMBOLS = [
     'ksfd_velocity', 'ksfd_velocity_max', 'ksfd_groom', 'ksfd_count_worms', 'ksfd_scale_rho', 'ksfd_mul_rho', 'ksfd_jacobian_nnz', 'ksfd_jacobian_csr', 'ksfd_set_state_random', 'ksfd_snapshot_begin', 'ksfd_snapshot_wait', 'ksfd_checkpoint',
     'ksfd_default_step_opts', 'ksfd_step', 'ksfd_get_last_error_vector', 'ksfd_set_profiling',
     'ksfd_get_profile', 'ksfd_synchronize', 'ksfd_bench_kernel', 'ksfd_set_tuning', 'ksfd_set_mg_params', 'ksfd_set_poly_params',
-    'ksfd_spectral_apply', 'ksfd_set_spectral_params',
+    'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply',
 ]
 
 
@@ -136,6 +137,7 @@ def load():
     L.ksfd_set_poly_params.argtypes = [vp, C.c_int32, C.c_double, C.c_double]
     L.ksfd_spectral_apply.argtypes = [vp, C.c_double, dp, dp, C.c_int32]
     L.ksfd_set_spectral_params.argtypes = [vp, C.c_double, C.c_int32]
+    L.ksfd_direct_apply.argtypes = [vp, C.c_double, dp, dp, C.c_int32]
     _lib = L
     return L
 
@@ -365,6 +367,13 @@ class KSFDHip:
         out = np.empty(self.nlocal)
         v = self._vec(v)
         self._chk(self.L.ksfd_spectral_apply(self.h, float(shift), _dp(v), _dp(out), layout))
+        return out
+
+    def direct_apply(self, shift, v, layout=SOA):
+        """z = (shift*I - J)^-1 v by the direct solver's dense LU (pc_type 5), J = the Jacobian at the resident state (test entry)"""
+        out = np.empty(self.nlocal)
+        v = self._vec(v)
+        self._chk(self.L.ksfd_direct_apply(self.h, float(shift), _dp(v), _dp(out), layout))
         return out
 
     def set_spectral_params(self, from_stiffness=0.0, enable=-1):

@@ -304,6 +304,10 @@ def decode_sources(sargs, params):
     return srcs
 
 
+# -ksfd_pc_type spelling -> ksfd_step_opts.pc_type (include/ksfd_hip.h)
+KSFD_PC_TYPES = {'auto': 2, 'none': 0, 'mg': 1, 'poly': 3, 'spectral': 4, 'lu': 5}
+
+
 def step_opts_from(params, petsc_args):
     """rtol/atol (ksfdsolver2.py:720-721) + the TSAdapt flags of the --petsc block (options84:47-67)."""
     v = params.values0
@@ -334,6 +338,11 @@ def step_opts_from(params, petsc_args):
             o.ksp_restart = int(nxt)
         elif k == '-ksp_max_it' and nxt:
             o.ksp_max_it = int(nxt)
+        elif k == '-ksfd_pc_type':
+            # stage solver of the HIP stepper; a bare -pc_type (the reference's lu) keeps the automatic choice
+            if nxt not in KSFD_PC_TYPES:
+                raise ValueError('-ksfd_pc_type must be one of %s, got %s' % ('/'.join(KSFD_PC_TYPES), nxt))
+            o.pc_type = KSFD_PC_TYPES[nxt]
         i += 2 if nxt is not None else 1
     return o
 
