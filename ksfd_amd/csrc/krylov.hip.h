@@ -1,6 +1,6 @@
 // libksfd_hip.so -- Chebyshev polynomial preconditioner, flexible/recycled GMRES(m), pipelined GMRES
 // (part of the single translation unit ksfd_hip.hip; included from there in this order:
-//  handle.hip.h, ops.hip.h, mg_host.hip.h, krylov.hip.h)
+//  handle.hip.h, ops.hip.h, spectral_host.hip.h, mg_host.hip.h, krylov.hip.h, lu_host.hip.h)
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // Polynomial preconditioner.  In the non-stiff regime (h*gamma*lambda_max(J) of order 1..10, the regime of the
@@ -16,7 +16,7 @@ static int est_lambda_max(ksfd_handle *h, double shift, int nits)
     int rc;
     if (!h->pvec) {
         if (alloc_d(h, &h->pvec, h->vlen)) return KSFD_ENOMEM;
-        int nb = (int)std::min<long long>((h->vlen + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+        const int nb = blocks_for(h->vlen);
         hipLaunchKernelGGL(k_hash_fill, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, (long long)h->vlen, h->pvec);
         if ((rc = op_multidot(h, h->pvec, h->pvec, 0))) return rc;
         const double n0 = sqrt(h->hres[0]);
@@ -471,7 +471,7 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
     float *r32 = reinterpret_cast<float *>(h->Z);  // ... kept in fp32 while only the preconditioner reads it
     double rn = bn, rprev = bn;
     // fp32 residual with the norm from the store epilogue: the 2-D strip kernel, or the 3-D one when its wave count fits the partial buffer
-    const bool fused = fused_ok(h) || (strip3d_ok(h) && (j3l_ok(h) ? (long long)make_k3d_lds(h).nblocks * KSFD_J3L_ROWS : (long long)make_k3d(h).nblocks * make_k3d(h).rows) <= part_capacity());
+    const bool fused = fused_ok(h) || (strip3d_ok(h) && k3d_waves(h) <= part_capacity());
     bool slow = false;
     // Predicted last sweep.  Every sweep multiplies the residual by (I - A M^-1); the four stage systems of a step share that
     // operator, so its contraction has been MEASURED by the time a solve is about to finish: rho_hat = the largest ratio

@@ -446,9 +446,8 @@ static int velocity_common(ksfd_handle *h, const double *uin, double *vel_dev, d
         Gplane = h->coef + G.plane;
     } else {
         if ((rc = halo(h, (double *)uin))) return rc;
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
         Scope sc(h, KC_GFIELD, 8.0 * (G.F + 1) * (double)G.plane);
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_gfield<NL, false>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, h->P, uin, (const double *)nullptr, h->Gb, (double *)nullptr));
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_gfield<NL, false>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, h->P, uin, (const double *)nullptr, h->Gb, (double *)nullptr));
     }
     int nb = (int)std::min<long long>((G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 1024);
     if (vmax && !vel_dev && G.dim == 2 && (G.nx % 2 == 0) && G.nx >= 4) {
@@ -725,7 +724,7 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
                 // ||b||^2 from the store epilogue (2-D strip kernel), and with it the inner products of b_i with the right-hand sides the stage
                 // guess is built from (the multi-dot below would read all of them again)
                 const int gdot_j0 = std::max(0, i - h->guess_max), gdot_n = (guess_on && i > 0 && h->rhs_dots) ? i - gdot_j0 : 0;
-                const bool rhs_norm = use_spec && fused_ok(h) && (!(guess_on && i > 0) || (gdot_n > 0 && gdot_n <= 2 && (long long)make_strips(h).nstrips * make_strips(h).nseg * (1 + gdot_n) <= part_capacity()));
+                const bool rhs_norm = use_spec && fused_ok(h) && (!(guess_on && i > 0) || (gdot_n > 0 && gdot_n <= 2 && strip_waves(h) * (1 + gdot_n) <= part_capacity()));
                 rhs_dots_done = rhs_norm && gdot_n > 0;
                 // ghosts of the newest stage vector (earlier ones done): exchanged behind the interior rows of the RHS (op_rhs)
                 if ((rc = op_rhs(h, h->u, i, bcur, &cmb, rhs_norm, i > 0 ? h->Y + (int64_t)(i - 1) * vs : nullptr, rhs_dots_done ? gdot_n : 0,

@@ -1,6 +1,6 @@
 // libksfd_hip.so -- host side of the geometric multigrid preconditioner (kernels and rationale: mg.hip.h)
 // (part of the single translation unit ksfd_hip.hip; included from there in this order:
-//  handle.hip.h, ops.hip.h, mg_host.hip.h, krylov.hip.h)
+//  handle.hip.h, ops.hip.h, spectral_host.hip.h, mg_host.hip.h, krylov.hip.h, lu_host.hip.h)
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // multigrid preconditioner (host side; kernels and rationale in mg.hip.h)
@@ -77,7 +77,7 @@ static int mg_build(ksfd_handle *h)
 // transfer operators, 2-D or 3-D by the level geometry
 static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const double *fine, double *coarse)
 {
-    int nb = (int)std::min<long long>((Lc.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+    int nb = point_blocks(Lc.G);
     if (Lf.G.dim == 1)
         hipLaunchKernelGGL(k_restrict1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
                            fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
@@ -90,7 +90,7 @@ static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np,
 }
 static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const double *coarse, double *fine)
 {
-    int nb = (int)std::min<long long>((Lf.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+    int nb = point_blocks(Lf.G);
     if (Lf.G.dim == 1)
         hipLaunchKernelGGL(k_prolong_add1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
                            coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
@@ -111,8 +111,6 @@ static int mg_halo(ksfd_handle *h, MGLevel &L, double *v, int np)
     return KSFD_OK;
 }
 
-// out = J v | shift v - J v | yadd - (shift v - J v) on level L
-// sm != NULL: modes 5 / 6, smoother algebra in the epilogue (2-D strip kernel and generic kernel only: see mg_can_fuse)
 // ... of an fp32 level vector: it travels through the double-typed transport as half as many doubles (nx is even on these levels)
 static int mg_halo32(ksfd_handle *h, MGLevel &L, float *v, int np)
 {
@@ -129,6 +127,8 @@ static bool mg_can_fuse(const ksfd_handle *h, const MGLevel &L)
     return h->mg_fuse && !strip3d;
 }
 
+// out = J v | shift v - J v | yadd - (shift v - J v) on level L
+// sm != NULL: modes 5 / 6, smoother algebra in the epilogue (2-D strip kernel and generic kernel only: see mg_can_fuse)
 static int mg_op(ksfd_handle *h, MGLevel &L, const double *v, int mode, double shift, double *out, const double *yadd,
                  const KSmooth *sm = nullptr)
 {
@@ -139,18 +139,7 @@ static int mg_op(ksfd_handle *h, MGLevel &L, const double *v, int mode, double s
     const double by = 8.0 * ((3 + h->P.nlig) + G.F + (mode == 5 ? 3.0 * G.F + 0.5 * G.F * G.F : mode == 6 ? 3.0 * G.F + 0.5 * G.F * G.F : G.F + (mode == 2 ? G.F : 0))) * (double)G.nloc;
     const KSmooth S = sm ? *sm : KSmooth{};
     if (G.dim == 2 && h->use_fused && (G.nx % 2 == 0) && G.nx >= 16 && h->P.nlig <= 4) {
-        KStrips K;
-        K.nstrips = (int)((G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
-        K.yseg = h->yseg_jvp;
-        {
-            long long fit = (long long)K.nstrips * G.sloc / 4096;
-            if (fit < 2) fit = 2;
-            if (fit < K.yseg) K.yseg = (int)fit;
-        }
-        K.nseg = (int)((G.sloc + K.yseg - 1) / K.yseg);
-        K.seg0 = 0; K.seg_stride = 1;
-        long long nb = ((long long)K.nstrips * K.nseg + 3) / 4;
-        K.nblocks = (int)((nb + 7) / 8 * 8);
+        const KStrips K = strips_for(G, h->yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
         // level 0 reads the fp32 copy of the coefficient planes when there is one (the V cycle is a preconditioner: see poly_apply)
         const float *c32 = (&L == &h->mg[0] && h->poly_fp32) ? h->coef32 : nullptr;
         Scope sc(h, cls, by - (c32 ? 4.0 * (3 + h->P.nlig) * (double)G.nloc : 0.0));
@@ -163,28 +152,15 @@ static int mg_op(ksfd_handle *h, MGLevel &L, const double *v, int mode, double s
         } else
         NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, (const double *)L.coef, v, mode, shift, out, yadd));
     } else if (G.dim == 3 && h->use_fused && (G.nx % 2 == 0) && G.nx >= 16 && h->P.nlig <= 4) {
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
-        K3D K;
-        K.rows = 4; K.sync = 0;
-        K.nstrips = (int)((G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
-        K.nygrp = (int)((G.ny + 3) / 4);
-        K.zseg = h->zseg;
-        {
-            long long fit = (long long)K.nstrips * K.nygrp * G.sloc / 1024;
-            if (fit < 2) fit = 2;
-            if (fit < K.zseg) K.zseg = (int)fit;
-        }
-        K.nzseg = (int)((G.sloc + K.zseg - 1) / K.zseg);
-        long long nb3 = (long long)K.nstrips * K.nygrp * K.nzseg;
-        K.nblocks = (int)((nb3 + 7) / 8 * 8);
+        const K3D K = k3d_for(G, 4, 0, h->zseg, 1024);
         Scope sc(h, cls, by + 8.0 * G.plane);
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, (const double *)L.coef, v, L.dG));
+        dg_pass(h, G, L.coef, v, L.dG, -1);
         NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp3d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, (const double *)L.coef, v, (const double *)L.dG, mode, shift, out, yadd));
     } else {
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
         Scope sc(h, cls, by + 8.0 * G.plane);
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, (const double *)L.coef, v, L.dG));
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, L.P, (const double *)L.coef, v, (const double *)(L.coef + G.plane), (const double *)L.dG, mode, shift, out, yadd, 0.0, 0.0, S));
+        dg_pass(h, G, L.coef, v, L.dG, -1);
+        // (on plane_blocks, not point_blocks as op_jvp_frozen has it: both are grid-stride launches)
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, L.P, (const double *)L.coef, v, (const double *)(L.coef + G.plane), (const double *)L.dG, mode, shift, out, yadd, 0.0, 0.0, S));
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
@@ -220,7 +196,7 @@ static int mg_restrict_coefs(ksfd_handle *h)
         if ((rc = mg_halo(h, Lc, Lc.coef, np))) return rc;       // fine ghosts were valid; now the coarse ones are too
         if (Lc.coef32) {
             // the fp32 cycle reads an fp32 copy (the same full weighting of the fine fp64 planes, rounded once)
-            int nb = (int)std::min<long long>((Lc.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+            int nb = point_blocks(Lc.G);
             {
                 Scope sc(h, KC_MG, np * (8.0 * Lf.G.nloc + 4.0 * Lc.G.nloc));
                 hipLaunchKernelGGL((k_restrict2d<double, float>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
@@ -241,7 +217,7 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
     for (size_t l = 0; l < h->mg.size(); l++) {
         MGLevel &L = h->mg[l];
         const int F = L.G.F;
-        int nb = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+        int nb = point_blocks(L.G);
         {
             Scope sc(h, KC_MG, 8.0 * (3 + h->P.nlig + F * F) * L.G.nloc);
             NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_blockdiag_inv<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G, L.P, (const double *)L.coef, shift, L.dinv));
@@ -296,7 +272,7 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
     // Fusions: a zero guess writes x = d_0 directly; the last sweep folds "x += d_old + d_new" into one kernel.
     int rc;
     const int F = L.G.F;
-    const int nb = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+    const int nb = point_blocks(L.G);
     const double lmax = L.lam_max, lmin = lmax / ratio;
     const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
     const long long off = L.kv.off;     // owned rows start here inside a (ghosted) plane
@@ -449,18 +425,7 @@ static int mg_op32(ksfd_handle *h, MGLevel &L, const float *v, int mode, double 
     const float *c32 = (&L == &h->mg[0]) ? (h->poly_fp32 ? h->coef32 : nullptr) : L.coef32;
     // planes moved (in units of 8 B per point): coefficients, v, per mode: 2: yadd + out; 5: yadd, Dinv, r, d; 6: Dinv, rr, x in and out
     const double by = ((c32 ? 4.0 : 8.0) * (3 + h->P.nlig) + 4.0 * G.F + (mode == 2 ? 8.0 * G.F : 12.0 * G.F + 4.0 * G.F * G.F + ((sm && sm->x64) ? 4.0 * G.F : 0.0))) * (double)G.nloc;
-    KStrips K;
-    K.nstrips = (int)((G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
-    K.yseg = h->yseg_jvp;
-    {
-        long long fit = (long long)K.nstrips * G.sloc / 4096;
-        if (fit < 2) fit = 2;
-        if (fit < K.yseg) K.yseg = (int)fit;
-    }
-    K.nseg = (int)((G.sloc + K.yseg - 1) / K.yseg);
-    K.seg0 = 0; K.seg_stride = 1;
-    long long nb = ((long long)K.nstrips * K.nseg + 3) / 4;
-    K.nblocks = (int)((nb + 7) / 8 * 8);
+    const KStrips K = strips_for(G, h->yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
     const KSmoothT<float> S = sm ? *sm : KSmoothT<float>{};
     Scope sc(h, cls, by);
     if (sm && c32) {
@@ -484,8 +449,8 @@ static int mg_coarse_correction32(ksfd_handle *h, size_t l, double shift)
     int rc;
     MGLevel &L = h->mg[l], &Lc = h->mg[l + 1];
     const int F = L.G.F;
-    const int nbr = (int)std::min<long long>((Lc.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
-    const int nbp = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+    const int nbr = point_blocks(Lc.G);
+    const int nbp = point_blocks(L.G);
     if ((rc = mg_halo32(h, L, L.r32, F))) return rc;                    // restriction reads fine rows -1 and sloc
     {
         Scope sc(h, KC_MG, F * (4.0 * L.G.nloc + (Lc.f32 ? 4.0 : 8.0) * Lc.G.nloc));
@@ -511,7 +476,7 @@ static int mg_vcycle32(ksfd_handle *h, size_t l, double shift, const double *b64
     int rc;
     MGLevel &L = h->mg[l];
     const int F = L.G.F;
-    const int nb = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+    const int nb = point_blocks(L.G);
     const double lmax = L.lam_max, lmin = lmax / h->mg_ratio;
     const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
     const double rho0 = 1.0 / sig1, rhon = 1.0 / (2.0 * sig1 - rho0);

@@ -1,6 +1,6 @@
-// libksfd_hip.so -- halo exchange, host-visible reductions, launch wrappers of every kernel class, host<->device layouts
+// libksfd_hip.so -- halo exchange, host-visible reductions, launch geometry, launch wrappers of every kernel class, host<->device layouts
 // (part of the single translation unit ksfd_hip.hip; included from there in this order:
-//  handle.hip.h, ops.hip.h, mg_host.hip.h, krylov.hip.h)
+//  handle.hip.h, ops.hip.h, spectral_host.hip.h, mg_host.hip.h, krylov.hip.h, lu_host.hip.h)
 #pragma once
 // ---- halo exchange (DMDA globalToLocal stand-in, KSFD/ksfdsym.py:919-920) -----------------------
 static int halo(ksfd_handle *h, double *vec)
@@ -13,7 +13,6 @@ static int halo(ksfd_handle *h, double *vec)
 }
 
 // ---- reductions to the host ------------------------------------------------------------------
-// part holds `rows` rows of `nblk` partials; result lands in h->hres[0..rows)
 // host side of the zero-copy hand-over: spin until the kernel has raised the flag (with a look at the stream now and then,
 // so that a faulted launch turns into an error instead of a hang)
 static int spin_for(ksfd_handle *h, unsigned long long seq)
@@ -31,6 +30,7 @@ static int spin_for(ksfd_handle *h, unsigned long long seq)
     }
 }
 
+// part holds `rows` rows of `nblk` partials; result lands in h->hres[0..rows)
 static int reduce_rows(ksfd_handle *h, int rows, int nblk, int op)
 {
     // several ranks with a device-side all-reduce (RCCL): a one-block k_publish behind the all-reduce hands the result over
@@ -77,32 +77,52 @@ static int reduce_rows(ksfd_handle *h, int rows, int nblk, int op)
     default: { constexpr int NL = 12; CALL; } break;                                               \
     }
 
-static KStrips make_strips(const ksfd_handle *h, bool jvp = false)
+// ---- launch geometry (of a KGeom, not of the handle: the multigrid levels have their own) -------
+// grid of a grid-stride launch over n items / the points of a plane with its ghost rows / the owned points
+static inline int blocks_for(long long n) { return (int)std::min<long long>((n + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096); }
+static inline int plane_blocks(const KGeom &G) { return blocks_for(G.plane); }
+static inline int point_blocks(const KGeom &G) { return blocks_for(G.nloc); }
+// strip launches: whole rounds over the 8 XCDs (ksfd_xcd_remap)
+static inline int round8(long long nb) { return (int)((nb + 7) / 8 * 8); }
+
+// segments seg0, seg0 + seg_stride, ... (nseg of them) of the strips K: four waves to a block
+static KStrips strips_sub(KStrips K, int seg0, int seg_stride, int nseg)
+{
+    K.seg0 = seg0; K.seg_stride = seg_stride; K.nseg = nseg;
+    K.nblocks = round8(((long long)K.nstrips * nseg + 3) / 4);
+    return K;
+}
+// all row segments of G in strips of at most yseg rows.  Small grids: shorter segments so that there are about wave_target waves
+// to fill 256 CUs (a wave costs ~1 us per row it marches; the 4 halo rows per segment are L2 hits at these sizes)
+static KStrips strips_for(const KGeom &G, int yseg, long long wave_target)
 {
     KStrips S;
-    S.nstrips = (int)((h->G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
-    S.yseg = jvp ? h->yseg_jvp : h->yseg;
-    // small grids: shorter segments so that there are enough waves to fill 256 CUs (a wave costs ~1 us per row it
-    // marches; the 4 halo rows per segment are L2 hits at these sizes)
-    {
-        static const long long t_jvp = getenv("KSFD_WAVES_JVP") ? atoll(getenv("KSFD_WAVES_JVP")) : 4096;       // experiments (tools/yseg_sweep.py)
-        static const long long t_rhs = getenv("KSFD_WAVES_RHS") ? atoll(getenv("KSFD_WAVES_RHS")) : 6144;
-        const long long target = jvp ? t_jvp : t_rhs;
-        long long fit = (long long)S.nstrips * h->G.sloc / target;
-        if (fit < 2) fit = 2;
-        if (fit < S.yseg) S.yseg = (int)fit;
-    }
-    S.nseg = (int)((h->G.sloc + S.yseg - 1) / S.yseg);
-    S.seg0 = 0;
-    S.seg_stride = 1;
-    long long waves = (long long)S.nstrips * S.nseg;
-    long long nb = (waves + 3) / 4;
-    nb = (nb + 7) / 8 * 8;
-    S.nblocks = (int)nb;
-    return S;
+    S.nstrips = (int)((G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
+    const long long fit = std::max<long long>((long long)S.nstrips * G.sloc / wave_target, 2);
+    S.yseg = (int)std::min<long long>(yseg, fit);
+    return strips_sub(S, 0, 1, (int)((G.sloc + S.yseg - 1) / S.yseg));
+}
+static KStrips make_strips(const ksfd_handle *h, bool jvp = false)
+{
+    static const long long t_jvp = getenv("KSFD_WAVES_JVP") ? atoll(getenv("KSFD_WAVES_JVP")) : 4096;       // experiments (tools/yseg_sweep.py)
+    static const long long t_rhs = getenv("KSFD_WAVES_RHS") ? atoll(getenv("KSFD_WAVES_RHS")) : 6144;
+    return strips_for(h->G, jvp ? h->yseg_jvp : h->yseg, jvp ? t_jvp : t_rhs);
 }
 
-// launch geometry of the 3-D z-marching strip kernels
+// launch geometry of the 3-D z-marching strip kernels: blocks of `rows` y rows, z segments of at most zseg planes, shorter when that
+// is what it takes to have about block_target blocks for 256 CUs
+static K3D k3d_for(const KGeom &G, int rows, int sync, int zseg, long long block_target)
+{
+    K3D K;
+    K.rows = rows; K.sync = sync;
+    K.nstrips = (int)((G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
+    K.nygrp = (int)((G.ny + rows - 1) / rows);
+    const long long fit = std::max<long long>((long long)K.nstrips * K.nygrp * G.sloc / block_target, 2);
+    K.zseg = (int)std::min<long long>(zseg, fit);
+    K.nzseg = (int)((G.sloc + K.zseg - 1) / K.zseg);
+    K.nblocks = round8((long long)K.nstrips * K.nygrp * K.nzseg);
+    return K;
+}
 // rows of y per block of the 3-D strip kernels (K3D).  Measured at 512^3 (bench.py --dim 3, ms per step): 4 rows 110.6, 4 rows with a
 // barrier per plane 107.8, 8 rows 111.9, 8 rows + barrier 115.5 -- so 4 rows marching in step; KSFD_ROWS3D=8 / KSFD_SYNC3D=0 for measurements
 static int rows3d(const ksfd_handle *h, long long ny)
@@ -113,25 +133,9 @@ static int rows3d(const ksfd_handle *h, long long ny)
 }
 static K3D make_k3d(const ksfd_handle *h)
 {
-    const KGeom &G = h->G;
-    K3D K;
-    K.rows = rows3d(h, G.ny);
-    {
-        static const int sync_env = getenv("KSFD_SYNC3D") ? atoi(getenv("KSFD_SYNC3D")) : 1;
-        K.sync = sync_env && (G.ny % K.rows == 0);
-    }
-    K.nstrips = (int)((G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
-    K.nygrp = (int)((G.ny + K.rows - 1) / K.rows);
-    K.zseg = h->zseg;
-    {
-        long long fit = (long long)K.nstrips * K.nygrp * G.sloc / (K.rows == 8 ? 512 : 1024);      // enough blocks for 256 CUs
-        if (fit < 2) fit = 2;
-        if (fit < K.zseg) K.zseg = (int)fit;
-    }
-    K.nzseg = (int)((G.sloc + K.zseg - 1) / K.zseg);
-    const long long nb3 = (long long)K.nstrips * K.nygrp * K.nzseg;
-    K.nblocks = (int)((nb3 + 7) / 8 * 8);
-    return K;
+    static const int sync_env = getenv("KSFD_SYNC3D") ? atoi(getenv("KSFD_SYNC3D")) : 1;
+    const int rows = rows3d(h, h->G.ny);
+    return k3d_for(h->G, rows, sync_env && (h->G.ny % rows == 0), h->zseg, rows == 8 ? 512 : 1024);
 }
 
 // second-generation 3-D Jacobian action (k_jvp3d_lds: y-neighbours through the LDS, dG on the fly): one or two ligands, ny a multiple of
@@ -155,24 +159,14 @@ static bool j3l_ok(ksfd_handle *h)
     }
     return h->j3l_usable;
 }
-static K3D make_k3d_lds(const ksfd_handle *h)
-{
-    const KGeom &G = h->G;
-    K3D K;
-    K.rows = KSFD_J3L_ROWS; K.sync = 0;
-    K.nstrips = (int)((G.nx + KSFD_STRIP_OUT - 1) / KSFD_STRIP_OUT);
-    K.nygrp = (int)(G.ny / KSFD_J3L_ROWS);
-    K.zseg = h->zseg;
-    {
-        long long fit = (long long)K.nstrips * K.nygrp * G.sloc / 1024;      // one block per CU: four rounds of blocks at least
-        if (fit < 2) fit = 2;
-        if (fit < K.zseg) K.zseg = (int)fit;
-    }
-    K.nzseg = (int)((G.sloc + K.zseg - 1) / K.zseg);
-    const long long nb3 = (long long)K.nstrips * K.nygrp * K.nzseg;
-    K.nblocks = (int)((nb3 + 7) / 8 * 8);
-    return K;
-}
+// (one block per CU: four rounds of blocks at least)
+static K3D make_k3d_lds(const ksfd_handle *h) { return k3d_for(h->G, KSFD_J3L_ROWS, 0, h->zseg, 1024); }
+
+// wave counts of the strip launches: the fused norms leave one partial per wave in h->part
+static inline long long part_capacity() { return (long long)(2 * KSFD_MAXDOT + 4) * 4096; }      // of h->part in doubles (ksfd_create)
+static long long strip_waves(const ksfd_handle *h, bool jvp = false) { const KStrips K = make_strips(h, jvp); return (long long)K.nstrips * K.nseg; }
+static long long k3d_waves(ksfd_handle *h) { const K3D K = j3l_ok(h) ? make_k3d_lds(h) : make_k3d(h); return (long long)K.nblocks * K.rows; }
+
 // launch of k_jvp3d_lds for 1 or 2 ligands and the storage type of the output
 template <typename TO>
 static void j3l_launch(ksfd_handle *h, const K3D &K, const double *v, int mode, double shift, TO *out, const double *yadd, double alpha, double beta, double *normpart)
@@ -189,14 +183,56 @@ static KSrc src_of(const ksfd_handle *h, int stage)
     return s;
 }
 
-// out = f(u) (+sources of `stage`); u must have valid ghosts when size>1
-// capacity of h->part in doubles (ksfd_create)
-static inline long long part_capacity() { return (long long)(2 * KSFD_MAXDOT + 4) * 4096; }
+// dG plane of the direction v from the frozen coefficient planes: the pass in front of the 3-D (first generation) and generic
+// Jacobian-action kernels.  cls < 0: the launch rides in the caller's Scope (multigrid levels charge both kernels as one)
+static void dg_pass(ksfd_handle *h, const KGeom &G, const double *coef, const double *v, double *dG, int cls = KC_GFIELD)
+{
+    auto launch = [&] { NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, coef, v, dG)); };
+    if (cls < 0) return launch();
+    Scope sc(h, cls, 8.0 * (2 + h->P.nlig + G.F) * (double)G.plane);
+    launch();
+}
 
+// Bytes per point a Jacobian action moves, by the storage types of its operands: impl = ncoef coefficient planes + v + out (+ yadd in
+// modes 2 and 3) + extra, alg = SURVEY.md 8d: read u, v, write out (+ the fused vector operand) in fp64.  ncoef is 3 + nlig where the
+// kernel reads the coefficient planes, 3 on the paths where a dG plane pass stands in for them.
+struct JvpBytes { double impl, alg; };
+template <typename TC = double, typename TV = double, typename TY = double, typename TO = double>
+static JvpBytes jvp_bytes(const KGeom &G, int mode, double ncoef, double extra = 0.0)
+{
+    const double y = (mode == 2 || mode == 3) ? G.F : 0;
+    return { ncoef * sizeof(TC) + G.F * (double)(sizeof(TV) + sizeof(TO)) + y * (double)sizeof(TY) + extra, 8.0 * (3.0 * G.F + y) };
+}
+
+// A strip launch whose input needs its ghost rows exchanged first (slab ranks), with the exchange hidden behind the interior rows:
+//   compute stream: [interior segments]                      [two boundary segments]
+//   comm stream   :   wait(input ready) -> ghost rows <- ring neighbours -> signal
+// Interior segments read owned rows only; the first and last segment are the only readers of ghost rows.  Without h->overlap or
+// with fewer than 3 segments: exchange on the compute stream, then one launch of everything.
+// exchange(stream) -> nonzero on failure; launch(strips, share of the work, normpart) -> KSFD error code.  normpart: per-wave
+// partials numbered over ALL segments of K (interior launch first, then the two boundary segments)
+template <typename Exchange, typename Launch>
+static int with_halo_overlap(ksfd_handle *h, const KStrips &K, double *normpart, Exchange exchange, Launch launch)
+{
+    int rc;
+    const bool ovl = h->overlap && K.nseg >= 3;
+    if (ovl) {
+        HIPCHK(h, hipEventRecord(h->ev_ready, h->st));
+        if ((rc = launch(strips_sub(K, 1, 1, K.nseg - 2), (double)(K.nseg - 2) / K.nseg, normpart))) return rc;
+        HIPCHK(h, hipStreamWaitEvent(h->st_comm, h->ev_ready, 0));
+    }
+    if (exchange(ovl ? h->st_comm : h->st)) return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
+    if (!ovl) return launch(K, 1.0, normpart);
+    HIPCHK(h, hipEventRecord(h->ev_halo, h->st_comm));
+    HIPCHK(h, hipStreamWaitEvent(h->st, h->ev_halo, 0));
+    return launch(strips_sub(K, 0, K.nseg - 1, 2), 2.0 / K.nseg, normpart ? normpart + (long long)K.nstrips * (K.nseg - 2) : nullptr);
+}
+
+// out = f(u) (+sources of `stage`); u must have valid ghosts when size>1
 // want_norm (fused 2-D path only): ||out||^2 lands in h->hres[0] without a pass of its own (per-wave partials in the store epilogue)
 // halo_vec (slab ranks): a vector among the inputs whose ghost rows have NOT been exchanged yet (the newest stage vector).  On the
-// 2-D strip path they travel on the communication stream while the interior segments are computed -- the scheme of
-// op_jvp_frozen_halo: only the first and the last segment read ghost rows -- elsewhere they are exchanged first.
+// 2-D strip path they travel on the communication stream while the interior segments are computed (with_halo_overlap); elsewhere
+// they are exchanged first.
 // ndots (with want_norm, fused 2-D path): <out, dotv + q*vlen>, q < ndots <= 2, land in h->hres[1 + q] beside ||out||^2 in h->hres[0]
 static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const KComb *cmb = nullptr, bool want_norm = false, double *halo_vec = nullptr,
                   int ndots = 0, const double *dotv = nullptr)
@@ -209,42 +245,25 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
     if (fused_ok(h)) {
         KStrips K = make_strips(h);
         KComb C = cmb ? *cmb : KComb{};
-        const long long nwaves = (long long)K.nstrips * K.nseg;
+        const long long nwaves = strip_waves(h);
         const bool fused_norm = want_norm && nwaves * (1 + ndots) <= part_capacity();
         KDots D = KDots{};
         if (fused_norm && ndots > 0) { D.n = std::min(ndots, 2); D.stride = nwaves; for (int q = 0; q < D.n; q++) D.v[q] = dotv + (int64_t)q * h->vlen; }
         // the vectors added at the store are the ones the stage argument is formed from: one read serves both (k_rhs2d_fused<NL, true>)
         bool carry = h->rhs_carry && C.nout > 0 && C.nout == C.nin;
         for (int j = 0; j < C.nout && carry; j++) carry = C.yin[j] == C.yout[j];
-        auto launch = [&](const KStrips &Kx, double frac, double *np) {
+        auto launch = [&](const KStrips &Kx, double frac, double *np) -> int {
             Scope sc(h, KC_RHS, vbytes(h, 2 + C.nin + (carry ? 0 : C.nout) + D.n) * frac, vbytes(h, 2 + C.nin + C.nout + D.n) * frac);
             if (carry) { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL, true>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D)); }
             else { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D)); }
+            return KSFD_OK;
         };
         double *np = fused_norm ? h->part : (double *)nullptr;
-        const bool ovl = halo_vec && h->overlap && K.nseg >= 3;
-        if (halo_vec && !ovl) { int rc = halo(h, halo_vec); if (rc) return rc; }
-        if (!ovl) launch(K, 1.0, np);
-        else {
-            HIPCHK(h, hipEventRecord(h->ev_ready, h->st));
-            KStrips Ki = K;
-            Ki.seg0 = 1; Ki.seg_stride = 1; Ki.nseg = K.nseg - 2;
-            long long nb = ((long long)Ki.nstrips * Ki.nseg + 3) / 4;
-            Ki.nblocks = (int)((nb + 7) / 8 * 8);
-            launch(Ki, (double)Ki.nseg / K.nseg, np);
-            HIPCHK(h, hipStreamWaitEvent(h->st_comm, h->ev_ready, 0));
-            {
-                Scope sc(h, KC_HALO, 4.0 * 2.0 * 8.0 * G.F * (double)G.inner * 2.0);
-                if (h->tr->exchange(halo_vec, G.F, G.plane, G.inner, G.sloc, G.ng, h->st_comm)) return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
-            }
-            HIPCHK(h, hipEventRecord(h->ev_halo, h->st_comm));
-            HIPCHK(h, hipStreamWaitEvent(h->st, h->ev_halo, 0));
-            KStrips Kb = K;
-            Kb.seg0 = 0; Kb.seg_stride = K.nseg - 1; Kb.nseg = 2;
-            nb = ((long long)Kb.nstrips * Kb.nseg + 3) / 4;
-            Kb.nblocks = (int)((nb + 7) / 8 * 8);
-            launch(Kb, 2.0 / K.nseg, np ? np + (long long)K.nstrips * (K.nseg - 2) : nullptr);
-        }
+        int rc = !halo_vec ? launch(K, 1.0, np) : with_halo_overlap(h, K, np, [&](hipStream_t st) {
+            Scope sc(h, KC_HALO, 4.0 * 2.0 * 8.0 * G.F * (double)G.inner * 2.0);
+            return h->tr->exchange(halo_vec, G.F, G.plane, G.inner, G.sloc, G.ng, st);
+        }, launch);
+        if (rc) return rc;
         HIPCHK(h, hipGetLastError());
         if (fused_norm) return reduce_rows(h, 1 + D.n, (int)nwaves, 0);
         if (want_norm) return fail(h, KSFD_EINVAL, "op_rhs: fused norm needs the strip kernels");
@@ -257,14 +276,13 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         KComb C = cmb ? *cmb : KComb{};
         const double *uin = u;
         const double *Gplane = h->Gb;
-        const int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
         // first stage of a step: the argument is the resident state itself and G(u) is plane 1 of the frozen coefficients the step has
         // just made of it (same parameters): nothing to form, no pass
         const bool reuse_G = C.nin == 0 && u == h->u && h->coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
         if (reuse_G) Gplane = h->coef + G.plane;
         else {
             Scope sc(h, KC_GFIELD, 8.0 * ((1 + C.nin) * G.F + (C.nin ? G.F : 0) + 1) * (double)G.plane, C.nin ? vbytes(h, 2 + C.nin) : 0.0);
-            NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_gfield_comb<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, PP, u, C, C.nin ? h->Z : (double *)nullptr, h->Gb));
+            NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_gfield_comb<NL>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, PP, u, C, C.nin ? h->Z : (double *)nullptr, h->Gb));
         }
         if (C.nin) uin = h->Z;
         K3D K = make_k3d(h);
@@ -272,14 +290,12 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         if (K.rows == 8) hipLaunchKernelGGL((k_rhs3d_strip<1, 8>), dim3(K.nblocks), dim3(8 * KSFD_WAVE), 0, h->st, G, PP, K, uin, Gplane, S, out, C);
         else NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs3d_strip<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, K, uin, Gplane, S, out, C));
     } else {
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
         {
             Scope sc(h, KC_GFIELD, 8.0 * (G.F + 1) * (double)G.plane);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_gfield<NL, false>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, PP, u, (const double *)nullptr, h->Gb, (double *)nullptr));
+            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_gfield<NL, false>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, PP, u, (const double *)nullptr, h->Gb, (double *)nullptr));
         }
-        int nb = (int)std::min<long long>((G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
         Scope sc(h, KC_RHS, vbytes(h, 2) + 8.0 * (double)G.nloc, vbytes(h, 2));
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_rhs_generic<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, G, PP, u, h->Gb, S, out));
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_rhs_generic<NL>), dim3(point_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, PP, u, h->Gb, S, out));
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
@@ -294,14 +310,12 @@ static int op_jvp(ksfd_handle *h, const double *u, const double *v, int mode, do
         Scope sc(h, KC_JVP, vbytes(h, 3));
         NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_fused<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, K, u, v, mode, shift, out));
     } else {
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
         {
             Scope sc(h, KC_GFIELD, 8.0 * (2 * G.F + 2) * (double)G.plane);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_gfield<NL, true>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, h->P, u, v, h->Gb, h->dGb));
+            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_gfield<NL, true>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, h->P, u, v, h->Gb, h->dGb));
         }
-        int nb = (int)std::min<long long>((G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
         Scope sc(h, KC_JVP, vbytes(h, 3) + 16.0 * (double)G.nloc, vbytes(h, 3));
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, G, h->P, u, v, h->Gb, h->dGb, mode, shift, out));
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(point_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, h->P, u, v, h->Gb, h->dGb, mode, shift, out));
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
@@ -312,7 +326,7 @@ static int op_jvp(ksfd_handle *h, const double *u, const double *v, int mode, do
 static int op_jcoef(ksfd_handle *h, const double *u, bool want_means = false)
 {
     const KGeom &G = h->G;
-    int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
+    const int nbp = plane_blocks(G);
     if (!h->coef32 && h->poly_fp32 && fused_ok(h) && h->P.nlig <= 4 && G.plane % 2 == 0 && G.inner % 2 == 0 &&
         hipMalloc((void **)&h->coef32, sizeof(float) * (size_t)(3 + h->P.nlig) * G.plane) != hipSuccess) { h->coef32 = nullptr; h->poly_fp32 = false; }
     float *c32 = h->poly_fp32 ? h->coef32 : nullptr;
@@ -343,7 +357,7 @@ static int ensure_coef(ksfd_handle *h, bool ghosts_done = false)
     if ((rc = op_jcoef(h, h->u, h->spec.ok))) return rc;
     h->coef_fresh = true;
     h->mg_coef_valid = false; h->mg_shift = -1.0;
-    h->spec.means_valid = h->spec.ok && (long long)(1 + h->P.nlig) * std::min<long long>((h->G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096) <= part_capacity();
+    h->spec.means_valid = h->spec.ok && (long long)(1 + h->P.nlig) * plane_blocks(h->G) <= part_capacity();
     return KSFD_OK;
 }
 
@@ -353,195 +367,133 @@ static int op_jvp_frozen(ksfd_handle *h, const double *v, int mode, double shift
                          const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0, bool want_norm = false)
 {
     const KGeom &G = h->G;
-    const double nplanes = (3 + h->P.nlig) + 2.0 * G.F + ((mode == 2 || mode == 3) ? G.F : 0);   // coefficients + v + out (+ yadd)
-    const double alg = 8.0 * (3.0 * G.F + ((mode == 2 || mode == 3) ? G.F : 0)) * (double)G.nloc;   // read u, v, write out (+ the fused vector operand)
+    const JvpBytes B = jvp_bytes(G, mode, 3 + h->P.nlig), Bdg = jvp_bytes(G, mode, 3);
     if (fused_ok(h)) {
         KStrips K = make_strips(h, true);
-        const long long nwaves = (long long)K.nstrips * K.nseg;
+        const long long nwaves = strip_waves(h, true);
         if (want_norm && nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_jvp_frozen: too many waves for the fused norm");
         {
-            Scope sc(h, KC_JVP, 8.0 * nplanes * (double)G.nloc, alg);
+            Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
             NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, K, (const double *)h->coef, v, mode, shift, out, yadd, alpha, beta, KSmooth{}, want_norm ? h->part : (double *)nullptr));
         }
         HIPCHK(h, hipGetLastError());
         return want_norm ? reduce_rows(h, 1, (int)nwaves, 0) : KSFD_OK;
     } else if (!want_norm && j3l_ok(h)) {
         K3D K = make_k3d_lds(h);
-        Scope sc(h, KC_JVP, 8.0 * nplanes * (double)G.nloc, alg);
+        Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
         j3l_launch<double>(h, K, v, mode, shift, out, yadd, alpha, beta, nullptr);
     } else if (h->use_fused && G.dim == 3 && (G.nx % 2 == 0) && G.nx >= 4 && h->P.nlig <= 4) {
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
-        {
-            Scope sc(h, KC_GFIELD, 8.0 * (2 + h->P.nlig + G.F) * (double)G.plane);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, (const double *)h->coef, v, h->dGb));
-        }
+        dg_pass(h, G, h->coef, v, h->dGb);
         K3D K = make_k3d(h);
-        Scope sc(h, KC_JVP, 8.0 * (2.0 * G.F + 3 + ((mode == 2 || mode == 3) ? G.F : 0)) * (double)G.nloc, alg);
+        Scope sc(h, KC_JVP, Bdg.impl * (double)G.nloc, Bdg.alg * (double)G.nloc);
         if (K.rows == 8) hipLaunchKernelGGL((k_jvp3d_frozen<1, double, 8>), dim3(K.nblocks), dim3(8 * KSFD_WAVE), 0, h->st, G, h->P, K, (const double *)h->coef, v, (const double *)h->dGb, mode, shift, out, yadd, alpha, beta);
         else NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp3d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, K, (const double *)h->coef, v, (const double *)h->dGb, mode, shift, out, yadd, alpha, beta));
     } else {
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
-        {
-            Scope sc(h, KC_GFIELD, 8.0 * (2 + h->P.nlig + G.F) * (double)G.plane);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, (const double *)h->coef, v, h->dGb));
-        }
-        int nb = (int)std::min<long long>((G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
-        Scope sc(h, KC_JVP, 8.0 * (2.0 * G.F + 3 + ((mode == 2 || mode == 3) ? G.F : 0)) * (double)G.nloc, alg);
+        dg_pass(h, G, h->coef, v, h->dGb);
+        Scope sc(h, KC_JVP, Bdg.impl * (double)G.nloc, Bdg.alg * (double)G.nloc);
         // the generic stencil kernel reads rho from plane 0 of its `u` argument (already clamped in C) and G from C
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, G, h->P, (const double *)h->coef, v, (const double *)(h->coef + G.plane), (const double *)h->dGb, mode, shift, out, yadd, alpha, beta));
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(point_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, h->P, (const double *)h->coef, v, (const double *)(h->coef + G.plane), (const double *)h->dGb, mode, shift, out, yadd, alpha, beta));
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
 }
 
-// Jacobian action with the halo exchange of v hidden behind the interior rows (slab ranks, 2-D fused kernel):
-//   compute stream: [interior segments]                      [two boundary segments]
-//   comm stream   :   wait(v ready) -> ghost rows of v <- ring neighbours -> signal
-// Interior segments read owned rows only; the first and last segment are the only readers of ghost rows.
-static int op_jvp_frozen_halo(ksfd_handle *h, double *v, int mode, double shift, double *out,
-                              const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0)
-{
-    int rc;
-    const KGeom &G = h->G;
-    if (!h->ring) return op_jvp_frozen(h, v, mode, shift, out, yadd, alpha, beta);
-    KStrips K = make_strips(h, true);
-    if (!h->overlap || !fused_ok(h) || K.nseg < 3 || h->P.nlig > 4) {
-        if ((rc = halo(h, v))) return rc;
-        return op_jvp_frozen(h, v, mode, shift, out, yadd, alpha, beta);
-    }
-    const double nplanes = (3 + h->P.nlig) + 2.0 * G.F + ((mode == 2 || mode == 3) ? G.F : 0);   // coefficients + v + out (+ yadd)
-    const double algp = 3.0 * G.F + ((mode == 2 || mode == 3) ? G.F : 0);
-    const int nseg_total = K.nseg;
-    HIPCHK(h, hipEventRecord(h->ev_ready, h->st));
-    {
-        KStrips Ki = K;
-        Ki.seg0 = 1; Ki.seg_stride = 1; Ki.nseg = nseg_total - 2;
-        long long nb = ((long long)Ki.nstrips * Ki.nseg + 3) / 4;
-        Ki.nblocks = (int)((nb + 7) / 8 * 8);
-        Scope sc(h, KC_JVP, 8.0 * nplanes * (double)G.nloc * (double)Ki.nseg / nseg_total, 8.0 * algp * (double)G.nloc * (double)Ki.nseg / nseg_total);
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL>), dim3(Ki.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, Ki, (const double *)h->coef, (const double *)v, mode, shift, out, yadd, alpha, beta));
-    }
-    HIPCHK(h, hipStreamWaitEvent(h->st_comm, h->ev_ready, 0));
-    {
-        Scope sc(h, KC_HALO, 4.0 * 2.0 * 8.0 * G.F * (double)G.inner * 2.0);
-        if (h->tr->exchange(v, G.F, G.plane, G.inner, G.sloc, G.ng, h->st_comm)) return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
-    }
-    HIPCHK(h, hipEventRecord(h->ev_halo, h->st_comm));
-    HIPCHK(h, hipStreamWaitEvent(h->st, h->ev_halo, 0));
-    {
-        KStrips Kb = K;
-        Kb.seg0 = 0; Kb.seg_stride = nseg_total - 1; Kb.nseg = 2;
-        long long nb = ((long long)Kb.nstrips * Kb.nseg + 3) / 4;
-        Kb.nblocks = (int)((nb + 7) / 8 * 8);
-        Scope sc(h, KC_JVP, 8.0 * nplanes * (double)G.nloc * 2.0 / nseg_total, 8.0 * algp * (double)G.nloc * 2.0 / nseg_total);
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL>), dim3(Kb.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, Kb, (const double *)h->coef, (const double *)v, mode, shift, out, yadd, alpha, beta));
-    }
-    HIPCHK(h, hipGetLastError());
-    return KSFD_OK;
-}
-
-// The same strip kernel with mixed storage types (fp32 coefficient copy / Horner temporaries of the polynomial
-// preconditioner).  Same overlap scheme as op_jvp_frozen_halo; a float vector travels through the double-typed transport
-// as half as many doubles (inner and plane are even on this path).
+// The 2-D strip kernel of the frozen Jacobian action on `frac` of the segments, for any storage types of its operands (fp32
+// coefficient copy / Horner temporaries of the polynomial preconditioner, fp32 residual of the spectral solver)
 template <typename TC, typename TV, typename TY, typename TO>
 static int jvp2d_launch_t(ksfd_handle *h, const KStrips &K, double frac, const TC *C, const TV *v, int mode, double shift,
                           TO *out, const TY *yadd, double alpha, double beta, double *normpart = nullptr)
 {
     const KGeom &G = h->G;
-    const double per_pt = (3.0 + h->P.nlig) * sizeof(TC) + G.F * (double)(sizeof(TV) + sizeof(TO)) + ((mode == 2 || mode == 3) ? G.F * (double)sizeof(TY) : 0.0);
-    Scope sc(h, KC_JVP, per_pt * (double)G.nloc * frac, 8.0 * (3.0 * G.F + ((mode == 2 || mode == 3) ? G.F : 0)) * (double)G.nloc * frac);
+    const JvpBytes B = jvp_bytes<TC, TV, TY, TO>(G, mode, 3 + h->P.nlig);
+    Scope sc(h, KC_JVP, B.impl * (double)G.nloc * frac, B.alg * (double)G.nloc * frac);
     NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, TC, TV, TY, TO>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st,
                                                                      G, h->P, K, C, (const TV *)v, mode, shift, out, yadd, alpha, beta, KSmooth{}, normpart));
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
 }
 
+// ... with the halo exchange of v hidden behind the interior rows on slab ranks (with_halo_overlap; the caller has NOT exchanged the
+// ghost rows of v).  A float vector travels through the double-typed transport as half as many doubles (inner and plane are even
+// on this path).  normpart != NULL: per-wave partials of ||out||^2
 template <typename TC, typename TV, typename TY, typename TO>
-static int jvp2d_halo_t(ksfd_handle *h, const TC *C, TV *v, int mode, double shift, TO *out, const TY *yadd, double alpha, double beta, double *normpart = nullptr);
+static int jvp2d_halo_t(ksfd_handle *h, const TC *C, TV *v, int mode, double shift, TO *out, const TY *yadd, double alpha, double beta, double *normpart = nullptr)
+{
+    const KGeom &G = h->G;
+    auto launch = [&](const KStrips &Kx, double frac, double *np) { return jvp2d_launch_t(h, Kx, frac, C, v, mode, shift, out, yadd, alpha, beta, np); };
+    if (!h->ring) return launch(make_strips(h, true), 1.0, normpart);
+    const long long scale = sizeof(double) / sizeof(TV);            // 1 for double, 2 for float
+    return with_halo_overlap(h, make_strips(h, true), normpart, [&](hipStream_t st) {
+        Scope sc(h, KC_HALO, 4.0 * 2.0 * sizeof(TV) * G.F * (double)G.inner * 2.0);
+        return h->tr->exchange(reinterpret_cast<double *>(v), G.F, G.plane / scale, G.inner / scale, G.sloc, G.ng, st);
+    }, launch);
+}
+
+// Jacobian action on a vector whose ghost rows have NOT been exchanged yet: behind the interior rows where the 2-D strip kernel
+// runs with at least 3 segments, else exchange first and op_jvp_frozen (which also serves the 3-D and generic kernels)
+static int op_jvp_frozen_halo(ksfd_handle *h, double *v, int mode, double shift, double *out,
+                              const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0)
+{
+    if (!h->ring) return op_jvp_frozen(h, v, mode, shift, out, yadd, alpha, beta);
+    if (!h->overlap || !fused_ok(h) || make_strips(h, true).nseg < 3 || h->P.nlig > 4) {
+        const int rc = halo(h, v);
+        return rc ? rc : op_jvp_frozen(h, v, mode, shift, out, yadd, alpha, beta);
+    }
+    return jvp2d_halo_t<double, double, double, double>(h, (const double *)h->coef, v, mode, shift, out, yadd, alpha, beta);
+}
 
 // r32 = b - A x stored in fp32 (its only reader is the spectral preconditioner, which works in fp32 anyway) with ||r||^2 in
-// fp64 from the store epilogue -> h->hres[0].  Single rank, strip kernels.
+// fp64 from the store epilogue -> h->hres[0].  Single rank or slab ranks (2-D), strip kernels.
 static int op_residual32(ksfd_handle *h, const double *x, double shift, const double *b, float *r32)
 {
-    if (h->G.dim == 3 && j3l_ok(h)) {
-        const KGeom &G = h->G;
-        K3D K = make_k3d_lds(h);
-        const long long nwaves = (long long)K.nblocks * K.rows;
+    const KGeom &G = h->G;
+    const long long nwaves = G.dim == 3 ? k3d_waves(h) : strip_waves(h, true);
+    if (G.dim == 3) {
+        // second generation, or: dG plane, then the z-marching Jacobian action in residual mode; fp32 output and the norm in the epilogue
+        const bool j3l = j3l_ok(h);
+        if (!j3l) dg_pass(h, G, h->coef, x, h->dGb);
         if (nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_residual32: too many waves for the fused norm");
+        // (the second generation charges one more fp64 vector than its operands: kept as it has always been reported)
+        const JvpBytes B = j3l ? jvp_bytes<double, double, double, float>(G, 2, 3 + h->P.nlig, 8.0 * G.F) : jvp_bytes<double, double, double, float>(G, 2, 3);
+        const K3D K = j3l ? make_k3d_lds(h) : make_k3d(h);
         {
-            Scope sc(h, KC_JVP, (8.0 * (3.0 * G.F + 3 + h->P.nlig) + 4.0 * G.F) * (double)G.nloc, 8.0 * 4.0 * G.F * (double)G.nloc);
-            j3l_launch<float>(h, K, x, 2, shift, r32, b, 0.0, 0.0, h->part);
-        }
-        HIPCHK(h, hipGetLastError());
-        return reduce_rows(h, 1, (int)nwaves, 0);
-    }
-    if (h->G.dim == 3) {
-        // 3-D strip kernel: dG plane, then the z-marching Jacobian action in residual mode with fp32 output and the norm in its epilogue
-        const KGeom &G = h->G;
-        int nbp = (int)std::min<long long>((G.plane + KSFD_BLOCK - 1) / KSFD_BLOCK, 4096);
-        {
-            Scope sc(h, KC_GFIELD, 8.0 * (2 + h->P.nlig + G.F) * (double)G.plane);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, (const double *)h->coef, x, h->dGb));
-        }
-        K3D K = make_k3d(h);
-        const long long nwaves = (long long)K.nblocks * K.rows;
-        if (nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_residual32: too many waves for the fused norm");
-        {
-            Scope sc(h, KC_JVP, (8.0 * (2.0 * G.F + 3) + 4.0 * G.F) * (double)G.nloc, 8.0 * 4.0 * G.F * (double)G.nloc);
-            if (K.rows == 8) hipLaunchKernelGGL((k_jvp3d_frozen<1, float, 8>), dim3(K.nblocks), dim3(8 * KSFD_WAVE), 0, h->st, G, h->P, K, (const double *)h->coef, x, (const double *)h->dGb, 2, shift, r32, b, 0.0, 0.0, h->part);
+            Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
+            if (j3l) j3l_launch<float>(h, K, x, 2, shift, r32, b, 0.0, 0.0, h->part);
+            else if (K.rows == 8) hipLaunchKernelGGL((k_jvp3d_frozen<1, float, 8>), dim3(K.nblocks), dim3(8 * KSFD_WAVE), 0, h->st, G, h->P, K, (const double *)h->coef, x, (const double *)h->dGb, 2, shift, r32, b, 0.0, 0.0, h->part);
             else NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp3d_frozen<NL, float>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, K, (const double *)h->coef, x, (const double *)h->dGb, 2, shift, r32, b, 0.0, 0.0, h->part));
         }
         HIPCHK(h, hipGetLastError());
         return reduce_rows(h, 1, (int)nwaves, 0);
     }
-    KStrips K = make_strips(h, true);
-    const long long nwaves = (long long)K.nstrips * K.nseg;
     if (nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_residual32: too many waves for the fused norm");
     // slab ranks: the ghost rows of x travel while the interior segments are computed (the caller has NOT exchanged them)
-    int rc = h->ring ? jvp2d_halo_t<double, double, double, float>(h, (const double *)h->coef, const_cast<double *>(x), 2, shift, r32, b, 0.0, 0.0, h->part)
-                         : jvp2d_launch_t<double, double, double, float>(h, K, 1.0, (const double *)h->coef, x, 2, shift, r32, b, 0.0, 0.0, h->part);
+    int rc = jvp2d_halo_t<double, double, double, float>(h, (const double *)h->coef, const_cast<double *>(x), 2, shift, r32, b, 0.0, 0.0, h->part);
     if (rc) return rc;
     return reduce_rows(h, 1, (int)nwaves, 0);
-}
-
-template <typename TC, typename TV, typename TY, typename TO>
-// normpart != NULL: per-wave partials of ||out||^2, numbered over ALL segments (interior launch first, then the two boundary segments)
-static int jvp2d_halo_t(ksfd_handle *h, const TC *C, TV *v, int mode, double shift, TO *out, const TY *yadd, double alpha, double beta, double *normpart)
-{
-    const KGeom &G = h->G;
-    KStrips K = make_strips(h, true);
-    if (!h->ring) return jvp2d_launch_t(h, K, 1.0, C, v, mode, shift, out, yadd, alpha, beta, normpart);
-    const long long scale = sizeof(double) / sizeof(TV);            // 1 for double, 2 for float
-    const bool ovl = h->overlap && K.nseg >= 3;
-    int rc;
-    if (ovl) {
-        HIPCHK(h, hipEventRecord(h->ev_ready, h->st));
-        KStrips Ki = K;
-        Ki.seg0 = 1; Ki.seg_stride = 1; Ki.nseg = K.nseg - 2;
-        long long nb = ((long long)Ki.nstrips * Ki.nseg + 3) / 4;
-        Ki.nblocks = (int)((nb + 7) / 8 * 8);
-        if ((rc = jvp2d_launch_t(h, Ki, (double)Ki.nseg / K.nseg, C, v, mode, shift, out, yadd, alpha, beta, normpart))) return rc;
-        HIPCHK(h, hipStreamWaitEvent(h->st_comm, h->ev_ready, 0));
-    }
-    {
-        Scope sc(h, KC_HALO, 4.0 * 2.0 * sizeof(TV) * G.F * (double)G.inner * 2.0);
-        if (h->tr->exchange(reinterpret_cast<double *>(v), G.F, G.plane / scale, G.inner / scale, G.sloc, G.ng, ovl ? h->st_comm : h->st))
-            return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
-    }
-    if (!ovl) return jvp2d_launch_t(h, K, 1.0, C, v, mode, shift, out, yadd, alpha, beta, normpart);
-    HIPCHK(h, hipEventRecord(h->ev_halo, h->st_comm));
-    HIPCHK(h, hipStreamWaitEvent(h->st, h->ev_halo, 0));
-    KStrips Kb = K;
-    Kb.seg0 = 0; Kb.seg_stride = K.nseg - 1; Kb.nseg = 2;
-    long long nb = ((long long)Kb.nstrips * Kb.nseg + 3) / 4;
-    Kb.nblocks = (int)((nb + 7) / 8 * 8);
-    return jvp2d_launch_t(h, Kb, 2.0 / K.nseg, C, v, mode, shift, out, yadd, alpha, beta, normpart ? normpart + (long long)K.nstrips * (K.nseg - 2) : nullptr);
 }
 
 // VW = 2 when every plane/offset/length is even (all accesses 16-byte aligned double2)
 static inline bool vec2(const ksfd_handle *h) { return (h->G.nloc % 2 == 0) && (h->kv.off % 2 == 0) && (h->G.plane % 2 == 0); }
 static inline dim3 vgridw(const ksfd_handle *h, int vw) { return dim3((h->nblk_vec + vw - 1) / vw, h->G.F); }
 #define VW_DISPATCH(h, CALL) do { if (vec2(h)) { constexpr int VW = 2; CALL; } else { constexpr int VW = 1; CALL; } } while (0)
+// basis-size ladder of the Krylov kernels: KB = 4 | 8 | 16 | 32 >= k
+#define KB_DISPATCH(k, CALL)                                                                       \
+    do {                                                                                           \
+        if ((k) <= 4) { constexpr int KB = 4; CALL; }                                              \
+        else if ((k) <= 8) { constexpr int KB = 8; CALL; }                                         \
+        else if ((k) <= 16) { constexpr int KB = 16; CALL; }                                       \
+        else { constexpr int KB = 32; CALL; }                                                      \
+    } while (0)
+// number of terms of k_lincomb: NT = 1..6
+#define NT_DISPATCH(nt, CALL)                                                                      \
+    switch (nt) {                                                                                  \
+    case 1: { constexpr int NT = 1; CALL; } break;                                                 \
+    case 2: { constexpr int NT = 2; CALL; } break;                                                 \
+    case 3: { constexpr int NT = 3; CALL; } break;                                                 \
+    case 4: { constexpr int NT = 4; CALL; } break;                                                 \
+    case 5: { constexpr int NT = 5; CALL; } break;                                                 \
+    default: { constexpr int NT = 6; CALL; } break;                                                \
+    }
 
 // want_norm: ||out||^2 lands in h->hres[0] (one reduction instead of a pass of its own)
 static int op_lincomb(ksfd_handle *h, int nt, const double *const *x, const double *a, double *out, bool want_norm = false)
@@ -550,14 +502,7 @@ static int op_lincomb(ksfd_handle *h, int nt, const double *const *x, const doub
     KLin L;
     for (int t = 0; t < 6; t++) { L.x[t] = t < nt ? x[t] : nullptr; L.a[t] = t < nt ? a[t] : 0.0; }
     Scope sc(h, KC_LINCOMB, vbytes(h, nt + 1));
-    switch (nt) {
-    case 1: VW_DISPATCH(h, hipLaunchKernelGGL((k_lincomb<1, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, L, out, part)); break;
-    case 2: VW_DISPATCH(h, hipLaunchKernelGGL((k_lincomb<2, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, L, out, part)); break;
-    case 3: VW_DISPATCH(h, hipLaunchKernelGGL((k_lincomb<3, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, L, out, part)); break;
-    case 4: VW_DISPATCH(h, hipLaunchKernelGGL((k_lincomb<4, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, L, out, part)); break;
-    case 5: VW_DISPATCH(h, hipLaunchKernelGGL((k_lincomb<5, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, L, out, part)); break;
-    default: VW_DISPATCH(h, hipLaunchKernelGGL((k_lincomb<6, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, L, out, part)); break;
-    }
+    NT_DISPATCH(nt, VW_DISPATCH(h, hipLaunchKernelGGL((k_lincomb<NT, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, L, out, part)));
     HIPCHK(h, hipGetLastError());
     if (want_norm) { const dim3 gr = vgridw(h, vec2(h) ? 2 : 1); return reduce_rows(h, 1, (int)(gr.x * gr.y), 0); }
     return KSFD_OK;
@@ -584,10 +529,7 @@ static int op_multidot(ksfd_handle *h, const double *w, const double *V, int k)
     const int nb = vec2(h) ? (h->nblk_vec + 1) / 2 : h->nblk_vec;
     {
         Scope sc(h, KC_MULTIDOT, vbytes(h, k + 1));
-        if (k <= 4) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot<4, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
-        else if (k <= 8) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot<8, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
-        else if (k <= 16) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot<16, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
-        else VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot<32, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
+        KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot<KB, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part)));
     }
     HIPCHK(h, hipGetLastError());
     return reduce_rows(h, k + 1, nb, 0);
@@ -599,10 +541,7 @@ static int op_multidot_gram(ksfd_handle *h, const double *w, const double *V, in
     const int nb = vec2(h) ? (h->nblk_vec + 1) / 2 : h->nblk_vec;
     {
         Scope sc(h, KC_MULTIDOT, vbytes(h, k + 1));
-        if (k <= 4) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<4, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
-        else if (k <= 8) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<8, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
-        else if (k <= 16) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<16, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
-        else VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<32, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part));
+        KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<KB, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, h->part)));
     }
     HIPCHK(h, hipGetLastError());
     return reduce_rows(h, 2 * k + 1, nb, 0);
@@ -621,10 +560,7 @@ static int op_gs_update(ksfd_handle *h, double *w, const double *V, int k, const
     KCoef C;
     for (int i = 0; i < KSFD_MAXDOT; i++) C.h[i] = i < k ? coef[i] : 0.0;
     Scope sc(h, KC_GSUPDATE, vbytes(h, k + 2));
-    if (k <= 4) VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update<4, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, C, scale));
-    else if (k <= 8) VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update<8, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, C, scale));
-    else if (k <= 16) VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update<16, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, C, scale));
-    else VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update<32, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, C, scale));
+    KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update<KB, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, C, scale)));
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
 }
@@ -644,10 +580,7 @@ static int op_basis_axpy(ksfd_handle *h, double *x, const double *V, int k, cons
     int nread = 0;                                      // vectors with a zero coefficient are not loaded
     for (int i = 0; i < KSFD_MAXDOT; i++) { C.h[i] = i < k ? coef[i] : 0.0; nread += C.h[i] != 0.0; }
     Scope sc(h, KC_BASISAXPY, vbytes(h, nread + 1 + (beta != 0.0)));
-    if (k <= 4) VW_DISPATCH(h, hipLaunchKernelGGL((k_basis_axpy<4, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, x, V, h->vlen, k, C, beta, part));
-    else if (k <= 8) VW_DISPATCH(h, hipLaunchKernelGGL((k_basis_axpy<8, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, x, V, h->vlen, k, C, beta, part));
-    else if (k <= 16) VW_DISPATCH(h, hipLaunchKernelGGL((k_basis_axpy<16, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, x, V, h->vlen, k, C, beta, part));
-    else VW_DISPATCH(h, hipLaunchKernelGGL((k_basis_axpy<32, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, x, V, h->vlen, k, C, beta, part));
+    KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_basis_axpy<KB, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, x, V, h->vlen, k, C, beta, part)));
     HIPCHK(h, hipGetLastError());
     if (want_norm) { const dim3 gr = vgridw(h, vec2(h) ? 2 : 1); return reduce_rows(h, 1, (int)(gr.x * gr.y), 0); }
     return KSFD_OK;

@@ -128,7 +128,8 @@ def _run(size, shape, nlig, transport, tmp_path):
 @pytest.mark.parametrize('size,shape,nlig', [(2, (64, 48), 1), (3, (40, 36), 2), (2, (16, 12, 16), 1), (2, (33, 16), 1),
                                              (2, (140, 160), 1), (3, (64, 240), 2),    # >= 3 row segments per rank -> halo/compute overlap path
                                              (2, (16, 16, 32), 1),                     # 3-D with a 2-level multigrid hierarchy on the slabs
-                                             (2, (96,), 2)])                           # 1-D slabs with the 1-D multigrid hierarchy
+                                             (2, (96,), 2),                            # 1-D slabs with the 1-D multigrid hierarchy
+                                             (2, (64, 8), 1)])                         # 4 rows = 2 row segments per rank: strip kernels, too few segments to overlap
 def test_slab_ranks_match_single_rank_host_transport(size, shape, nlig, tmp_path):
     _run(size, shape, nlig, 'host', tmp_path)
 
