@@ -278,6 +278,43 @@ int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enab
  * non-finite pivot.  The state and what the stepper remembers are not changed. */
 int ksfd_direct_apply(ksfd_handle *h, double shift, const double *v, double *out, int32_t layout);
 
+
+/* -- GMRES with deflated restarting (GMRES-DR; Morgan, SIAM J. Sci. Comput. 24, 2002) as the Krylov solver of the stage systems.
+ * Off by default.  keep = 0 switches it off, 1..16 = harmonic Ritz vectors of smallest modulus kept in the basis across a restart (one
+ * more when the last one is half of a complex pair); above 16: KSFD_EINVAL.  ksfd_step returns KSFD_EINVAL, state untouched, while
+ * keep > ksp_restart - 3.  carry_stages != 0: the relation kept at the end of a stage solve also serves the later stage systems of the
+ * same step attempt (same matrix); it never crosses an attempt, a step or ksfd_checkpoint.
+ * With deflation on, the solves pc_type selects as plain, multigrid-preconditioned or polynomial-preconditioned GMRES run deflated: the
+ * restart length is ksp_restart and stays fixed (no restart growth), Krylov recycling across stages and the pipelined solver (tuning bits
+ * 3-8, 20) are bypassed, the V cycle preconditions flexibly like the polynomial (z_j kept: the cycle is not a linear operator), and a
+ * solve returns KSFD_OK only on the TRUE residual b - A x, never on the recurrence alone: it must meet the tolerance, or -- unpreconditioned
+ * solves only -- exceed it by no more than an estimate of the rounding error of evaluating it, nnz_row * u * ||A|| ||x||, and by no more than
+ * a quarter of the tolerance; such solves are counted in rounding_passes and report their residual in ksp_resid.  The spectral defect correction with its fallbacks and the direct solver (pc_type 5) are untouched. */
+int ksfd_set_deflation(ksfd_handle *h, int32_t keep, int32_t carry_stages);
+typedef struct ksfd_deflation_stats {   /* of the last ksfd_step call, all its attempts together */
+    int32_t restarts;           /* deflated restarts */
+    int32_t kept;               /* vectors kept at the last of them */
+    int32_t stage_its[4];       /* iterations per stage system */
+    int32_t true_resid_fail;    /* solves whose recurrence residual met the tolerance while the true residual did not: continued */
+    int32_t projections;        /* residuals projected on a kept relation (carry_stages, and continuations after a failed check) */
+    int32_t rounding_passes;    /* solves accepted with a true residual above the tolerance (by < 25 %) within the rounding error of b - A x */
+    int32_t reserved;
+} ksfd_deflation_stats;
+int ksfd_get_deflation_stats(ksfd_handle *h, ksfd_deflation_stats *stats);
+/* Vectors the Krylov basis of this handle holds (restart length that fits + 1): 9 ... 121 by the memory free at ksfd_create.  The upper
+ * limit of nin below; a caller of the test entry cannot know it otherwise. */
+int32_t ksfd_basis_capacity(const ksfd_handle *h);
+/* Parity/test entry of the basis rotation kernel: uploads nin host vectors (each ksfd_local_size doubles) into the Krylov basis and runs
+ * V[:, 0:nout] <- V[:, 0:nin] * P in place (P nin x nout, row-major; nout <= 18, nin <= min(121, ksfd_basis_capacity)).  vout_host
+ * receives ALL nin slots, not only the first nout: the first nout rotated, slots nout .. nin-1 as the kernel left them, which is
+ * untouched -- so that a test can assert exactly that. */
+int ksfd_basis_rotate(ksfd_handle *h, int32_t nin, int32_t nout, const double *P_host, const double *vin_host, double *vout_host,
+                      int32_t layout);
+/* ksfd_bench_kernel classes beyond the profile's kernel classes: the rotation kernel on 31 -> 11 vectors in one pass, and the same
+ * rotation composed from 11 basis combinations of 31 vectors (out of place) */
+#define KSFD_BENCH_ROTATE 100
+#define KSFD_BENCH_ROTATE_COMPOSED 101
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,15 @@ struct ksfd_handle {
     bool rhs_dots = true;            // inner products for the stage guesses from the RHS kernel's store epilogue (KSFD_TUNE bit 21 clears)
     bool rec_mg = false;             // multigrid-preconditioned solves: the WHOLE first cycle of every stage is kept for the later stages of the step (KSFD_TUNE bit 20 sets; measured: no gain, see gmres)
 
+    // Deflated restart of GMRES (krylov_dr.hip.h; ksfd_set_deflation).  keep = 0: off, every other solver path is as without it.
+    int dr_keep = 0;                 // harmonic Ritz vectors kept across a restart (1..16)
+    bool dr_carry = false;           // the kept relation also serves the later stage systems of a step attempt
+    double *dr_P = nullptr, *dr_Phost = nullptr;      // rotation matrix of op_basis_rotate: device copy and pinned staging (KSFD_ROT_MAXIN x KSFD_ROT_MAXOUT)
+    // A M^-1 V_kk = V_kk+1 H (H (kk+1) x kk column-major) in the leading slots of V (and Zb): valid for this matrix, shift and preconditioner only
+    struct DrKept { bool valid = false; int kk = 0, pc = -1; double shift = 0.0, shift_pc = 0.0; std::vector<double> H; };
+    DrKept dr;
+    ksfd_deflation_stats dr_stats = {};
+
     LUState lu;
 
     // multigrid preconditioner

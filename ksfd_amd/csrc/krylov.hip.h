@@ -159,6 +159,7 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
     // tol_abs > 0: stop at that absolute residual norm (the caller solves a correction equation A d = b - A x0 and wants the
     // tolerance of the original system)
     const bool use_pc = pcmode == 1;       // multigrid, right preconditioning
+    h->dr.valid = false;                   // this solve builds in V: a relation kept by the deflated solver (krylov_dr.hip.h) is gone
     // the hierarchy may be built for a LARGER shift than the system's (h->mg_shift_floor): when 1/(gamma h) falls below the growth
     // rate of the chemotactic instability, shift*I - J is indefinite and a V cycle of it is no contraction; the V cycle of the
     // positively shifted operator still is, and GMRES (true residual of the real system) takes care of the difference

@@ -25,6 +25,7 @@
 #include "spectral_host.hip.h"
 #include "mg_host.hip.h"
 #include "krylov.hip.h"
+#include "krylov_dr.hip.h"
 #include "lu_host.hip.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -45,6 +46,8 @@ extern "C" void ksfd_destroy(ksfd_handle *h)
     if (h->pub_count) hipFree(h->pub_count);
     if (h->gm_host) hipHostFree(h->gm_host);
     if (h->gm_dev) hipFree(h->gm_dev);
+    if (h->dr_P) hipFree(h->dr_P);
+    if (h->dr_Phost) hipHostFree(h->dr_Phost);
     for (auto e : h->gm_ev) if (e) hipEventDestroy(e);
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->pool) hipEventDestroy(e);
@@ -331,6 +334,7 @@ extern "C" int ksfd_checkpoint(ksfd_handle *h, int32_t op)
 {
     if (!h || op < 0 || op > 1) return KSFD_EINVAL;
     hipSetDevice(h->device);
+    h->dr.valid = false;                                 // a kept Krylov relation never crosses a save or a restore: replays stay bitwise
     if (op == 0) {
         if (!h->ckpt && alloc_d(h, &h->ckpt, h->vlen)) return KSFD_ENOMEM;
         HIPCHK(h, hipMemcpyAsync(h->ckpt, h->u, sizeof(double) * (size_t)h->vlen, hipMemcpyDeviceToDevice, h->st));
@@ -625,6 +629,13 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
         const int g = direct_guard(h);
         if (g) return g;
     }
+    // deflated restarting (krylov_dr.hip.h): the restart length is the caller's, fixed, and must leave room behind the kept vectors
+    const bool dr_on = h->dr_keep > 0 && !direct;
+    if (dr_on) {
+        const int m_dr = std::min(opts->ksp_restart > 0 ? opts->ksp_restart : 30, h->restart_alloc);
+        if (h->dr_keep > m_dr - 3) return fail(h, KSFD_EINVAL, "deflation: keep = %d needs a restart length of at least %d (ksp_restart %d, basis vectors allocated %d)", h->dr_keep, h->dr_keep + 3, (int)opts->ksp_restart, h->restart_alloc);
+    }
+    memset(&h->dr_stats, 0, sizeof h->dr_stats);
     if (getenv("KSFD_PC_SIGMA")) { h->mg_shift_floor = atof(getenv("KSFD_PC_SIGMA")); h->sf_auto = false; }      // experiment knob: fixed floor
     ksfd_step_stats st;
     memset(&st, 0, sizeof st);
@@ -656,6 +667,7 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
     h->spec.rho_step = 0.0;
     while (true) {
         const double shift = 1.0 / (GAMMA_RA * hh);
+        h->dr.valid = false;                             // every attempt has its own matrix: nothing is carried into it
         // stiffness estimate X = h*gamma*lambda_max of the diffusion part; the multigrid preconditioner pays off above ~60
         double dmax = h->P.s2, lap = 0.0;
         for (int l = 0; l < h->P.nlig; l++) dmax = std::max(dmax, h->P.lig_D[l]);
@@ -692,7 +704,7 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
             use_poly = h->poly_deg >= 1 && h->poly_max_deg >= 1;
         }
         const bool small = (double)h->G.F * (double)h->G.nloc <= 6.0e6;
-        const bool use_async = !direct && !use_spec && !use_pc && !use_poly && h->use_frozen && !(opts->reserved & 1) && stiff >= 1e-3 &&
+        const bool use_async = !dr_on && !direct && !use_spec && !use_pc && !use_poly && h->use_frozen && !(opts->reserved & 1) && stiff >= 1e-3 &&
                                (!h->ring || h->tr->device_allreduce()) &&
                                (h->async_mode == 1 || (h->async_mode == 2 && small));
         h->mg_use32 = opts->ksp_rtol >= 1e-7;          // fp32 level vectors inside the V cycle (mg_vcycle32); tight tolerances keep fp64
@@ -821,11 +833,13 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
                 for (int j = 0; j < sg.n; j++) { xs[j] = sg.Y[j]; a[j] = sg.c[j]; }
                 if ((rc = op_lincomb(h, sg.n, xs, a, xi)) || (rc = halo(h, xi)) || (rc = op_jvp_frozen(h, xi, 2, shift, h->Z, bcur))) break;
                 const double tol = std::max(opts->ksp_rtol * sqrt(bnorm2), opts->ksp_atol);
-                rc = gmres(h, h->u, shift, h->Z, h->t3, opts, &ls, 1, i, tol);        // stage index: the Krylov spaces of the earlier stages are projected out first
+                rc = dr_on ? gmres_dr(h, h->u, shift, h->Z, h->t3, opts, &ls, 1, i, tol)
+                           : gmres(h, h->u, shift, h->Z, h->t3, opts, &ls, 1, i, tol);        // stage index: the Krylov spaces of the earlier stages are projected out first
                 if (!rc) { const double *x2[2] = { xi, h->t3 }; double a2[2] = { 1.0, 1.0 }; rc = op_lincomb(h, 2, x2, a2, xi); }
                 st.pc_used |= 2;
             } else {
             rc = use_async ? gmres_async(h, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls)
+                 : dr_on ? gmres_dr(h, h->u, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, use_pc ? 1 : (use_poly ? 2 : 0), i)
                            : gmres(h, h->u, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, use_pc ? 1 : (use_poly ? 2 : 0), i);
             st.pc_used |= use_pc ? 2 : (use_poly ? 4 : 1);
             }
@@ -1028,6 +1042,44 @@ extern "C" int ksfd_direct_apply(ksfd_handle *h, double shift, const double *vh,
     if ((rc = upload(h, vh, layout, h->t2)) || (rc = direct_solve(h, h->t2, h->t3))) return rc;
     return download(h, h->t3, layout, outh);
 }
+extern "C" int ksfd_set_deflation(ksfd_handle *h, int32_t keep, int32_t carry_stages)
+{
+    if (!h) return KSFD_EINVAL;
+    if (keep < 0 || keep > 16) return fail(h, KSFD_EINVAL, "deflation: keep = %d outside 0 (off) .. 16", (int)keep);
+    h->dr_keep = keep;
+    h->dr_carry = carry_stages != 0;
+    h->dr.valid = false;
+    return KSFD_OK;
+}
+extern "C" int ksfd_get_deflation_stats(ksfd_handle *h, ksfd_deflation_stats *s)
+{
+    if (!h || !s) return KSFD_EINVAL;
+    *s = h->dr_stats;
+    return KSFD_OK;
+}
+extern "C" int32_t ksfd_basis_capacity(const ksfd_handle *h) { return h ? h->restart_alloc + 1 : 0; }
+extern "C" int ksfd_basis_rotate(ksfd_handle *h, int32_t nin, int32_t nout, const double *P, const double *vin, double *vout, int32_t layout)
+{
+    if (!h || !P || !vin || !vout) return KSFD_EINVAL;
+    if (layout < 0 || layout > 2) return fail(h, KSFD_EINVAL, "bad layout %d", layout);
+    if (nin < 1 || nout < 1 || nout > nin || nout > KSFD_ROT_MAXOUT || nin > KSFD_ROT_MAXIN || nin > h->restart_alloc + 1)
+        return fail(h, KSFD_EINVAL, "basis_rotate: %d -> %d vectors outside 1 <= nout <= %d, nout <= nin <= min(%d, %d)", (int)nin, (int)nout, KSFD_ROT_MAXOUT, KSFD_ROT_MAXIN, h->restart_alloc + 1);
+    hipSetDevice(h->device);
+    h->dr.valid = false;
+    rec_reset(h);
+    int rc;
+    const int64_t nl = (int64_t)h->G.F * h->G.nloc;
+    for (int i = 0; i < nin; i++) {
+        if ((rc = upload(h, vin + (int64_t)i * nl, layout, h->V + (int64_t)i * h->vlen))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->st));            // the staging buffer of upload() is reused by the next vector
+    }
+    std::vector<double> Pp((size_t)nin * KSFD_ROT_MAXOUT, 0.0);
+    for (int i = 0; i < nin; i++) for (int j = 0; j < nout; j++) Pp[(size_t)i * KSFD_ROT_MAXOUT + j] = P[(size_t)i * nout + j];
+    if ((rc = op_basis_rotate(h, h->V, nin, nout, Pp.data(), KSFD_ROT_MAXOUT))) return rc;
+    for (int i = 0; i < nin; i++)                          // all nin slots come back: the first nout rotated, the rest as uploaded
+        if ((rc = download(h, h->V + (int64_t)i * h->vlen, layout, vout + (int64_t)i * nl))) return rc;
+    return KSFD_OK;
+}
 extern "C" int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enable)
 {
     if (!h) return KSFD_EINVAL;
@@ -1097,11 +1149,22 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         case KC_GSUPDATE: r = op_gs_update(h, h->t3, h->V, 8, coef, 1.0); break;
         case KC_SPECTRAL: r = spec_apply(h, 10.0, h->Y, h->t3); break;
         case KC_LINCOMB: { const double *xs[3] = { h->u, h->Y, h->Y + h->vlen }; double aa[3] = { 1.0, 0.5, 0.25 }; r = op_lincomb(h, 3, xs, aa, h->t3); } break;
+        case KSFD_BENCH_ROTATE: {                                      // basis rotation 31 -> 11 vectors in one pass (k_basis_rotate)
+            std::vector<double> Pb((size_t)31 * KSFD_ROT_MAXOUT, 0.0);
+            for (int j = 0; j < 11; j++) Pb[(size_t)j * KSFD_ROT_MAXOUT + j] = 1.0;
+            r = op_basis_rotate(h, h->V, 31, 11, Pb.data(), KSFD_ROT_MAXOUT);
+        } break;
+        case KSFD_BENCH_ROTATE_COMPOSED: {                                      // the same rotation as 11 combinations of 31 vectors each (out of place, into Zb)
+            for (int i = 0; i < 31; i++) coef[i] = 1.0 / 31.0;
+            for (int j = 0; j < 11 && !r; j++) r = op_basis_axpy(h, h->Zb + (int64_t)j * h->vlen, h->V, 31, coef, 0.0);
+        } break;
         default: r = fail(h, KSFD_EINVAL, "bench_kernel: class %d not benchable", cls);
         }
         by = h->bytes_acc - b0;
         return r;
     };
+    if ((cls == KSFD_BENCH_ROTATE || cls == KSFD_BENCH_ROTATE_COMPOSED) && (h->restart_alloc < 30 || !h->Zb)) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the rotation benchmark needs 31 basis vectors and the flexible basis"); goto done; }
+    if (cls == KSFD_BENCH_ROTATE || cls == KSFD_BENCH_ROTATE_COMPOSED) { h->dr.valid = false; rec_reset(h); }
     if ((rc = halo(h, h->u))) goto done;
     if (h->use_frozen && (cls == KC_JVP || cls == KC_SPECTRAL) && (rc = ensure_coef(h, true))) goto done;
     if (cls == KC_SPECTRAL && (rc = spec_means(h))) goto done;

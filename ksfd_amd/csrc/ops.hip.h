@@ -586,6 +586,31 @@ static int op_basis_axpy(ksfd_handle *h, double *x, const double *V, int k, cons
     return KSFD_OK;
 }
 
+// V[:, 0:nout] <- V[:, 0:nin] * P in place (k_basis_rotate): P row-major on the host, nin x nout with row stride ldp.  Same index range
+// as op_basis_axpy (owned points; ghost rows untouched), booked with the Gram-Schmidt updates.  The coefficients travel through a pinned
+// staging buffer of the handle: every caller has waited on the stream (a reduction result, a download) since the previous rotation.
+static int op_basis_rotate(ksfd_handle *h, double *V, int nin, int nout, const double *P, int ldp)
+{
+    if (nin < 1 || nout < 1 || nout > nin || nin > KSFD_ROT_MAXIN || nout > KSFD_ROT_MAXOUT || ldp < nout || ldp > KSFD_ROT_MAXOUT)
+        return fail(h, KSFD_EINVAL, "basis rotation %d -> %d vectors (row stride %d) outside 1 <= nout <= %d, nout <= nin <= %d", nin, nout, ldp, KSFD_ROT_MAXOUT, KSFD_ROT_MAXIN);
+    const size_t nP = (size_t)KSFD_ROT_MAXIN * KSFD_ROT_MAXOUT;
+    if (!h->dr_P && hipMalloc((void **)&h->dr_P, sizeof(double) * nP) != hipSuccess) { h->dr_P = nullptr; return fail(h, KSFD_ENOMEM, "hipMalloc of the rotation matrix failed"); }
+    if (!h->dr_Phost && hipHostMalloc((void **)&h->dr_Phost, sizeof(double) * nP, hipHostMallocDefault) != hipSuccess) { h->dr_Phost = nullptr; return fail(h, KSFD_ENOMEM, "hipHostMalloc of the rotation matrix failed"); }
+    if (P) {                                            // NULL: the matrix of the previous call is still on the device (Zb follows V)
+        memcpy(h->dr_Phost, P, sizeof(double) * (size_t)nin * ldp);
+        HIPCHK(h, hipMemcpyAsync(h->dr_P, h->dr_Phost, sizeof(double) * (size_t)nin * ldp, hipMemcpyHostToDevice, h->st));
+    }
+    Scope sc(h, KC_GSUPDATE, vbytes(h, nin + nout));
+#define ROT_LAUNCH(NO) VW_DISPATCH(h, hipLaunchKernelGGL((k_basis_rotate<NO, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, V, (long long)h->vlen, nin, nout, (const double *)h->dr_P, ldp))
+    if (nout <= 4) ROT_LAUNCH(4);
+    else if (nout <= 8) ROT_LAUNCH(8);
+    else if (nout <= 12) ROT_LAUNCH(12);
+    else ROT_LAUNCH(KSFD_ROT_MAXOUT);
+#undef ROT_LAUNCH
+    HIPCHK(h, hipGetLastError());
+    return KSFD_OK;
+}
+
 static int op_copy(ksfd_handle *h, double *dst, const double *src)
 {
     Scope sc(h, KC_MISC, vbytes(h, 2));

@@ -408,6 +408,55 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_basis_axpy(KVec g, double *__res
     if (part) ksfd_block_sum_to(nrm, part + (long long)blockIdx.y * gridDim.x + blockIdx.x);     // ||x||^2 share, see k_lincomb
 }
 
+// In-place rotation of a basis (deflated restart of GMRES, krylov_dr.hip.h):  V[:, 0:nout] <- V[:, 0:nin] * P, P nin x nout.
+// One pass: a thread owns VW points of one field per trip, streams over the nin vectors once with NOUT accumulators per point in
+// registers, and stores its nout results only after its last load -- no other thread touches its points, which is what makes in-place
+// safe (V carries no __restrict__).  P (row-major, row stride ldp in global memory) is staged in LDS with the compile-time row stride
+// NOUT, so a row is read with wave-uniform addresses (broadcast, no bank conflicts) and adjacent coefficients pair into 16-byte reads.
+// Vectors nout .. nin-1 are left as they were.
+#define KSFD_ROT_MAXIN 121
+#define KSFD_ROT_MAXOUT 18
+template <int NOUT, int VW>
+__global__ void __launch_bounds__(KSFD_BLOCK) k_basis_rotate(KVec g, double *V, long long vstride, int nin, int nout,
+                                                             const double *__restrict__ P, int ldp)
+{
+    __shared__ double sP[KSFD_ROT_MAXIN * NOUT];
+    for (int q = threadIdx.x; q < nin * NOUT; q += blockDim.x) {
+        const int i = q / NOUT, j = q - i * NOUT;
+        sP[q] = j < nout ? P[i * ldp + j] : 0.0;
+    }
+    __syncthreads();
+    const long long base = (long long)blockIdx.y * g.plane + g.off;
+    const long long stride = (long long)gridDim.x * blockDim.x * VW;
+    for (long long p = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * VW; p < g.nloc; p += stride) {
+        double acc[NOUT][VW];
+#pragma unroll
+        for (int j = 0; j < NOUT; j++)
+#pragma unroll
+            for (int e = 0; e < VW; e++) acc[j][e] = 0.0;
+        const double *src = V + base + p;
+#pragma unroll 4
+        for (int i = 0; i < nin; i++) {
+            const typename KPack<VW>::T vv = kload<VW>(src + (long long)i * vstride);
+            const double *row = sP + i * NOUT;
+#pragma unroll
+            for (int j = 0; j < NOUT; j++) {
+                const double c = row[j];
+#pragma unroll
+                for (int e = 0; e < VW; e++) acc[j][e] = fma(c, kget(vv, e), acc[j][e]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NOUT; j++)
+            if (j < nout) {
+                typename KPack<VW>::T s;
+#pragma unroll
+                for (int e = 0; e < VW; e++) kset(s, e, acc[j][e]);
+                kstore<VW>(V + (long long)j * vstride + base + p, s);
+            }
+    }
+}
+
 // Step completion (PETSc TSEvaluateStep_RosW + TSErrorWeightedNorm, restated):
 //   unew = u + sum_j bt[j] Y_j ;  err = sum_j (b2t[j]-bt[j]) Y_j ;
 //   partial sum of (err / (atol + rtol*max(|unew|, |unew+err|)))^2.

@@ -64,6 +64,15 @@ class Profile(C.Structure):
                 ('alg_bytes', C.c_double * NKCLASS)]
 
 
+class DeflationStats(C.Structure):
+    _fields_ = [('restarts', C.c_int32), ('kept', C.c_int32), ('stage_its', C.c_int32 * 4),
+                ('true_resid_fail', C.c_int32), ('projections', C.c_int32), ('rounding_passes', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+ROT_MAXIN, ROT_MAXOUT = 121, 18     # KSFD_ROT_MAXIN / KSFD_ROT_MAXOUT: limits of the basis rotation kernel
+BENCH_ROTATE, BENCH_ROTATE_COMPOSED = 100, 101      # ksfd_bench_kernel: one-pass rotation 31 -> 11 vectors / 11 basis combinations
+
 _lib = None
 
 # every symbol include/ksfd_hip.h declares (checked by tests/test_abi.py without a GPU)
@@ -75,6 +84,7 @@ ABI_SYMBOLS = [
     'ksfd_default_step_opts', 'ksfd_step', 'ksfd_get_last_error_vector', 'ksfd_set_profiling',
     'ksfd_get_profile', 'ksfd_synchronize', 'ksfd_bench_kernel', 'ksfd_set_tuning', 'ksfd_set_mg_params', 'ksfd_set_poly_params',
     'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply',
+    'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity',
 ]
 
 
@@ -138,6 +148,11 @@ def load():
     L.ksfd_spectral_apply.argtypes = [vp, C.c_double, dp, dp, C.c_int32]
     L.ksfd_set_spectral_params.argtypes = [vp, C.c_double, C.c_int32]
     L.ksfd_direct_apply.argtypes = [vp, C.c_double, dp, dp, C.c_int32]
+    L.ksfd_set_deflation.argtypes = [vp, C.c_int32, C.c_int32]
+    L.ksfd_get_deflation_stats.argtypes = [vp, C.POINTER(DeflationStats)]
+    L.ksfd_basis_capacity.argtypes = [vp]
+    L.ksfd_basis_capacity.restype = C.c_int32
+    L.ksfd_basis_rotate.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32]
     _lib = L
     return L
 
@@ -374,6 +389,34 @@ class KSFDHip:
         out = np.empty(self.nlocal)
         v = self._vec(v)
         self._chk(self.L.ksfd_direct_apply(self.h, float(shift), _dp(v), _dp(out), layout))
+        return out
+
+    def set_deflation(self, keep, carry_stages=False):
+        """GMRES with deflated restarting for the stage solves: keep harmonic Ritz vectors (0 = off, at most 16) survive a restart;
+        carry_stages: the kept space also serves the later stages of a step attempt"""
+        self._chk(self.L.ksfd_set_deflation(self.h, int(keep), int(bool(carry_stages))))
+
+    def deflation_stats(self):
+        """of the last step() call: dict(restarts, kept, stage_its[4], true_resid_fail, projections, rounding_passes)"""
+        s = DeflationStats()
+        self._chk(self.L.ksfd_get_deflation_stats(self.h, C.byref(s)))
+        return dict(restarts=s.restarts, kept=s.kept, stage_its=list(s.stage_its), true_resid_fail=s.true_resid_fail,
+                    projections=s.projections, rounding_passes=s.rounding_passes)
+
+    def basis_capacity(self):
+        """vectors the Krylov basis V holds (restart length that fits + 1)"""
+        return int(self.L.ksfd_basis_capacity(self.h))
+
+    def basis_rotate(self, P, vin, layout=SOA):
+        """V[:, :nout] <- V[:, :nin] P on the device (test entry): P (nin, nout), vin (nin, nlocal); returns (nin, nlocal) -- rows
+        nout.. come back as they went in"""
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        nin, nout = P.shape
+        vin = np.ascontiguousarray(vin, dtype=np.float64)
+        if vin.shape != (nin, self.nlocal):
+            raise ValueError('expected vin of shape (%d, %d), got %r' % (nin, self.nlocal, vin.shape))
+        out = np.empty((nin, self.nlocal))
+        self._chk(self.L.ksfd_basis_rotate(self.h, nin, nout, _dp(P), _dp(vin), _dp(out), layout))
         return out
 
     def set_spectral_params(self, from_stiffness=0.0, enable=-1):

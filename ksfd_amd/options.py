@@ -347,6 +347,40 @@ def step_opts_from(params, petsc_args):
     return o
 
 
+# -ksfd_ksp_type: Krylov solver of the stage systems.  dgmres = GMRES with deflated restarting (ksfd_set_deflation), PETSc's spelling
+KSFD_KSP_TYPES = ('gmres', 'dgmres')
+DGMRES_EIGEN_DEFAULT = 8        # harmonic Ritz vectors kept when -ksfd_dgmres_eigen is not given
+DGMRES_EIGEN_MAX = 16
+DGMRES_CARRY_DEFAULT = 0        # 1: the kept space also serves the later stages of a step attempt (measured: no fewer iterations)
+
+
+def deflation_from(petsc_args):
+    """(keep, carry_stages) for KSFDHip.set_deflation from -ksfd_ksp_type gmres|dgmres, -ksfd_dgmres_eigen <k> and
+    -ksfd_dgmres_carry 0|1, or None when the list asks for plain GMRES (what a list without these flags does)."""
+    a = list(petsc_args)
+    ksp, eigen, carry = 'gmres', None, None
+    for i, k in enumerate(a):
+        nxt = a[i + 1] if i + 1 < len(a) else None
+        if k == '-ksfd_ksp_type':
+            if nxt not in KSFD_KSP_TYPES:
+                raise ValueError('-ksfd_ksp_type must be one of %s, got %s' % ('/'.join(KSFD_KSP_TYPES), nxt))
+            ksp = nxt
+        elif k == '-ksfd_dgmres_eigen':
+            try:
+                eigen = int(nxt)
+            except (TypeError, ValueError):
+                eigen = -1
+            if not 1 <= eigen <= DGMRES_EIGEN_MAX:
+                raise ValueError('-ksfd_dgmres_eigen must be an integer 1..%d, got %s' % (DGMRES_EIGEN_MAX, nxt))
+        elif k == '-ksfd_dgmres_carry':
+            if nxt not in ('0', '1'):
+                raise ValueError('-ksfd_dgmres_carry must be 0 or 1, got %s' % nxt)
+            carry = int(nxt)
+    if ksp != 'dgmres':
+        return None
+    return (DGMRES_EIGEN_DEFAULT if eigen is None else eigen, DGMRES_CARRY_DEFAULT if carry is None else carry)
+
+
 def _isnum(s):
     try:
         float(s.split(',')[0])

@@ -188,7 +188,7 @@ class KSFDTS:
     default_hmin = 1e-20
 
     def __init__(self, derivs, t0=0.0, dt=0.001, tmax=20, maxsteps=100, rtol=1e-5, atol=1e-5, restart=True,
-                 hmin=None, comm=None, opts=None, rng=None):
+                 hmin=None, comm=None, opts=None, rng=None, deflation=None):
         self.derivs = derivs
         self.ks = derivs.ks
         self.comm = comm if comm is not None else derivs.grid.comm
@@ -198,6 +198,8 @@ class KSFDTS:
         self.hmin = float(hmin) if hmin else self.default_hmin
         self.opts = opts if opts is not None else klib.default_step_opts()
         self.opts.rtol, self.opts.atol = self.rtol, self.atol
+        if deflation is not None:                   # (keep, carry_stages) of -ksfd_ksp_type dgmres: ksfd_amd.options.deflation_from
+            self.ks.set_deflation(*deflation)
         self.history = []
         self.u = derivs.u0
         self._t, self._h, self._k = self.t0, float(dt), 0

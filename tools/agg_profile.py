@@ -1,12 +1,15 @@
 """Late (aggregated) phase on one GPU, by kernel class: the state bench.py's aggregated leg builds (tile^2 run with options81 spacing until
 the V cycle has owned 60 steps, tiled to n^2), then `steps` adaptive steps with events on every launch.
-usage: python tools/agg_profile.py [n=2048] [nlig=1] [steps=5] [tile=256]"""
+usage: python tools/agg_profile.py [n=2048] [nlig=1] [steps=5] [tile=256] [--ksp-type gmres|dgmres] [--eigen K] [--carry 0|1]"""
 import sys, os, time, json
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from ksfd_amd import lib as klib
 from ksfd_amd.config import ProblemConfig
 from ksfd_amd.initial import start_values
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from dgmres_flags import KSP_TYPE, EIGEN, CARRY
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
 nlig = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -40,6 +43,8 @@ print('tile state: t=%.4g h=%.4g rho %.0f..%.0f' % (t, h, u[0].min(), u[0].max()
 big = ProblemConfig.standard(2, (n, n), L=(n / 384.0,) * 2, nlig=nlig)
 kb = klib.KSFDHip(big)
 kb.set_state(np.tile(u, (1, reps, reps)).reshape(-1))
+if KSP_TYPE == 'dgmres':
+    kb.set_deflation(EIGEN, CARRY)
 if os.environ.get('MG_NU'):
     kb.set_mg_params(nu=int(os.environ['MG_NU']))
 if os.environ.get('MG_RATIO'):
@@ -60,6 +65,8 @@ kb.synchronize()
 el = time.perf_counter() - t0
 print('%d^2 x %d fields: %.2f ms/step, %.1f its/step (%.3f ms per iteration), %.0f launches and %.1f host syncs per step, pc_used %d, h %.3g'
       % (n, big.F, 1e3 * el / steps, its / steps, 1e3 * el / max(its, 1), launches / steps, syncs / steps, st.pc_used, st.h_used), flush=True)
+if KSP_TYPE == 'dgmres':
+    print('dgmres eigen %d carry %d: last step %s' % (EIGEN, CARRY, kb.deflation_stats()), flush=True)
 if os.environ.get('AGG_CLASSES', '1') != '0':
     kb.set_profiling(True)
     for _ in range(steps):
