@@ -266,8 +266,13 @@ int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_max, int32_t 
 int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, double mg_threshold);
 /* Spectral preconditioner: z = (shift*I - J0)^-1 v with J0 the constant-coefficient part of the Jacobian at the resident state
  * (grid means of rho*G_rho, rho*G_Ul; the 4th-order star's exact symbol), three hand-written FFT kernels (csrc/spectral.hip.h).
- * _apply is the parity/test entry (host vectors; KSFD_EINVAL where the handle has no spectral solver: 1-D, extents outside
- * {2^k, 3*2^k} or 32..16384, rank counts other than 1, 2, 4, 8, a transport without an all-to-all).  _params: stiffness
+ * Handles that have it: 2-D with nx and ny each 2^k (32..16384) or 3*2^k (48..12288), on one rank or on 1 (ring of one), 2, 4 or 8
+ * slab ranks over a transport with an all-to-all, ny/P >= 4 local rows (3*2^j rows travel as three chunks of 2^j); 3-D with
+ * power-of-two extents on one rank or on 1, 2, 4, 8 z-slab ranks with 2^j local planes.
+ * Handles that do not: 1-D, other extents (3*2^k in 3-D included), other rank counts, a transport without an all-to-all, and 2-D
+ * grids with a 3*2^k extent whose 2*npair columns of a block do not fit the LDS together (the two-phase column kernel that takes
+ * over there is power-of-two only).  Timing between different devices is unmeasured for all of them.
+ * _apply is the parity/test entry (host vectors; KSFD_EINVAL where the handle has no spectral solver).  _params: stiffness
  * h*gamma*lambda_max(diffusion) from which pc_type 2 prefers it (default 0.1 where the fused 2-D residual kernel runs, 0.3
  * elsewhere; <= 0 keeps) and enable (0 = never pick it automatically, 1 = default, < 0 keeps). */
 int ksfd_spectral_apply(ksfd_handle *h, double shift, const double *v_host, double *out_host, int32_t layout);

@@ -44,8 +44,9 @@ struct SpecState {
     int *posz = nullptr, *kzofpos = nullptr;
     float *lz = nullptr;
     int rb = 0, npair = 0, nyp = 0;
+    int nch = 1;                             // slab ranks with 3 * 2^j rows: 3 chunks of 2^j rows (spectral_plan.h); else 1
     size_t lds_rows = 0, lds_cols = 0;
-    kcf *W = nullptr, *W2 = nullptr, *twx = nullptr, *twy = nullptr, *twz = nullptr;     // W: [pair][pos_x][y_local]; W2: after the all-to-all, [rank][pair][own pos][y_local]
+    kcf *W = nullptr, *W2 = nullptr, *twx = nullptr, *twy = nullptr, *twz = nullptr;     // W: [pair][pos_x][y_local]; W2: after the all-to-all, [rank][pair][own pos][y_local] (nch = 3: [chunk] in front of [pair] in both)
     int *posy = nullptr, *kyofpos = nullptr;
     int2 *ytab = nullptr;                    // per y position: (position of -ky, bits of ly[ky]) -- symbol stage of k_spec_cols
     int lgw = -1;                            // layout of the forward work array (kspec_wt_index)

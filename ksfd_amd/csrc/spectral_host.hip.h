@@ -32,7 +32,7 @@ static void spec_build3d(ksfd_handle *h)
     if (ring && (!h->tr || !h->tr->has_alltoall() || (P != 1 && P != 2 && P != 4 && P != 8) || getenv("KSFD_SPEC_SINGLE"))) return;
     const long long nzg = h->cfg.n[2], nzl = G.sloc;               // global / local z planes
     if (!spec_plan(G.nx, S.px) || !spec_plan(G.ny, S.py) || !spec_plan(nzg, S.pz)) return;
-    if (S.px.m != 1 || S.py.m != 1 || S.pz.m != 1) return;           // (3 * 2^k extents: 2-D, one rank so far)
+    if (S.px.m != 1 || S.py.m != 1 || S.pz.m != 1) return;           // (3 * 2^k extents: 2-D only)
     if (S.px.radix[0] != 16 || G.nx > 32768 || G.ny > 32768 || (nzl & (nzl - 1)) || nzl < 2) return;
     S.dim = 3;
     S.npair = (G.F + 1) / 2;
@@ -141,8 +141,12 @@ static void spec_build(ksfd_handle *h)
     const long long ny = h->cfg.n[1], nyl = G.sloc;                  // global / local rows
     if (!spec_plan(G.nx, S.px) || !spec_plan(ny, S.py)) return;
     const bool pow2 = S.px.m == 1 && S.py.m == 1;
-    if (ring && (!pow2 || S.px.radix[0] != 16 || (nyl & (nyl - 1)))) return;      // slab ownership goes by the top radix-16 digit
+    SpecOwn O;
+    int nch = 1;                                                     // chunks of a rank's rows (3 on slab ranks with 3 * 2^j rows)
+    if (ring && !spec_slab_eligible(S.px, S.py, P, nyl, O, nch)) return;
     if (nyl < 4) return;
+    const long long cs = nyl / nch;                                  // rows per chunk: a power of two on slab ranks
+    S.nch = nch;
     S.npair = (G.F + 1) / 2;
     const size_t lds_max = 160 * 1024;
     const size_t row_bytes = sizeof(kcf) * spec_sstride(S.px);
@@ -183,20 +187,18 @@ static void spec_build(ksfd_handle *h)
         for (int k = 0; k < n; k++) { const double th = 2.0 * M_PI * k / n; l[k] = (float)((-30.0 + 32.0 * cos(th) - 2.0 * cos(2.0 * th)) / 12.0 * inv_h2); }
         return l;
     };
-    // ownership of spectral positions: top digit -> (rank, index of the digit in that rank's list)
-    const int nx = (int)G.nx, nx16 = nx / 16, ndig = 16 / P;
-    int dig_rank[16], dig_idx[16];
-    for (int q = 0; q < P; q++) for (int di = 0; di < ndig; di++) { const int d = spec_digit_order[q * ndig + di]; dig_rank[d] = q; dig_idx[d] = di; }
+    // ownership of spectral positions on slab ranks: spectral_plan.h (one rank: the work array is used in place, positions are their own index)
+    const int nx = (int)G.nx;
     S.nxl = nx / P;
     S.lg_pl = 0;
-    while ((1LL << S.lg_pl) < nyl) S.lg_pl++;
+    while ((1LL << S.lg_pl) < cs) S.lg_pl++;
     const std::vector<int> posx = positions(S.px);
-    // among the owner's positions (one rank: the work array is used in place, positions are their own index)
-    auto local_index = [&](int j) { return !ring ? j : dig_idx[j / nx16] * nx16 + (j % nx16); };
+    auto mine = [&](int j) { return !ring || spec_owner(O, j) == h->rank; };
+    auto local_index = [&](int j) { return !ring ? j : spec_local_index(O, j); };
     std::vector<int4> pairs;
     for (int kx = 0; kx <= nx / 2; kx++) {
         const int kxm = (nx - kx) % nx, j = posx[kx], jm = posx[kxm];
-        if (dig_rank[j / nx16] != h->rank) continue;
+        if (!mine(j)) continue;
         if (kx == 0) pairs.push_back(make_int4(local_index(posx[0]), local_index(posx[nx / 2]), 0, nx / 2 + 1));     // the two self-paired columns share a block
         else if (kx != nx / 2) pairs.push_back(make_int4(local_index(j), local_index(jm), kx, 0));
     }
@@ -204,10 +206,11 @@ static void spec_build(ksfd_handle *h)
     // array, and of the transposed one through the inverse row kernel's tiles)
     std::sort(pairs.begin(), pairs.end(), [](const int4 &a, const int4 &b) { return a.x < b.x; });
     S.nblk_cols = (int)pairs.size();
-    if (S.nblk_cols != S.nxl / 2) return;                            // (cannot happen for P in {1, 2, 4, 8}: the digit pairs keep kx and -kx together)
-    // column stride of W: the rows of this rank, rounded up to the power of two the column kernel addresses pieces with (equal for 2^k rows)
-    const long long cstride = ring ? nyl : (1LL << S.lg_pl);
-    const size_t wbytes = sizeof(kcf) * (size_t)S.npair * G.nx * cstride;
+    if (S.nblk_cols != S.nxl / 2) return;                            // (cannot happen: the ownership order keeps kx and -kx together)
+    // column stride of W: the rows of this rank, rounded up to the power of two the column kernel addresses pieces with (equal for 2^k
+    // rows); slab ranks: the rows of one chunk, W = [chunk][pair][pos][row in chunk]
+    const long long cstride = ring ? cs : (1LL << S.lg_pl);
+    const size_t wbytes = sizeof(kcf) * (size_t)S.npair * G.nx * cstride * nch;
     S.nyp = (int)cstride;
     S.tile_major = !ring && rb >= 2 && !getenv("KSFD_SPEC_TRANSPOSED");
     if (hipMalloc((void **)&S.W, wbytes) != hipSuccess || ((ring || S.tile_major || S.cols_split) && hipMalloc((void **)&S.W2, wbytes) != hipSuccess) ||
@@ -226,16 +229,15 @@ static void spec_build(ksfd_handle *h)
         if (S.lgw >= 0 && (S.nxl & ((1 << S.lgw) - 1))) S.lgw = -1;
     }
     if (ring) {
-        // pieces of the two all-to-alls: one per (peer, pair, top digit of the receiver) = nx/16 columns x nyl rows, contiguous on both sides
-        const size_t pbytes = sizeof(kcf) * (size_t)nx16 * nyl;
+        // blocks of the two all-to-alls: one per (peer, pair, piece of the receiver, chunk) = w columns x cs rows, contiguous on both sides
+        // (spectral_plan.h; 2^k grids: nx/16 columns x all rows of the rank)
+        const size_t pbytes = sizeof(kcf) * (size_t)O.w * cs;
         for (int q = 0; q < P; q++)
             for (int p = 0; p < S.npair; p++)
-                for (int di = 0; di < ndig; di++) {
-                    const int dq = spec_digit_order[q * ndig + di], dme = spec_digit_order[h->rank * ndig + di];
-                    kcf *mine_for_q = S.W + ((size_t)p * nx + (size_t)dq * nx16) * nyl;                               // my rows of q's columns
-                    kcf *from_q = S.W2 + (((size_t)q * S.npair + p) * S.nxl + (size_t)di * nx16) * nyl;               // q's rows of my columns
-                    kcf *back_mine = S.W + ((size_t)p * nx + (size_t)dq * nx16) * nyl;
-                    (void)dme;
+                for (int di = 0; di < O.per; di++) for (int c = 0; c < nch; c++) {
+                    kcf *mine_for_q = S.W + spec_a2a_src(O, nx, S.npair, cs, q, p, di, c);                            // my rows of q's columns
+                    kcf *from_q = S.W2 + spec_a2a_dst(O, S.npair, nch, cs, q, p, di, c);                              // q's rows of my columns
+                    kcf *back_mine = mine_for_q;
                     S.a2a_fwd_s.push_back({ q, mine_for_q, pbytes });
                     S.a2a_fwd_r.push_back({ q, from_q, pbytes });
                     if (S.cols_split) {
@@ -290,7 +292,11 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
     Y.den_floor = (float)(0.02 * shift);
     for (int l = 0; l < h->P.nlig; l++) { Y.a_rU[l] = (float)S.a_rU[l]; Y.s[l] = (float)h->P.lig_s[l]; Y.gam[l] = (float)h->P.lig_gamma[l]; Y.D[l] = (float)h->P.lig_D[l]; }
     const bool d3 = S.dim == 3;
-    const int ntiles = (int)((d3 ? G.ny * G.sloc : G.sloc) / S.rb);     // 3-D: the x rows are the nz*ny rows of the box
+    // slab ranks with 3 * 2^j rows: the row kernels run once per chunk of 2^j rows, on that chunk's part of the vectors and of the
+    // chunk-major work array (spec_build); everywhere else nch = 1 and the loops below are one launch
+    const int nch = d3 ? 1 : S.nch;
+    const int ntiles = (int)((d3 ? G.ny * G.sloc : G.sloc) / S.rb) / nch;     // 3-D: the x rows are the nz*ny rows of the box
+    const long long rows_off = G.sloc / nch * G.nx, w_off = (long long)S.npair * G.nx * S.nyp;      // a chunk's rows in a plane / in W
     const long long goff = (long long)G.ng * G.inner;                // the row kernels address owned rows only
     KSpecLin ex, add;
     memset(&ex, 0, sizeof ex); memset(&add, 0, sizeof add);
@@ -320,8 +326,14 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
     const double fn = (double)G.F * (double)G.nloc, pn = 8.0 * S.npair * (double)G.nloc;
     {
         Scope sc(h, KC_SPECTRAL, (v32 ? 4.0 : 8.0) * fn + 8.0 * ex.n * fn + pn, 8.0 * (1 + ex.n) * fn);        // read v (+ guess vectors) | write W
-        if (v32) hipLaunchKernelGGL(k_spec_rows_fwd<float>, dim3(ntiles, S.npair), dim3(thr_rows), S.lds_rows, h->st, px_f, S.nyp, S.rb, S.tile_major ? -ntiles : ntiles, G.F, v32 + goff, G.plane, S.tile_major ? S.W2 : S.W, (const kcf *)S.twx, ex);
-        else hipLaunchKernelGGL(k_spec_rows_fwd<double>, dim3(ntiles, S.npair), dim3(thr_rows), S.lds_rows, h->st, px_f, S.nyp, S.rb, S.tile_major ? -ntiles : ntiles, G.F, v + goff, G.plane, S.tile_major ? S.W2 : S.W, (const kcf *)S.twx, ex);
+        for (int c = 0; c < nch; c++) {
+            const long long ro = c * rows_off;
+            kcf *Wf = (S.tile_major ? S.W2 : S.W) + c * w_off;
+            KSpecLin exc = ex;
+            for (int j = 0; j < exc.n; j++) exc.p[j] += ro;
+            if (v32) hipLaunchKernelGGL(k_spec_rows_fwd<float>, dim3(ntiles, S.npair), dim3(thr_rows), S.lds_rows, h->st, px_f, S.nyp, S.rb, S.tile_major ? -ntiles : ntiles, G.F, v32 + goff + ro, G.plane, Wf, (const kcf *)S.twx, exc);
+            else hipLaunchKernelGGL(k_spec_rows_fwd<double>, dim3(ntiles, S.npair), dim3(thr_rows), S.lds_rows, h->st, px_f, S.nyp, S.rb, S.tile_major ? -ntiles : ntiles, G.F, v + goff + ro, G.plane, Wf, (const kcf *)S.twx, exc);
+        }
     }
     if (d3) {
         const int cz = 1 << S.lg_cz;
@@ -396,7 +408,12 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
     }
     {
         Scope sc(h, KC_SPECTRAL, pn + 8.0 * (1 + add.n) * fn, 8.0 * (1 + add.n) * fn);     // read W (+ x / guess vectors) | write z
-        hipLaunchKernelGGL(k_spec_rows_inv, dim3(ntiles, S.npair), dim3(thr_rows), S.lds_rows, h->st, px_i, S.nyp, S.rb, ntiles, G.F, (const kcf *)((d3 || S.cols_split) ? S.W2 : S.W), z + goff, G.plane, (const kcf *)S.twx, add);
+        for (int c = 0; c < nch; c++) {
+            const long long ro = c * rows_off;
+            KSpecLin addc = add;
+            for (int j = 0; j < addc.n; j++) addc.p[j] += ro;
+            hipLaunchKernelGGL(k_spec_rows_inv, dim3(ntiles, S.npair), dim3(thr_rows), S.lds_rows, h->st, px_i, S.nyp, S.rb, ntiles, G.F, (const kcf *)((d3 || S.cols_split) ? S.W2 : S.W) + c * w_off, z + goff + ro, G.plane, (const kcf *)S.twx, addc);
+        }
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;

@@ -50,6 +50,55 @@ static int spec_pos(const KFFTPlan &P, int k)
 // the digits handed out in these pairs both columns of every {kx, -kx} pair land on one rank.
 static const int spec_digit_order[16] = { 0, 8, 1, 15, 2, 14, 3, 13, 4, 12, 5, 11, 6, 10, 7, 9 };
 
+// The same for every plan (2-D).  The unit of ownership is a PIECE of w contiguous positions: the 16 top digits of a power-of-two
+// plan (w = n/16), or, behind a radix-3 stage, the 48 pieces (q0, d) = (k % 3, (k / 3) % 16) of w = n/48 positions, piece id
+// q0 * 16 + d = pos / w.  Since 3 | n, -k lies in (0, (16 - d) % 16) for q0 = 0 and in (2, 15 - d) for q0 = 1 (and back), so the
+// ownership ORDER below keeps partners next to each other at an even index: first the q0 = 0 pieces in spec_digit_order (kx = 0 and
+// kx = n/2, pieces (0,0) and (0,8), lead: they share a block of the column kernel and go to rank 0), then (1,0), (2,15), (1,1),
+// (2,14), ...  Rank q owns the `per` = npiece/P pieces [q * per, (q + 1) * per) of the order -- an even count for P = 1, 2, 4, 8 --
+// and stores them in that order: local index of a position = (index of its piece among the rank's) * w + pos % w.
+struct SpecOwn {
+    int P, npiece, w, per;         // ranks, pieces, positions per piece, pieces per rank
+    int piece[48], order[48];      // piece[o] = id of the o-th piece of the order; order[id] = o
+};
+static bool spec_ownership(const KFFTPlan &Q, int P, SpecOwn &O)
+{
+    if ((P != 1 && P != 2 && P != 4 && P != 8) || Q.nstage < 1 || Q.radix[0] != 16) return false;
+    O.P = P; O.npiece = 16 * Q.m; O.w = Q.n / O.npiece; O.per = O.npiece / P;
+    for (int o = 0; o < 16; o++) O.piece[o] = spec_digit_order[o];
+    if (Q.m == 3) for (int d = 0; d < 16; d++) { O.piece[16 + 2 * d] = 16 + d; O.piece[17 + 2 * d] = 32 + 15 - d; }
+    for (int o = 0; o < O.npiece; o++) O.order[O.piece[o]] = o;
+    return true;
+}
+static int spec_owner(const SpecOwn &O, int pos) { return O.order[pos / O.w] / O.per; }
+static int spec_local_index(const SpecOwn &O, int pos) { return (O.order[pos / O.w] % O.per) * O.w + pos % O.w; }
+static int spec_piece_start(const SpecOwn &O, int rank, int i) { return O.piece[rank * O.per + i] * O.w; }      // first position of rank's i-th piece
+
+// Which slab handles have the 2-D solver -- the one place that decides it (the transport must also offer an all-to-all: spec_build).
+// nx, ny each 2^k or 3 * 2^k (the plans); P = 1, 2, 4, 8; nyl = ny/P local rows, at least 4.  ny = 3 * 2^k gives a rank 3 * 2^j rows:
+// they are handled as nch = 3 CHUNKS of cs = 2^j rows, so that the column kernel still sees a column as pieces of a power of two
+// (3 P pieces of 2^j); cs >= 2 because it moves two elements at a time.
+static bool spec_slab_eligible(const KFFTPlan &px, const KFFTPlan &py, int P, long long nyl, SpecOwn &O, int &nch)
+{
+    if (!spec_ownership(px, P, O)) return false;
+    nch = py.m;
+    if (nyl < 4 || nyl % nch) return false;
+    const long long cs = nyl / nch;
+    return cs >= 2 && !(cs & (cs - 1));
+}
+// The two all-to-alls move blocks (peer, field pair p, piece i of the receiver, chunk c) of w positions x cs rows, contiguous on both
+// sides.  Sender: W[chunk][pair][pos][row in chunk] (the row kernels' transposed store, chunk-major); receiver:
+// W2[sender * nch + chunk][pair][own position][row in chunk], i.e. piece number (global row / cs) of every column, as k_spec_cols
+// addresses it.  Element offsets of a block:
+static size_t spec_a2a_src(const SpecOwn &O, int nx, int npair, long long cs, int peer, int p, int i, int c)
+{
+    return (((size_t)c * npair + p) * nx + spec_piece_start(O, peer, i)) * cs;
+}
+static size_t spec_a2a_dst(const SpecOwn &O, int npair, int nch, long long cs, int sender, int p, int i, int c)
+{
+    return ((((size_t)sender * nch + c) * npair + p) * ((size_t)O.per * O.w) + (size_t)i * O.w) * cs;
+}
+
 // exp(-2 pi i j / 2^lg), j < 2^lg, for the power-of-two stages; behind it, for 3 * 2^lg, exp(-2 pi i j / n), j < 2^lg (radix-3 stage)
 static std::vector<kcf> spec_twiddles(const KFFTPlan &P)
 {
