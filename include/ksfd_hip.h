@@ -98,8 +98,8 @@ typedef struct ksfd_step_opts {
     double ksp_rtol, ksp_atol;  /* GMRES: stop at ||r|| <= max(ksp_rtol*||b||, ksp_atol) */
     int32_t ksp_restart, ksp_max_it;
     int32_t pc_type;            /* 0 none; 1 geometric multigrid V cycle always; 2 automatic (default): the spectral defect correction
-                                 * (constant-coefficient part of shift*I - J inverted by FFT; 2-D and 3-D, extents 2^k or 3*2^k, on 1, 2,
-                                 * 4 or 8 slab ranks) while it converges in a few sweeps, else multigrid when the step is stiff,
+                                 * (constant-coefficient part of shift*I - J inverted by FFT; 2-D and 3-D, extents 2^k or 3*2^k on one
+                                 * rank; on 1, 2, 4 or 8 slab ranks see ksfd_spectral_apply) while it converges in a few sweeps, else multigrid when the step is stiff,
                                  * Chebyshev polynomial + flexible GMRES when mildly stiff, none when not; 3 polynomial only;
                                  * 4 spectral always; 5 direct: dense LU of shift*I - J on the device, factored once per step attempt, every
                                  * stage solve checked by its true residual against max(ksp_rtol*||b||, ksp_atol) with at most two refinement
@@ -266,12 +266,14 @@ int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_max, int32_t 
 int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, double mg_threshold);
 /* Spectral preconditioner: z = (shift*I - J0)^-1 v with J0 the constant-coefficient part of the Jacobian at the resident state
  * (grid means of rho*G_rho, rho*G_Ul; the 4th-order star's exact symbol), three hand-written FFT kernels (csrc/spectral.hip.h).
- * Handles that have it: 2-D with nx and ny each 2^k (32..16384) or 3*2^k (48..12288), on one rank or on 1 (ring of one), 2, 4 or 8
- * slab ranks over a transport with an all-to-all, ny/P >= 4 local rows (3*2^j rows travel as three chunks of 2^j); 3-D with
- * power-of-two extents on one rank or on 1, 2, 4, 8 z-slab ranks with 2^j local planes.
- * Handles that do not: 1-D, other extents (3*2^k in 3-D included), other rank counts, a transport without an all-to-all, and 2-D
- * grids with a 3*2^k extent whose 2*npair columns of a block do not fit the LDS together (the two-phase column kernel that takes
- * over there is power-of-two only).  Timing between different devices is unmeasured for all of them.
+ * Handles that have it: on one rank without a halo transport, every 2-D and 3-D grid whose extents are each 2^k (32..16384) or
+ * 3*2^k (48..12288), through every column path (the two-phase column kernel for columns that do not fit the LDS included); 2-D
+ * on 1 (ring of one), 2, 4 or 8 slab ranks over a transport with an all-to-all, ny/P >= 4 local rows (3*2^j rows travel as three
+ * chunks of 2^j); 3-D with power-of-two extents on 1, 2, 4, 8 z-slab ranks with 2^j local planes.
+ * Handles that do not: 1-D, other extents, other rank counts, a transport without an all-to-all, and -- on slab ranks and the ring
+ * of one only -- 3-D boxes with a 3*2^k extent, and 2-D grids with a 3*2^k column extent whose 2*npair columns of a block do not
+ * fit the LDS together (more than 8192 rows, or 6144 rows with three or more fields: the two-phase column kernel is power-of-two
+ * only there).  Timing between different devices is unmeasured for all of them.
  * _apply is the parity/test entry (host vectors; KSFD_EINVAL where the handle has no spectral solver).  _params: stiffness
  * h*gamma*lambda_max(diffusion) from which pc_type 2 prefers it (default 0.1 where the fused 2-D residual kernel runs, 0.3
  * elsewhere; <= 0 keeps) and enable (0 = never pick it automatically, 1 = default, < 0 keeps). */

@@ -81,6 +81,16 @@ struct KSpecSym {
 };
 
 __device__ __forceinline__ int kspec_pad(int i) { return i + (i >> 4); }      // one element of padding per 16: conflict-free butterflies
+// R3: the axis is 3 * 2^lg (KFFTPlan.m == 3) -- a compile-time property of the 3-D y/z kernels and of the split column kernel, so that
+// the power-of-two instances keep their shifts and masks.  kspec_div, kspec_mod: idx / n and idx % n for n = 2^lg or 3 * 2^lg; kspec_lp: padded LDS position of element e
+template <bool R3> __device__ __forceinline__ int kspec_div(int lg, int idx) { return R3 ? (idx >> lg) / 3 : idx >> lg; }
+template <bool R3> __device__ __forceinline__ int kspec_mod(int n, int idx, int q) { return R3 ? idx - q * n : idx & (n - 1); }      // idx % n, q = idx / n
+template <bool R3> __device__ __forceinline__ int kspec_lp(const KFFTPlan &P, int e)
+{
+    if (!R3) return kspec_pad(e);
+    const int b = e >> P.lg, i = e & ((1 << P.lg) - 1);
+    return b * kspec_ss(P) + i + (i >> 4);
+}
 __device__ __forceinline__ kcf kc_mul(kcf a, kcf b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ kcf kc_add(kcf a, kcf b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ kcf kc_sub(kcf a, kcf b) { return make_float2(a.x - b.x, a.y - b.y); }
@@ -713,7 +723,8 @@ __global__ void __launch_bounds__(1024) k_spec_cols(KFFTPlan PY, int nxl, int lg
 //            from W (contiguous along y in both walking directions); inverse transform; result to Wout -- a different array, since
 //            the blocks of the other field pairs still read W
 // 2 + (npair + 2) passes over a pair's columns instead of 2: the price of keeping the solver at all for such sizes.
-template <int NL>
+// R3 = true: columns of 3 * 2^k points (one rank: a column is one piece, its stride in W rounded up to the power of two of lg_pl).
+template <int NL, bool R3>
 __device__ __forceinline__ void kspec_cols_symbol_split(const KFFTPlan &PY, kcf *lds, int sstride, bool self, int kxA, int kxB, int p0, const kcf *__restrict__ W,
                                                         int nxl, int lg_pl, long long pstride, int jA, int jB, const int *__restrict__ posy,
                                                         const int *__restrict__ kyofpos, const float *__restrict__ lx, const float *__restrict__ ly, const KSpecSym &S)
@@ -725,13 +736,13 @@ __device__ __forceinline__ void kspec_cols_symbol_split(const KFFTPlan &PY, kcf 
         return W + (long long)(y >> lg_pl) * pstride + (((long long)p * nxl + (c ? jB : jA)) << lg_pl) + (y & plmask);
     };
     for (int item = threadIdx.x; item < nitem; item += blockDim.x) {
-        const int mpos = item & (ny - 1);
+        const int cs = R3 ? (int)(item >= ny) : item >> PY.lg, mpos = R3 ? item - cs * ny : item & (ny - 1);      // item < 2 ny
         const int ky = kyofpos[mpos];
         int ca = 0, cb = 1;
-        if (self) { ca = cb = item >> PY.lg; if (ky > half) continue; }
-        const int kym = (ny - ky) & (ny - 1);
+        if (self) { ca = cb = cs; if (ky > half) continue; }
+        const int kym = R3 ? (ky ? ny - ky : 0) : (ny - ky) & (ny - 1);
         const int mposp = posy[kym];
-        const int m = kspec_pad(mpos), mp = kspec_pad(mposp);
+        const int m = kspec_lp<R3>(PY, mpos), mp = kspec_lp<R3>(PY, mposp);
         const float L2 = lx[ca ? kxB : kxA] + ly[ky];
         kcf a[npair], b[npair];
 #pragma unroll
@@ -782,6 +793,7 @@ __device__ __forceinline__ void kspec_cols_symbol_split1(const KFFTPlan &PY, kcf
     }
 }
 
+template <bool R3>      // R3: ny = 3 * 2^lg (one rank)
 __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY, int nxl, int lg_pl, long long pstride, kcf *__restrict__ W, const kcf *__restrict__ Wt, int lg_rb,
                                                          kcf *__restrict__ Wout, const kcf *__restrict__ tw, const int4 *__restrict__ pairtab, const int *__restrict__ posy,
                                                          const int *__restrict__ kyofpos, const float *__restrict__ lx, const float *__restrict__ ly, KSpecSym S)
@@ -801,7 +813,7 @@ __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY
     };
     // fused edge stages as in k_spec_cols: phase 1 does the first forward stage on the values as they are gathered, phase 2 the last
     // inverse stage straight into the store (PY.flags bits 0 / 1)
-    const bool edge = PY.m == 1 && PY.nstage > 0 && PY.radix[0] == 16;
+    const bool edge = !R3 && PY.nstage > 0 && PY.radix[0] == 16;
     const int S0 = ny >> 4;
     if (phase == 1 && edge && (PY.flags & 1)) {
         kspec_stage0_fwd_from(kspec_lds, sstride, ncol, PY.lg, tw, [&](int cl, int i, int q) {
@@ -826,7 +838,7 @@ __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY
         for (int u = 0; u < 8; u++) {
             const int idx = base + u * blockDim.x + threadIdx.x;
             if (idx < ncol * half) {
-                const int c = c0 + (idx >> lg_half), y = 2 * (idx & (half - 1));
+                const int cl = kspec_div<R3>(lg_half, idx), c = c0 + cl, y = 2 * kspec_mod<R3>(half, idx, cl);
                 t[u] = (phase == 1 && lg_rb >= 0)
                            ? *reinterpret_cast<const float4 *>(Wt + (long long)p0 * nxl * ny + kspec_wt_index(PY.lgw, lg_rb, ny >> lg_rb, nxl, y >> lg_rb, c ? jB : jA, y & ((1 << lg_rb) - 1)))
                            : *reinterpret_cast<const float4 *>(colat(W, c, y));
@@ -836,10 +848,10 @@ __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY
         for (int u = 0; u < 8; u++) {
             const int idx = base + u * blockDim.x + threadIdx.x;
             if (idx < ncol * half) {
-                const int cl = idx >> lg_half, y = 2 * (idx & (half - 1));
+                const int cl = kspec_div<R3>(lg_half, idx), y = 2 * kspec_mod<R3>(half, idx, cl);
                 kcf *q = kspec_lds + cl * sstride;
-                q[kspec_pad(y)] = make_float2(t[u].x, t[u].y);
-                q[kspec_pad(y + 1)] = make_float2(t[u].z, t[u].w);
+                q[kspec_lp<R3>(PY, y)] = make_float2(t[u].x, t[u].y);
+                q[kspec_lp<R3>(PY, y + 1)] = make_float2(t[u].z, t[u].w);
             }
         }
     }
@@ -848,7 +860,7 @@ __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY
     if (phase == 1) kspec_fft_fwd(PY, kspec_lds, sstride, ncol, tw);
     else {
         if (one) { KSPEC_NL_SWITCH(S.nlig, (kspec_cols_symbol_split1<NL>(PY, kspec_lds, self, c0, kxA, kxB, p0, W, nxl, lg_pl, pstride, jA, jB, posy, kyofpos, lx, ly, S))); }
-        else { KSPEC_NL_SWITCH(S.nlig, (kspec_cols_symbol_split<NL>(PY, kspec_lds, sstride, self, kxA, kxB, p0, W, nxl, lg_pl, pstride, jA, jB, posy, kyofpos, lx, ly, S))); }
+        else { KSPEC_NL_SWITCH(S.nlig, (kspec_cols_symbol_split<NL, R3>(PY, kspec_lds, sstride, self, kxA, kxB, p0, W, nxl, lg_pl, pstride, jA, jB, posy, kyofpos, lx, ly, S))); }
         __syncthreads();
         if (edge && (PY.flags & 2)) {
             kspec_fft_inv(PY, kspec_lds, sstride, ncol, tw, 1);
@@ -862,9 +874,9 @@ __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY
         dst = Wout;
     }
     for (int idx = threadIdx.x; idx < ncol * half; idx += blockDim.x) {
-        const int cl = idx >> lg_half, y = 2 * (idx & (half - 1));
+        const int cl = kspec_div<R3>(lg_half, idx), y = 2 * kspec_mod<R3>(half, idx, cl);
         const kcf *q = kspec_lds + cl * sstride;
-        const kcf c0v = q[kspec_pad(y)], c1v = q[kspec_pad(y + 1)];
+        const kcf c0v = q[kspec_lp<R3>(PY, y)], c1v = q[kspec_lp<R3>(PY, y + 1)];
         *reinterpret_cast<float4 *>(colat(dst, c0 + cl, y)) = make_float4(c0v.x, c0v.y, c1v.x, c1v.y);
     }
 }
@@ -878,6 +890,8 @@ __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY
 //   k_spec3_z<NL> : PB pairs of columns {(kx,ky), (-kx,-ky)} per block, contiguous in z: DIF, symbol, DIT inverse, in place
 //   k_spec3_y_inv : reads CZ-z segments of W2, DIT inverse along y, stores W3[pair][pos_x][z*ny + y] (contiguous runs of ny)
 // and the inverse x rows over W3.  HBM traffic 48 F N bytes per application (five kernels, four passes over the work arrays).
+// Each of the y and z kernels has two instances, chosen by ITS axis: R3 = false for 2^k points (with the fused edge stages), R3 = true for
+// 3 * 2^k (generic staging, sequences of three padded sub-sequences; one rank) -- a box may mix them.
 // ---------------------------------------------------------------------------------------------
 // global -> LDS staging in batches of 8 items per thread: all loads of a batch are issued before the first LDS store (one memory
 // latency per batch instead of one per item; the plain loop left it to the compiler, which kept them in order)
@@ -893,12 +907,13 @@ __device__ __forceinline__ void kspec_stage_in(int total, LD ld, ST st)
     }
 }
 
+template <bool R3>
 __global__ void __launch_bounds__(1024) k_spec3_y_fwd(KFFTPlan PY, int nx, int nz, int lg_cz, int npair, int lg_rb, const kcf *__restrict__ Wt,
                                                       kcf *__restrict__ W2, const kcf *__restrict__ tw)
 {
     extern __shared__ kcf kspec_lds[];
     const int ny = PY.n, lg_ny = PY.lg, cz = 1 << lg_cz, jx = blockIdx.y, z0 = blockIdx.x * cz;
-    const int sstride = ny + (ny >> 4) + 1;
+    const int sstride = R3 ? kspec_sstride(PY) : ny + (ny >> 4) + 1;
     const int rb = 1 << lg_rb;
     const long long ntiles = ((long long)ny * nz) >> lg_rb;
     const int nseq = npair * cz;
@@ -908,44 +923,45 @@ __global__ void __launch_bounds__(1024) k_spec3_y_fwd(KFFTPlan PY, int nx, int n
         const long long R = (long long)(z0 + zc) * ny + y;
         return Wt[(((long long)p * ntiles + (R >> lg_rb)) * nx + jx) * rb + (R & (rb - 1))];
     };
-    if (PY.m == 1 && PY.radix[0] == 16 && (PY.flags & 1)) {
+    if (!R3 && PY.radix[0] == 16 && (PY.flags & 1)) {
         // first stage on the gathered values themselves (the 16 loads of a thread in flight together, no staging pass: as k_spec_cols)
         const int S0 = ny >> 4;
         kspec_stage0_fwd_from(kspec_lds, sstride, nseq, lg_ny, tw, [&](int s, int i, int q) { return gather(s, i + q * S0); });
         __syncthreads();
         kspec_fft_fwd(PY, kspec_lds, sstride, nseq, tw, 1);
     } else {
-        kspec_stage_in<kcf>(nseq * ny, [&](int idx) { return gather(idx >> lg_ny, idx & (ny - 1)); },
-                            [&](int idx, kcf v) { kspec_lds[(idx >> lg_ny) * sstride + kspec_pad(idx & (ny - 1))] = v; });
+        kspec_stage_in<kcf>(nseq * ny, [&](int idx) { const int s = kspec_div<R3>(lg_ny, idx); return gather(s, kspec_mod<R3>(ny, idx, s)); },
+                            [&](int idx, kcf v) { const int s = kspec_div<R3>(lg_ny, idx); kspec_lds[s * sstride + kspec_lp<R3>(PY, kspec_mod<R3>(ny, idx, s))] = v; });
         __syncthreads();
         kspec_fft_fwd(PY, kspec_lds, sstride, nseq, tw);
     }
     for (int idx = threadIdx.x; idx < nseq * ny; idx += blockDim.x) {
         const int zc = idx & (cz - 1), rest = idx >> lg_cz;
-        const int jy = rest & (ny - 1), p = rest >> lg_ny;
-        W2[(((long long)p * nx + jx) * ny + jy) * nz + z0 + zc] = kspec_lds[(p * cz + zc) * sstride + kspec_pad(jy)];
+        const int p = kspec_div<R3>(lg_ny, rest), jy = kspec_mod<R3>(ny, rest, p);
+        W2[(((long long)p * nx + jx) * ny + jy) * nz + z0 + zc] = kspec_lds[(p * cz + zc) * sstride + kspec_lp<R3>(PY, jy)];
     }
 }
 
+template <bool R3>
 __global__ void __launch_bounds__(1024) k_spec3_y_inv(KFFTPlan PY, int nx, int nz, int lg_cz, int npair, const kcf *__restrict__ W2,
                                                       kcf *__restrict__ W3, const kcf *__restrict__ tw)
 {
     extern __shared__ kcf kspec_lds[];
     const int ny = PY.n, lg_ny = PY.lg, cz = 1 << lg_cz, jx = blockIdx.y, z0 = blockIdx.x * cz;
-    const int sstride = ny + (ny >> 4) + 1;
+    const int sstride = R3 ? kspec_sstride(PY) : ny + (ny >> 4) + 1;
     const int nseq = npair * cz;
     kspec_stage_in<kcf>(nseq * ny, [&](int idx) {
         const int zc = idx & (cz - 1), rest = idx >> lg_cz;
-        const int jy = rest & (ny - 1), p = rest >> lg_ny;
+        const int p = kspec_div<R3>(lg_ny, rest), jy = kspec_mod<R3>(ny, rest, p);
         return W2[(((long long)p * nx + jx) * ny + jy) * nz + z0 + zc];
     }, [&](int idx, kcf v) {
         const int zc = idx & (cz - 1), rest = idx >> lg_cz;
-        const int jy = rest & (ny - 1), p = rest >> lg_ny;
-        kspec_lds[(p * cz + zc) * sstride + kspec_pad(jy)] = v;
+        const int p = kspec_div<R3>(lg_ny, rest), jy = kspec_mod<R3>(ny, rest, p);
+        kspec_lds[(p * cz + zc) * sstride + kspec_lp<R3>(PY, jy)] = v;
     });
     __syncthreads();
     const long long nrows = (long long)ny * nz;
-    if (PY.m == 1 && PY.radix[0] == 16 && (PY.flags & 2)) {
+    if (!R3 && PY.radix[0] == 16 && (PY.flags & 2)) {
         // last stage of the inverse straight into the store (runs of consecutive y per lane group)
         kspec_fft_inv(PY, kspec_lds, sstride, nseq, tw, 1);
         const int S0 = ny >> 4;
@@ -959,13 +975,13 @@ __global__ void __launch_bounds__(1024) k_spec3_y_inv(KFFTPlan PY, int nx, int n
     }
     kspec_fft_inv(PY, kspec_lds, sstride, nseq, tw);
     for (int idx = threadIdx.x; idx < nseq * ny; idx += blockDim.x) {
-        const int s = idx >> lg_ny, y = idx & (ny - 1);
+        const int s = kspec_div<R3>(lg_ny, idx), y = kspec_mod<R3>(ny, idx, s);
         const int p = s >> lg_cz, zc = s & (cz - 1);
-        W3[((long long)p * nx + jx) * nrows + (long long)(z0 + zc) * ny + y] = kspec_lds[s * sstride + kspec_pad(y)];
+        W3[((long long)p * nx + jx) * nrows + (long long)(z0 + zc) * ny + y] = kspec_lds[s * sstride + kspec_lp<R3>(PY, y)];
     }
 }
 
-template <int NL>
+template <int NL, bool R3>
 __device__ __forceinline__ void kspec3_z_symbol(const KFFTPlan &PZ, kcf *kspec_lds, int sstride, int ne, int e0, const int4 *__restrict__ pairtab, const int *__restrict__ posz,
                                                 const int *__restrict__ kzofpos, const float *__restrict__ lx, const float *__restrict__ ly, const float *__restrict__ lz,
                                                 const int2 *__restrict__ ztab, const KSpecSym &S)
@@ -973,14 +989,14 @@ __device__ __forceinline__ void kspec3_z_symbol(const KFFTPlan &PZ, kcf *kspec_l
     constexpr int F = NL + 1, npair = (F + 1) / 2;
     const int nz = PZ.n, half = nz >> 1;
     for (int item = threadIdx.x; item < ne * nz; item += blockDim.x) {
-        const int slot = item >> PZ.lg, mpos = item & (nz - 1);
+        const int slot = kspec_div<R3>(PZ.lg, item), mpos = kspec_mod<R3>(nz, item, slot);
         const int4 pt = pairtab[e0 + slot];
         // ztab[pos] = (position of -kz, bits of lz[kz]), kz = the wavenumber at position pos: one coalesced load instead of the dependent
         // chain kzofpos[pos] -> posz[-kz], lz[kz] (as in k_spec_cols); only the four self-paired columns still need kz itself
         const int2 zt = ztab[mpos];
         const bool self = pt.w != 0;
         if (self && kzofpos[mpos] > half) continue;                // (A, kz) and (A, -kz) are one item
-        const int m = kspec_pad(mpos), mp = kspec_pad(zt.x);
+        const int m = kspec_lp<R3>(PZ, mpos), mp = kspec_lp<R3>(PZ, zt.x);
         const float L2 = lx[pt.z & 0xffff] + ly[pt.z >> 16] + __int_as_float(zt.y);
         const int sa = slot * npair * 2, cb = self ? 0 : 1;
         kcf a[npair], b[npair];
@@ -995,7 +1011,7 @@ __device__ __forceinline__ void kspec3_z_symbol(const KFFTPlan &PZ, kcf *kspec_l
 // pairtab[e] = (column A, column B, kx | ky << 16, self) with column = pos_x * ny + pos_y; self: A == B is its own partner
 // Column storage as in k_spec_cols: a column consists of nz >> lg_pl pieces of 2^lg_pl elements, `pstride` elements apart (one piece
 // per z-slab rank after the all-to-all; a single piece on one rank).
-template <int NPAIR_T>      // as k_spec_cols: 1, 2 or 0 = run-time number of field pairs
+template <int NPAIR_T, bool R3>      // NPAIR_T as k_spec_cols: 1, 2 or 0 = run-time number of field pairs; R3: nz = 3 * 2^lg (one rank)
 __global__ void __launch_bounds__(1024) k_spec3_z(KFFTPlan PZ, int nent, int pb, long long ncol, int lg_pl, long long pstride, kcf *__restrict__ W2, const kcf *__restrict__ tw,
                                                   const int4 *__restrict__ pairtab, const int *__restrict__ posz, const int *__restrict__ kzofpos,
                                                   const float *__restrict__ lx, const float *__restrict__ ly, const float *__restrict__ lz, const int2 *__restrict__ ztab, KSpecSym S)
@@ -1003,7 +1019,7 @@ __global__ void __launch_bounds__(1024) k_spec3_z(KFFTPlan PZ, int nent, int pb,
     extern __shared__ kcf kspec_lds[];
     const int npair = NPAIR_T ? NPAIR_T : (S.nlig + 2) / 2;
     const int nz = PZ.n;
-    const int sstride = nz + (nz >> 4) + 1;
+    const int sstride = R3 ? kspec_sstride(PZ) : nz + (nz >> 4) + 1;
     const int e0 = blockIdx.x * pb;
     const int ne = min(pb, nent - e0);
     const int nseq = 2 * npair * ne;                              // sequence s = (slot*npair + p)*2 + c
@@ -1012,10 +1028,11 @@ __global__ void __launch_bounds__(1024) k_spec3_z(KFFTPlan PZ, int nent, int pb,
     auto colptr = [&](int s) {                                     // start of the column's FIRST piece
         const int c = s & 1, p = (s >> 1) % npair, slot = (s >> 1) / npair;
         const int4 pt = pairtab[e0 + slot];
+        if (R3) return W2 + ((long long)p * ncol + (c ? pt.y : pt.x)) * nz;        // one piece of exactly nz elements
         return W2 + (((long long)p * ncol + (c ? pt.y : pt.x)) << lg_pl);
     };
-    auto zoff = [&](int z) { return (long long)(z >> lg_pl) * pstride + (z & plmask); };      // z even: a float4 never straddles two pieces
-    const bool edge_in = PZ.m == 1 && PZ.radix[0] == 16 && (PZ.flags & 1), edge_out = PZ.m == 1 && PZ.radix[0] == 16 && (PZ.flags & 2);
+    auto zoff = [&](int z) { return R3 ? (long long)z : (long long)(z >> lg_pl) * pstride + (z & plmask); };      // z even: a float4 never straddles two pieces
+    const bool edge_in = !R3 && PZ.radix[0] == 16 && (PZ.flags & 1), edge_out = !R3 && PZ.radix[0] == 16 && (PZ.flags & 2);
     const int S0 = nz >> 4;
     if (edge_in) {
         kspec_stage0_fwd_from(kspec_lds, sstride, nseq, PZ.lg, tw, [&](int s, int i, int q) { return colptr(s)[zoff(i + q * S0)]; });
@@ -1023,22 +1040,22 @@ __global__ void __launch_bounds__(1024) k_spec3_z(KFFTPlan PZ, int nent, int pb,
         kspec_fft_fwd(PZ, kspec_lds, sstride, nseq, tw, 1);
     } else {
     kspec_stage_in<float4>(nseq * half, [&](int idx) {
-        const int s = idx >> lg_half, z = 2 * (idx & (half - 1));
+        const int s = kspec_div<R3>(lg_half, idx), z = 2 * kspec_mod<R3>(half, idx, s);
         return *reinterpret_cast<const float4 *>(colptr(s) + zoff(z));
     }, [&](int idx, float4 t) {
-        const int s = idx >> lg_half, z = 2 * (idx & (half - 1));
+        const int s = kspec_div<R3>(lg_half, idx), z = 2 * kspec_mod<R3>(half, idx, s);
         kcf *q = kspec_lds + s * sstride;
-        q[kspec_pad(z)] = make_float2(t.x, t.y);
-        q[kspec_pad(z + 1)] = make_float2(t.z, t.w);
+        q[kspec_lp<R3>(PZ, z)] = make_float2(t.x, t.y);
+        q[kspec_lp<R3>(PZ, z + 1)] = make_float2(t.z, t.w);
     });
     __syncthreads();
     kspec_fft_fwd(PZ, kspec_lds, sstride, nseq, tw);
     }
-    if (NPAIR_T == 1) kspec3_z_symbol<1>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S);
+    if (NPAIR_T == 1) kspec3_z_symbol<1, R3>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S);
     else if (NPAIR_T == 2) {
-        if (S.nlig == 2) kspec3_z_symbol<2>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S);
-        else kspec3_z_symbol<3>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S);
-    } else { KSPEC_NL_SWITCH(S.nlig, (kspec3_z_symbol<NL>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S))); }
+        if (S.nlig == 2) kspec3_z_symbol<2, R3>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S);
+        else kspec3_z_symbol<3, R3>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S);
+    } else { KSPEC_NL_SWITCH(S.nlig, (kspec3_z_symbol<NL, R3>(PZ, kspec_lds, sstride, ne, e0, pairtab, posz, kzofpos, lx, ly, lz, ztab, S))); }
     __syncthreads();
     if (edge_out) {
         kspec_fft_inv(PZ, kspec_lds, sstride, nseq, tw, 1);
@@ -1052,10 +1069,10 @@ __global__ void __launch_bounds__(1024) k_spec3_z(KFFTPlan PZ, int nent, int pb,
     }
     kspec_fft_inv(PZ, kspec_lds, sstride, nseq, tw);
     for (int idx = threadIdx.x; idx < nseq * half; idx += blockDim.x) {
-        const int s = idx >> lg_half, z = 2 * (idx & (half - 1));
+        const int s = kspec_div<R3>(lg_half, idx), z = 2 * kspec_mod<R3>(half, idx, s);
         if ((s & 1) && pairtab[e0 + (s >> 1) / npair].w) continue;      // the B slot of a self column is a copy
         const kcf *q = kspec_lds + s * sstride;
-        const kcf c0 = q[kspec_pad(z)], c1 = q[kspec_pad(z + 1)];
+        const kcf c0 = q[kspec_lp<R3>(PZ, z)], c1 = q[kspec_lp<R3>(PZ, z + 1)];
         *reinterpret_cast<float4 *>(colptr(s) + zoff(z)) = make_float4(c0.x, c0.y, c1.x, c1.y);
     }
 }

@@ -17,7 +17,8 @@ template <typename T> static bool spec_upload(T **dev, const std::vector<T> &hos
            hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice) == hipSuccess;
 }
 
-// 3-D (see spectral.hip.h): plans per axis, the column-pair table of the z kernel, two work arrays.  z-slab ranks (P = 2, 4, 8): the
+// 3-D (see spectral.hip.h): plans per axis, the column-pair table of the z kernel, two work arrays.  One rank: every extent with a plan,
+// 2^k or 3 * 2^k per axis (the y and z kernels have an instance for each: template parameter R3).  z-slab ranks (P = 2, 4, 8), 2^k only: the
 // x and y transforms are local (a rank owns whole z planes); for the z transforms every rank needs whole z columns, so
 // W[pair][pos_x][pos_y][z_local] is redistributed by an all-to-all over pos_x exactly as in 2-D (same digit ownership: the columns
 // (kx, ky) and (-kx, -ky) land on one rank), a received column consisting of P pieces of nz/P elements.
@@ -32,13 +33,13 @@ static void spec_build3d(ksfd_handle *h)
     if (ring && (!h->tr || !h->tr->has_alltoall() || (P != 1 && P != 2 && P != 4 && P != 8) || getenv("KSFD_SPEC_SINGLE"))) return;
     const long long nzg = h->cfg.n[2], nzl = G.sloc;               // global / local z planes
     if (!spec_plan(G.nx, S.px) || !spec_plan(G.ny, S.py) || !spec_plan(nzg, S.pz)) return;
-    if (S.px.m != 1 || S.py.m != 1 || S.pz.m != 1) return;           // (3 * 2^k extents: 2-D only)
-    if (S.px.radix[0] != 16 || G.nx > 32768 || G.ny > 32768 || (nzl & (nzl - 1)) || nzl < 2) return;
+    if (ring && (S.px.m != 1 || S.py.m != 1 || S.pz.m != 1 || (nzl & (nzl - 1)))) return;      // (3 * 2^k extents: one rank without a halo transport only)
+    if (S.px.radix[0] != 16 || G.nx > 32768 || G.ny > 32768 || nzl < 2) return;
     S.dim = 3;
     S.npair = (G.F + 1) / 2;
     const size_t lds_max = 160 * 1024 - 1024;
     const long long nrows = G.ny * nzl;
-    const size_t row_bytes = sizeof(kcf) * (size_t)(G.nx + (G.nx >> 4) + 1);
+    const size_t row_bytes = sizeof(kcf) * spec_sstride(S.px);
     int rb = 16;
     while (rb > 1 && row_bytes * rb > lds_max) rb >>= 1;
     while (rb > 2 && nrows / rb < 512) rb >>= 1;
@@ -47,7 +48,7 @@ static void spec_build3d(ksfd_handle *h)
     S.nyp = (int)nrows;                                            // column stride of the array the inverse row kernel reads
     S.lg_rb3 = 0; while ((1 << S.lg_rb3) < rb) S.lg_rb3++;
     S.lds_rows = row_bytes * rb;
-    const size_t ycol = sizeof(kcf) * (size_t)(G.ny + (G.ny >> 4) + 1) * S.npair, zcol = sizeof(kcf) * (size_t)(nzg + (nzg >> 4) + 1) * 2 * S.npair;
+    const size_t ycol = sizeof(kcf) * spec_sstride(S.py) * S.npair, zcol = sizeof(kcf) * spec_sstride(S.pz) * 2 * S.npair;
     int cz = 16;
     while (cz > 1 && (ycol * cz > lds_max / 2 || nzl % cz)) cz >>= 1;      // <= half the LDS: two blocks per CU
     if (getenv("KSFD_SPEC_CZ")) cz = std::max(1, std::min(cz, atoi(getenv("KSFD_SPEC_CZ"))));        // experiment knob
@@ -64,11 +65,13 @@ static void spec_build3d(ksfd_handle *h)
         hipError_t e = hipFuncSetAttribute((const void *)k_spec_rows_fwd<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_spec_rows_fwd<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_spec_rows_inv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_spec3_y_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_y3);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_spec3_y_inv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_y3);
-        if (e == hipSuccess) e = S.npair == 1 ? hipFuncSetAttribute((const void *)k_spec3_z<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_z3)
-                               : S.npair == 2 ? hipFuncSetAttribute((const void *)k_spec3_z<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_z3)
-                                              : hipFuncSetAttribute((const void *)k_spec3_z<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_z3);
+        const bool y3 = S.py.m == 3, z3 = S.pz.m == 3;             // the kernel instances spec_apply launches
+        if (e == hipSuccess) e = hipFuncSetAttribute(y3 ? (const void *)k_spec3_y_fwd<true> : (const void *)k_spec3_y_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_y3);
+        if (e == hipSuccess) e = hipFuncSetAttribute(y3 ? (const void *)k_spec3_y_inv<true> : (const void *)k_spec3_y_inv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_y3);
+        const void *kz = S.npair == 1 ? (z3 ? (const void *)k_spec3_z<1, true> : (const void *)k_spec3_z<1, false>)
+                       : S.npair == 2 ? (z3 ? (const void *)k_spec3_z<2, true> : (const void *)k_spec3_z<2, false>)
+                                      : (z3 ? (const void *)k_spec3_z<0, true> : (const void *)k_spec3_z<0, false>);
+        if (e == hipSuccess) e = hipFuncSetAttribute(kz, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_z3);
         if (e != hipSuccess) { hipGetLastError(); return; }
     }
     // ownership of the x positions (as in 2-D): top digit -> (rank, index of the digit in that rank's list)
@@ -168,13 +171,13 @@ static void spec_build(ksfd_handle *h)
         S.lds_cols = sizeof(kcf) * spec_sstride(S.py);
     }
     if (S.lds_cols > lds_max - 1024) return;
-    if (S.cols_split && !pow2) return;                               // (the two-phase column kernel is power-of-two only)
+    if (S.cols_split && !pow2 && ring) return;                       // (slab ranks: the two-phase column kernel is power-of-two only)
     if (hipFuncSetAttribute((const void *)k_spec_rows_fwd<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_spec_rows_fwd<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_spec_rows_inv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows) != hipSuccess) { hipGetLastError(); return; }
     {
         hipError_t e = hipSuccess;
-        e = S.cols_split ? hipFuncSetAttribute((const void *)k_spec_cols_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_cols)
+        e = S.cols_split ? hipFuncSetAttribute(S.py.m == 3 ? (const void *)k_spec_cols_split<true> : (const void *)k_spec_cols_split<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_cols)
                          : S.npair == 1 ? hipFuncSetAttribute((const void *)k_spec_cols<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_cols)
                          : S.npair == 2 ? hipFuncSetAttribute((const void *)k_spec_cols<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_cols)
                                         : hipFuncSetAttribute((const void *)k_spec_cols<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_cols);
@@ -338,8 +341,9 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
     if (d3) {
         const int cz = 1 << S.lg_cz;
         const long long nzg = h->cfg.n[2], nzl = G.sloc;
-        const int thr_y = (int)std::min<long long>(1024, std::max<long long>(256, (long long)S.npair * cz * G.ny / 16));
-        int thr_z = (int)std::min<long long>(1024, std::max<long long>(128, (long long)2 * S.npair * S.pb * nzg / 16));
+        // (whole waves: 3 * 2^k extents with three or more field pairs give odd multiples of 32)
+        const int thr_y = (int)std::min<long long>(1024, std::max<long long>(256, ((long long)S.npair * cz * G.ny / 16 + 63) & ~63LL));
+        int thr_z = (int)std::min<long long>(1024, std::max<long long>(128, ((long long)2 * S.npair * S.pb * nzg / 16 + 63) & ~63LL));
         if (getenv("KSFD_SPEC_THRZ")) thr_z = atoi(getenv("KSFD_SPEC_THRZ"));
         // fused edge stages of the y and z kernels (bit 0: first forward stage on the loaded values, bit 1: last inverse stage into the store)
         static const int fuse3 = getenv("KSFD_SPEC_FUSE3") ? atoi(getenv("KSFD_SPEC_FUSE3")) : 3;
@@ -347,8 +351,10 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
         py3.flags = pz3.flags = fuse3 & 3;
         {
             Scope sc(h, KC_SPECTRAL, 2.0 * pn, 0.0);
-            hipLaunchKernelGGL(k_spec3_y_fwd, dim3((unsigned)(nzl / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzl, S.lg_cz, S.npair, S.lg_rb3,
-                               (const kcf *)S.W2, S.W, (const kcf *)S.twy);
+#define KSPEC_YF_LAUNCH(R3) hipLaunchKernelGGL(k_spec3_y_fwd<R3>, dim3((unsigned)(nzl / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzl, S.lg_cz, S.npair, S.lg_rb3, \
+                               (const kcf *)S.W2, S.W, (const kcf *)S.twy)
+            if (py3.m == 3) KSPEC_YF_LAUNCH(true); else KSPEC_YF_LAUNCH(false);
+#undef KSPEC_YF_LAUNCH
         }
         kcf *Wz = S.W;
         if (h->ring) {                                                // z planes of everybody's columns -> whole z columns of mine
@@ -359,9 +365,10 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
         {
             Scope sc(h, KC_SPECTRAL, 2.0 * pn, 0.0);
             const long long pstride = (long long)S.npair * S.nxl * G.ny << S.lg_pl;
-#define KSPEC_Z_LAUNCH(NP) hipLaunchKernelGGL(k_spec3_z<NP>, dim3((unsigned)((S.nent + S.pb - 1) / S.pb)), dim3(thr_z), S.lds_z3, h->st, pz3, S.nent, S.pb, (long long)S.nxl * G.ny, S.lg_pl, pstride, Wz, \
+#define KSPEC_Z_LAUNCH(NP) hipLaunchKernelGGL((k_spec3_z<NP, R3>), dim3((unsigned)((S.nent + S.pb - 1) / S.pb)), dim3(thr_z), S.lds_z3, h->st, pz3, S.nent, S.pb, (long long)S.nxl * G.ny, S.lg_pl, pstride, Wz, \
                                (const kcf *)S.twz, (const int4 *)S.pairtab, (const int *)S.posz, (const int *)S.kzofpos, (const float *)S.lx, (const float *)S.ly, (const float *)S.lz, (const int2 *)S.ytab, Y)
-            if (S.npair == 1) KSPEC_Z_LAUNCH(1); else if (S.npair == 2) KSPEC_Z_LAUNCH(2); else KSPEC_Z_LAUNCH(0);
+            if (pz3.m == 3) { constexpr bool R3 = true; if (S.npair == 1) KSPEC_Z_LAUNCH(1); else if (S.npair == 2) KSPEC_Z_LAUNCH(2); else KSPEC_Z_LAUNCH(0); }
+            else { constexpr bool R3 = false; if (S.npair == 1) KSPEC_Z_LAUNCH(1); else if (S.npair == 2) KSPEC_Z_LAUNCH(2); else KSPEC_Z_LAUNCH(0); }
 #undef KSPEC_Z_LAUNCH
         }
         if (h->ring) {
@@ -370,8 +377,10 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
         }
         {
             Scope sc(h, KC_SPECTRAL, 2.0 * pn, 0.0);
-            hipLaunchKernelGGL(k_spec3_y_inv, dim3((unsigned)(nzl / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzl, S.lg_cz, S.npair,
-                               (const kcf *)S.W, S.W2, (const kcf *)S.twy);
+#define KSPEC_YI_LAUNCH(R3) hipLaunchKernelGGL(k_spec3_y_inv<R3>, dim3((unsigned)(nzl / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzl, S.lg_cz, S.npair, \
+                               (const kcf *)S.W, S.W2, (const kcf *)S.twy)
+            if (py3.m == 3) KSPEC_YI_LAUNCH(true); else KSPEC_YI_LAUNCH(false);
+#undef KSPEC_YI_LAUNCH
         }
         // the inverse x rows read W3 = S.W2 ([pair][pos_x][z*ny + y]) below
     } else {
@@ -389,10 +398,11 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
         if (S.cols_split) {
             // one rank: tiles (W2) -> spectrum (W) -> result (W2); slab ranks: in place in W2, then result into W as scratch
             kcf *spec = h->ring ? S.W2 : S.W, *res = h->ring ? S.W : S.W2;
-            for (int phase = 1; phase <= 2; phase++)
-                hipLaunchKernelGGL(k_spec_cols_split, dim3((unsigned)S.nblk_cols, (unsigned)S.npair, S.cols_split == 2 ? 2u : 1u), dim3(thr_cols), S.lds_cols, h->st, phase, py_c, S.nxl, S.lg_pl, pstride, spec,
-                                   (const kcf *)(S.tile_major ? S.W2 : nullptr), S.tile_major ? lg_rb : -1, res, (const kcf *)S.twy,
-                                   (const int4 *)S.pairtab, (const int *)S.posy, (const int *)S.kyofpos, (const float *)S.lx, (const float *)S.ly, Y);
+#define KSPEC_SPLIT_LAUNCH(R3) hipLaunchKernelGGL(k_spec_cols_split<R3>, dim3((unsigned)S.nblk_cols, (unsigned)S.npair, S.cols_split == 2 ? 2u : 1u), dim3(thr_cols), S.lds_cols, h->st, phase, py_c, S.nxl, S.lg_pl, pstride, spec, \
+                                   (const kcf *)(S.tile_major ? S.W2 : nullptr), S.tile_major ? lg_rb : -1, res, (const kcf *)S.twy, \
+                                   (const int4 *)S.pairtab, (const int *)S.posy, (const int *)S.kyofpos, (const float *)S.lx, (const float *)S.ly, Y)
+            for (int phase = 1; phase <= 2; phase++) { if (S.py.m == 3) KSPEC_SPLIT_LAUNCH(true); else KSPEC_SPLIT_LAUNCH(false); }
+#undef KSPEC_SPLIT_LAUNCH
         } else {
 #define KSPEC_COLS_LAUNCH(NP) hipLaunchKernelGGL(k_spec_cols<NP>, dim3((unsigned)S.nblk_cols), dim3(thr_cols), S.lds_cols, h->st, py_c, S.nxl, S.lg_pl, pstride, Wc, \
                            (const kcf *)(S.tile_major ? S.W2 : nullptr), S.tile_major ? lg_rb : -1, (const kcf *)S.twy, \
