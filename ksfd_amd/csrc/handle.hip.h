@@ -55,13 +55,7 @@ struct SpecState {
     std::vector<A2APiece> a2a_fwd_s, a2a_fwd_r, a2a_bwd_s, a2a_bwd_r;
     float *lx = nullptr, *ly = nullptr;
     double a_rr = 0.0, a_rU[KSFD_MAXL] = { 0 };
-    // adaptation: steps (counted by ksfd_step calls) before which the automatic choice leaves it alone after it converged badly
-    long long bad_until = 0;
     bool user_off = false;                   // ksfd_set_spectral_params(enable = 0): off until enabled again; a checkpoint restore does not bring it back
-    int backoff = 8;
-    // largest contraction ||r_k+1|| / ||r_k|| of a defect-correction sweep measured in the current / the previous step
-    // (spec_solve: predicted last sweep)
-    double rho_step = 0.0, rho_prev = 0.0;
 };
 
 // dense direct solver, pc_type 5 (lu.hip.h / lu_host.hip.h): buffers allocated on first use, factors rebuilt every step attempt
@@ -112,12 +106,11 @@ struct ksfd_handle {
     long long n_predicted = 0;              // ... how many solves ended that way
     long long n_residual = 0;               // true residuals evaluated by the spectral defect correction
     long long n_host_sync = 0;              // host waits on the device so far (reduction results, stream synchronisations)
-    struct SolverMemo { double lamJ; int lam_age, lam_period; double mg_shift_floor; int sf_dir, sf_hold; bool sf_tried_down; double sf_prev_its, sf_prev_floor;
-                        long long nsteps, spec_bad_until; int spec_backoff; double spec_rho_step, spec_rho_prev; };
     SpecState spec;
-    long long nsteps = 0;                   // ksfd_step calls so far
+    // what the solvers remember from one step to the next (step_control.h), and the copy a checkpoint holds: besides the state vector
+    // this is all that ksfd_checkpoint saves and restores
+    ksfd_ctl::StepMemo memo, ckpt_memo;
     double spec_from = 0.1;                 // stiffness above which pc_type 2 prefers the spectral solver (below: plain GMRES; measured at 4096^2, X = 0.19: 6 sweeps = 7.3 ms against 5 GMRES iterations = 7.9 ms per step)
-    SolverMemo ckpt_memo;
     bool ckpt_valid = false;
     double *Gb = nullptr, *dGb = nullptr;   // generic-path scratch planes
     double *coef = nullptr;                 // frozen-Jacobian coefficient planes [rho, G, G_rho, G_U..]
@@ -162,8 +155,6 @@ struct ksfd_handle {
     // polynomial (Chebyshev) preconditioner + flexible GMRES (see poly_setup / gmres)
     double *Zb = nullptr;           // preconditioned basis z_j = p(A) v_j (allocated on first use)
     double *pvec = nullptr;         // power-iteration vector for lambda_max(A)
-    double lamJ = -1.0;             // running estimate of lambda_max(-J) = lambda_max(A) - shift
-    int lam_age = 0, lam_period = 1;   // steps since the last estimate / re-estimate every lam_period steps (1..8, grows while stable)
     int poly_deg = 0;
     double poly_alpha[8];           // z = sum_i alpha_i (A/shift)^i v
     double poly_shift = -1.0;
@@ -207,11 +198,7 @@ struct ksfd_handle {
 
     // multigrid preconditioner
     std::vector<MGLevel> mg;
-    double mg_shift_floor = 0.0;  // lower bound on the shift the multigrid hierarchy is built for (see gmres)
-    // online search for that floor (ksfd_step): hill climbing in log2(floor) on the iterations per step
-    int sf_dir = 0, sf_hold = 0;  // +1 doubling, -1 halving, 0 settled (and steps to wait before the next probe)
-    bool sf_tried_down = false, sf_auto = true;
-    double sf_prev_its = 0.0, sf_prev_floor = 0.0;
+    bool sf_auto = true;         // online search for memo.mg_shift_floor (shift_floor_update); KSFD_PC_SIGMA fixes the floor instead
     bool mg_fp32 = true;         // V cycle with fp32 level vectors when the solve tolerance allows (KSFD_TUNE bit 19 clears); see mg_vcycle32
     bool mg_use32 = false;       // ... decided per step by ksfd_step (ksp_rtol >= 1e-7)
     bool mg_graph_f32 = false;   // precision the captured coarse cycle was recorded in

@@ -33,14 +33,14 @@ static int est_lambda_max(ksfd_handle *h, double shift, int nits)
         if ((rc = op_lincomb(h, 1, xs, a, h->pvec))) return rc;
     }
     const double est = lamA - shift;
-    h->lamJ = est > 0.0 ? est : 0.0;
+    h->memo.lamJ = est > 0.0 ? est : 0.0;
     return KSFD_OK;
 }
 
 // coefficients of p for this shift; degree 0 = "do not precondition"
 static void poly_setup(ksfd_handle *h, double shift)
 {
-    const double a = 0.97, b = 1.0 + 1.15 * h->lamJ / shift;      // spectrum of A/shift (power iteration converges from below: +15 %)
+    const double a = 0.97, b = 1.0 + 1.15 * h->memo.lamJ / shift;      // spectrum of A/shift (power iteration converges from below: +15 %)
     h->poly_shift = shift;
     h->poly_deg = 0;
     const double kappa = b / a;
@@ -160,10 +160,10 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
     // tolerance of the original system)
     const bool use_pc = pcmode == 1;       // multigrid, right preconditioning
     h->dr.valid = false;                   // this solve builds in V: a relation kept by the deflated solver (krylov_dr.hip.h) is gone
-    // the hierarchy may be built for a LARGER shift than the system's (h->mg_shift_floor): when 1/(gamma h) falls below the growth
+    // the hierarchy may be built for a LARGER shift than the system's (h->memo.mg_shift_floor): when 1/(gamma h) falls below the growth
     // rate of the chemotactic instability, shift*I - J is indefinite and a V cycle of it is no contraction; the V cycle of the
     // positively shifted operator still is, and GMRES (true residual of the real system) takes care of the difference
-    const double shift_pc = std::max(shift, h->mg_shift_floor);
+    const double shift_pc = std::max(shift, h->memo.mg_shift_floor);
     const bool use_poly = pcmode == 2 || pcmode == 3;     // flexible GMRES (z_j = M^-1 v_j kept in Zb): 2 Chebyshev polynomial p(A), 3 spectral (spectral_host.hip.h)
     // use_pc: right preconditioning with one multigrid V cycle, w = A (M^-1 v_j), x = M^-1 (V y)
     auto apply_A = [&](const double *vin, double *wout) -> int {
@@ -491,7 +491,7 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
         if (rc) return rc;
         ls->its++;
         if (final_pending) {
-            const double rho_hat = std::max(h->spec.rho_step, h->spec.rho_prev);
+            const double rho_hat = std::max(h->memo.spec_rho_step, h->memo.spec_rho_prev);
             ls->rel = PRED_SAFETY * rho_hat * rn / bn;                            // the bound the decision was made on
             h->n_predicted++;
             if (verify_env == 1) {
@@ -524,9 +524,9 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
         // initial guess.  The first sweep from zero is a class of its own and is neither recorded nor predicted from: b = f(u) is
         // smooth, (I - A M^-1) b = dJ M^-1 b is several times larger relative to b (3-6 % on the bench window) than the same operator
         // makes of the rough residuals that follow (0.6-1 %), and after one sweep a residual never is that smooth again.
-        if (k >= 1) h->spec.rho_step = std::max(h->spec.rho_step, rn / rprev);
+        if (k >= 1) h->memo.spec_rho_step = std::max(h->memo.spec_rho_step, rn / rprev);
         rprev = rn;
-        const double rho_hat = std::max(h->spec.rho_step, h->spec.rho_prev);
+        const double rho_hat = std::max(h->memo.spec_rho_step, h->memo.spec_rho_prev);
         if (predict && rho_hat > 0.0 && (k >= 1 || guess) && k + 1 < maxit && PRED_SAFETY * rho_hat * rn <= tol) final_pending = true;
     }
     if (fused && (rc = op_jvp_frozen(h, x, 2, shift, r, b))) return rc;       // the correction solve below wants the residual in fp64

@@ -36,7 +36,7 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     // preconditioning misses the true one by more than the tolerance (measured: 107 failed checks in 30 steps of the 384^2 run at
     // ksp_rtol = 1e-6, every one answered with more iterations), and the update costs a V cycle of its own.
     const bool use_pc = pcmode == 1, use_flex = pcmode == 1 || pcmode == 2;
-    const double shift_pc = std::max(shift, h->mg_shift_floor);
+    const double shift_pc = std::max(shift, h->memo.mg_shift_floor);
     const int m = std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc);
     const int keep = h->dr_keep;
     const int maxit = o->ksp_max_it > 0 ? o->ksp_max_it : 2000;

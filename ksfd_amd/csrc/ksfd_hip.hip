@@ -1,6 +1,7 @@
-// libksfd_hip.so -- C ABI (include/ksfd_hip.h) and the Rosenbrock-W step; handle, launch wrappers, multigrid and Krylov
-// solvers live in handle.hip.h / ops.hip.h / mg_host.hip.h / krylov.hip.h (one translation unit).  Together they
-// stand in for petsc4py TS.step() in the reference (KSFD/ksfdts.py:211).
+// libksfd_hip.so -- C ABI (include/ksfd_hip.h) and the attempt loop of the Rosenbrock-W step (ksfd_step); handle, launch wrappers,
+// multigrid and Krylov solvers live in handle.hip.h / ops.hip.h / mg_host.hip.h / krylov.hip.h, the parts of a step attempt in
+// step.hip.h (one translation unit), the step's decisions and its step-to-step memory (StepMemo) as plain C++ in step_control.h.
+// Together they stand in for petsc4py TS.step() in the reference (KSFD/ksfdts.py:211).
 // gfx950 only.  No CPU fallback: every entry point runs HIP kernels or fails.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -18,7 +19,7 @@
 #include "spectral.hip.h"
 #include "lu.hip.h"
 #include "transport.h"
-
+#include "step_control.h"
 
 #include "handle.hip.h"
 #include "ops.hip.h"
@@ -27,6 +28,7 @@
 #include "krylov.hip.h"
 #include "krylov_dr.hip.h"
 #include "lu_host.hip.h"
+#include "step.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -338,8 +340,7 @@ extern "C" int ksfd_checkpoint(ksfd_handle *h, int32_t op)
     if (op == 0) {
         if (!h->ckpt && alloc_d(h, &h->ckpt, h->vlen)) return KSFD_ENOMEM;
         HIPCHK(h, hipMemcpyAsync(h->ckpt, h->u, sizeof(double) * (size_t)h->vlen, hipMemcpyDeviceToDevice, h->st));
-        h->ckpt_memo = { h->lamJ, h->lam_age, h->lam_period, h->mg_shift_floor, h->sf_dir, h->sf_hold, h->sf_tried_down, h->sf_prev_its, h->sf_prev_floor,
-                         h->nsteps, h->spec.bad_until, h->spec.backoff, h->spec.rho_step, h->spec.rho_prev };
+        h->ckpt_memo = h->memo;
         for (MGLevel &L : h->mg) L.pv_norm = 0.0;       // the step after a save and the step after a restore both set the hierarchy up cold
         h->ckpt_valid = true;
         return KSFD_OK;
@@ -347,11 +348,8 @@ extern "C" int ksfd_checkpoint(ksfd_handle *h, int32_t op)
     if (!h->ckpt_valid) return fail(h, KSFD_EINVAL, "no checkpoint has been saved");
     HIPCHK(h, hipMemcpyAsync(h->u, h->ckpt, sizeof(double) * (size_t)h->vlen, hipMemcpyDeviceToDevice, h->st));
     h->coef_fresh = false;
-    const ksfd_handle::SolverMemo &m = h->ckpt_memo;
-    h->lamJ = m.lamJ; h->lam_age = m.lam_age; h->lam_period = m.lam_period; h->mg_shift_floor = m.mg_shift_floor;
-    h->sf_dir = m.sf_dir; h->sf_hold = m.sf_hold; h->sf_tried_down = m.sf_tried_down; h->sf_prev_its = m.sf_prev_its; h->sf_prev_floor = m.sf_prev_floor;
-    h->nsteps = m.nsteps; h->spec.bad_until = m.spec_bad_until; h->spec.backoff = m.spec_backoff; h->spec.means_valid = false;
-    h->spec.rho_step = m.spec_rho_step; h->spec.rho_prev = m.spec_rho_prev;
+    h->memo = h->ckpt_memo;
+    h->spec.means_valid = false;
     h->mg_coef_valid = false; h->mg_shift = -1.0; h->poly_shift = -1.0; h->have_err = false;
     for (MGLevel &L : h->mg) L.pv_norm = 0.0;
     rec_reset(h);
@@ -617,7 +615,82 @@ extern "C" void ksfd_default_step_opts(ksfd_step_opts *o)
     o->pc_type = 2;    // 0 none, 1 multigrid always, 2 multigrid when the step is stiff (2-D, single rank)
 }
 
-// One TSStep_RosW attempt loop (PETSc rosw.c restated; tableau/derivation in oracle/ksfd_oracle.c).
+// One TSStep_RosW attempt loop (PETSc rosw.c restated; tableau/derivation in oracle/ksfd_oracle.c) over the parts in step.hip.h.
+// Grooms and saves the state, then tries step sizes until the controller accepts one: plan, four stages, the solvers' own adaptation,
+// completion with the embedded error norm, TSAdaptChoose_Basic.  Every rejection rolls the state back from usave.
+static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_opts *opts, bool direct, bool dr_on, ksfd_step_stats &st)
+{
+    int rc;
+    StepMemo &m = h->memo;
+    double hh = *hstep;
+    bool prev_accept = !(opts->reserved & 4);           // bit 2: the caller's previous attempt of this step was rejected
+    bool lam_done = false;
+    int rejects = 0;
+    const int max_rej = opts->max_reject < 0 ? 0x7fffffff : opts->max_reject;      // PETSc: -ts_max_reject -1 = unlimited
+    const bool single = (opts->reserved & 2) != 0;                                   // one attempt per call (the caller owns the reject loop)
+    // KSFDTS.solve grooms the global vector before every TS.step (KSFD/ksfdts.py:210)
+    {
+        // groom + roll-back copy of the owned points in one pass (ghost units of usave are never used: every roll-back is followed by a halo exchange)
+        Scope sc(h, KC_MISC, vbytes(h, 3));
+        hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin, h->usave);
+        if (hipGetLastError() != hipSuccess) return fail(h, KSFD_EHIP, "k_groom launch failed");
+    }
+    if ((rc = halo(h, h->u))) return rc;
+    if (h->use_frozen && (rc = ensure_coef(h, true))) return rc;      // usually already there: the CFL check after the last step made them
+    h->poly_shift = -1.0;
+    m.nsteps++;
+    if (m.spec_rho_step > 0.0) m.spec_rho_prev = m.spec_rho_step;      // contraction memory of the spectral sweeps: this step's maximum replaces the last one's
+    m.spec_rho_step = 0.0;
+    while (true) {
+        AttemptPlan p;
+        if ((rc = plan_attempt(h, opts, hh, direct, dr_on, lam_done, p))) return rc;
+        const int its_before = st.linear_its;
+        bool spec_failed = false;
+        rc = step_attempt(h, opts, p, spec_failed, st);
+        const int its = st.linear_its - its_before;
+        if (p.use_spec && opts->pc_type == 2) ksfd_ctl::spec_backoff_update(m, spec_failed, its, m.nsteps);
+        if (!rc && p.use_pc && h->sf_auto) ksfd_ctl::shift_floor_update(m, (double)its, p.shift);
+        if (rc == KSFD_ELINEAR && opts->adapt && !single && rejects < max_rej && hh * 0.25 >= opts->dt_min) {
+            // PETSc's -ts_adapt_scale_solve_failed (0.25): a failed solve rejects the step and quarters it.  The
+            // reference disables that by setMaxSNESFailures(1) (KSFD/ksfdts.py:135) because its LU cannot fail this
+            // way; an iterative solve can, and aborting a long run for it would not be a service.
+            rejects++;
+            st.rejections = rejects;
+            prev_accept = false;
+            if ((rc = op_copy(h, h->u, h->usave))) return rc;
+            hh *= 0.25;
+            *hstep = hh;
+            if ((rc = halo(h, h->u))) return rc;
+            continue;
+        }
+        if (rc) { op_copy(h, h->u, h->usave); hipStreamSynchronize(h->st); return rc; }
+        if ((rc = step_finish(h, opts, &st.wrms))) return rc;
+        if (!(st.wrms == st.wrms) || isinf(st.wrms)) {
+            op_copy(h, h->u, h->usave); hipStreamSynchronize(h->st);
+            h->coef_fresh = h->use_frozen;
+            return fail(h, KSFD_ENAN, "non-finite error norm at t=%g h=%g", *t, hh);
+        }
+        ksfd_ctl::AdaptChoice next = { true, hh };
+        if (opts->adapt) next = ksfd_ctl::adapt_basic(hh, st.wrms, prev_accept, opts->safety, opts->reject_safety, opts->clip_lo, opts->clip_hi, opts->dt_min, opts->dt_max);
+        prev_accept = next.accept;
+        if (next.accept) {
+            st.accepted = 1; st.h_used = hh;
+            *t += hh;
+            *hstep = next.hnext;
+            return KSFD_OK;
+        }
+        rejects++;
+        st.rejections = rejects;
+        if ((rc = op_copy(h, h->u, h->usave))) return rc;
+        h->coef_fresh = h->use_frozen;                           // the planes were made from exactly this state
+        hh = next.hnext;
+        *hstep = next.hnext;
+        if (single) return KSFD_OK;                              // single attempt: report the rejection
+        if (rejects > max_rej) return fail(h, KSFD_EREJECT, "step rejected %d times at t=%g", rejects, *t);
+        if ((rc = halo(h, h->u))) return rc;
+    }
+}
+
 extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_step_opts *opts, ksfd_step_stats *stats)
 {
     if (!h || !t || !hstep || !opts) return KSFD_EINVAL;
@@ -636,339 +709,12 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
         if (h->dr_keep > m_dr - 3) return fail(h, KSFD_EINVAL, "deflation: keep = %d needs a restart length of at least %d (ksp_restart %d, basis vectors allocated %d)", h->dr_keep, h->dr_keep + 3, (int)opts->ksp_restart, h->restart_alloc);
     }
     memset(&h->dr_stats, 0, sizeof h->dr_stats);
-    if (getenv("KSFD_PC_SIGMA")) { h->mg_shift_floor = atof(getenv("KSFD_PC_SIGMA")); h->sf_auto = false; }      // experiment knob: fixed floor
+    if (getenv("KSFD_PC_SIGMA")) { h->memo.mg_shift_floor = atof(getenv("KSFD_PC_SIGMA")); h->sf_auto = false; }      // experiment knob: fixed floor
     ksfd_step_stats st;
     memset(&st, 0, sizeof st);
-    const double bytes0 = h->bytes_acc;
-    const int64_t rhs0 = h->prof.launches[KC_RHS], jvp0 = h->prof.launches[KC_JVP];
-    int64_t launches0 = 0;
-    for (int c = 0; c < KSFD_NKCLASS; c++) launches0 += h->prof.launches[c];
-    const long long sync0 = h->n_host_sync, pred0 = h->n_predicted, resid0 = h->n_residual;
-    int rc = KSFD_OK;
-    const int64_t vs = h->vlen;
-    double hh = *hstep;
-    bool prev_accept = !(opts->reserved & 4);           // bit 2: the caller's previous attempt of this step was rejected
-    bool lam_done = false;
-    int rejects = 0;
-    const int max_rej = opts->max_reject < 0 ? 0x7fffffff : opts->max_reject;      // PETSc: -ts_max_reject -1 = unlimited
-    const bool single = (opts->reserved & 2) != 0;                                   // one attempt per call (the caller owns the reject loop)
-    // KSFDTS.solve grooms the global vector before every TS.step (KSFD/ksfdts.py:210)
-    {
-        // groom + roll-back copy of the owned points in one pass (ghost units of usave are never used: every roll-back is followed by a halo exchange)
-        Scope sc(h, KC_MISC, vbytes(h, 3));
-        hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin, h->usave);
-        if (hipGetLastError() != hipSuccess) { rc = fail(h, KSFD_EHIP, "k_groom launch failed"); goto out; }
-    }
-    if ((rc = halo(h, h->u))) goto out;
-    if (h->use_frozen && (rc = ensure_coef(h, true))) goto out;      // usually already there: the CFL check after the last step made them
-    h->poly_shift = -1.0;
-    h->nsteps++;
-    if (h->spec.rho_step > 0.0) h->spec.rho_prev = h->spec.rho_step;      // contraction memory of the spectral sweeps: this step's maximum replaces the last one's
-    h->spec.rho_step = 0.0;
-    while (true) {
-        const double shift = 1.0 / (GAMMA_RA * hh);
-        h->dr.valid = false;                             // every attempt has its own matrix: nothing is carried into it
-        // stiffness estimate X = h*gamma*lambda_max of the diffusion part; the multigrid preconditioner pays off above ~60
-        double dmax = h->P.s2, lap = 0.0;
-        for (int l = 0; l < h->P.nlig; l++) dmax = std::max(dmax, h->P.lig_D[l]);
-        for (int a = 0; a < h->G.dim; a++) lap += (16.0 / 3.0) * h->P.inv_h2[a];
-        const double stiff = dmax * lap / shift;
-        // (measured crossover against the degree-6 polynomial: X ~ 80 on 4096^2, ~ 280 on 1024^2 where the V cycle is latency-bound)
-        const double mg_from = h->mg_threshold * ((double)h->G.F * (double)h->G.nloc < 8.0e6 ? 3.0 : 1.0);
-        // spectral preconditioner (constant-coefficient part of shift*I - J inverted by FFT): nearly exact while the state is a
-        // smooth perturbation of a uniform one, at any stiffness; pc_type 2 uses it until it converges badly (see below), 4 always
-        bool use_spec = !direct && h->spec.ok && h->use_frozen && (opts->pc_type == 4 || (opts->pc_type == 2 && stiff >= (fused_ok(h) ? h->spec_from : std::max(h->spec_from, 0.3)) && h->nsteps > h->spec.bad_until && !h->spec.user_off));      // (without the fused 2-D residual kernel a sweep costs more: 3-D at X = 0.29, 80 ms plain GMRES against 83 ms)
-        if (use_spec) {
-            if (!h->Zb && alloc_d(h, &h->Zb, (int64_t)h->restart_alloc * h->vlen)) { rc = KSFD_ENOMEM; goto out; }
-            if (!h->spec.means_valid && (rc = spec_means(h))) goto out;
-        }
-        const bool use_pc = !direct && !use_spec && h->mg_ok && h->use_frozen && (opts->pc_type == 1 || (opts->pc_type == 2 && stiff > mg_from));
-        // pipelined solver: latency-bound iterations only (small local problem), not in the tiny-h regime where the
-        // Pythagorean norm update cancels heavily (|w|^2/h_n^2 ~ 1/stiff^2) and gmres() takes its explicit second pass
-        // polynomial preconditioner in the mildly stiff regime (pc_type 2 = automatic, 3 = polynomial whenever useful)
-        bool use_poly = false;
-        if (!use_spec && !use_pc && h->use_frozen && (opts->pc_type == 2 || opts->pc_type == 3) && stiff >= 0.3) {
-            if (!h->Zb && alloc_d(h, &h->Zb, (int64_t)h->restart_alloc * h->vlen)) { rc = KSFD_ENOMEM; goto out; }
-            if (!lam_done) {
-                if (h->lamJ < 0.0 || ++h->lam_age >= h->lam_period) {
-                    const double before = h->lamJ;
-                    if ((rc = est_lambda_max(h, shift, before < 0.0 ? 8 : 2))) goto out;    // warm-started after the first step
-                    // J changes slowly from step to step: while the estimate moves by < 2 %, look less often
-                    const bool stable = before > 0.0 && fabs(h->lamJ - before) <= 0.02 * before;
-                    h->lam_period = stable ? std::min(2 * h->lam_period, 8) : 1;
-                    h->lam_age = 0;
-                }
-                lam_done = true;
-            }
-            if (h->poly_shift != shift) poly_setup(h, shift);
-            use_poly = h->poly_deg >= 1 && h->poly_max_deg >= 1;
-        }
-        const bool small = (double)h->G.F * (double)h->G.nloc <= 6.0e6;
-        const bool use_async = !dr_on && !direct && !use_spec && !use_pc && !use_poly && h->use_frozen && !(opts->reserved & 1) && stiff >= 1e-3 &&
-                               (!h->ring || h->tr->device_allreduce()) &&
-                               (h->async_mode == 1 || (h->async_mode == 2 && small));
-        h->mg_use32 = opts->ksp_rtol >= 1e-7;          // fp32 level vectors inside the V cycle (mg_vcycle32); tight tolerances keep fp64
-        const bool fuse_stage = (fused_ok(h) || (strip3d_ok(h) && h->rhs3d_strip)) && h->P.nlig <= 4 && h->fuse_stage;
-        const int its_before = st.linear_its;
-        bool spec_failed = false;
-        // Initial guesses for the spectral stage solves from the earlier stages of the step (A Y_j = b_j is known): the right-hand
-        // sides of a step are nearly dependent -- b_1 = c b_0 to ~1e-3, later ones to a few per cent (CPU experiment with the oracle)
-        // -- so x0 = sum c_j Y_j, c = argmin ||b_i - sum c_j b_j||, starts the defect correction 1-3 digits ahead for one small
-        // multi-dot.  The b_j are kept in bstore (three vectors, allocated on first use); gb = their Gram matrix.
-        const bool guess_on = (use_spec || use_pc) && fuse_stage && h->spec_guess && h->bstore;
-        double gb[4][4];
-        // direct: the factors of shift*I - J(u_n) serve the four stages of this attempt (the coefficient planes are those of u_n here
-        // also with use_frozen off: ensure_coef)
-        if (direct && !(rc = ensure_coef(h, true))) rc = direct_factor(h, shift);
-        for (int i = 0; i < 4 && !rc; i++) {
-            const double *zin = h->u;
-            double bnorm2 = -1.0;                 // ||b||^2 when the RHS kernel's epilogue delivered it
-            bool rhs_dots_done = false;           // ... and <b_i, b_j> for the stage guess with it
-            double rhs_dot[2] = { 0.0, 0.0 };
-            double *bcur = (guess_on && i < 3) ? h->bstore + (int64_t)i * vs : h->bvec;
-            if (fuse_stage) {
-                // stage argument and Zdot term folded into the RHS kernel (no Z vector, no separate passes)
-                KComb cmb = KComb{};
-                for (int j = 0; j < i; j++) {
-                    if (h->At[i][j] != 0.0) { cmb.yin[cmb.nin] = h->Y + (int64_t)j * vs; cmb.ain[cmb.nin++] = h->At[i][j]; }
-                    if (h->Ginv[i][j] != 0.0) { cmb.yout[cmb.nout] = h->Y + (int64_t)j * vs; cmb.aout[cmb.nout++] = -h->Ginv[i][j] / hh; }
-                }
-                // ||b||^2 from the store epilogue (2-D strip kernel), and with it the inner products of b_i with the right-hand sides the stage
-                // guess is built from (the multi-dot below would read all of them again)
-                const int gdot_j0 = std::max(0, i - h->guess_max), gdot_n = (guess_on && i > 0 && h->rhs_dots) ? i - gdot_j0 : 0;
-                const bool rhs_norm = use_spec && fused_ok(h) && (!(guess_on && i > 0) || (gdot_n > 0 && gdot_n <= 2 && strip_waves(h) * (1 + gdot_n) <= part_capacity()));
-                rhs_dots_done = rhs_norm && gdot_n > 0;
-                // ghosts of the newest stage vector (earlier ones done): exchanged behind the interior rows of the RHS (op_rhs)
-                if ((rc = op_rhs(h, h->u, i, bcur, &cmb, rhs_norm, i > 0 ? h->Y + (int64_t)(i - 1) * vs : nullptr, rhs_dots_done ? gdot_n : 0,
-                                 rhs_dots_done ? h->bstore + (int64_t)gdot_j0 * vs : nullptr))) break;
-                if (rhs_norm) bnorm2 = h->hres[0];
-                if (rhs_dots_done) for (int j = 0; j < gdot_n; j++) rhs_dot[j] = h->hres[1 + j];
-            } else {
-            if (i > 0) {
-                const double *xs[5]; double a[5]; int nt = 0;
-                xs[nt] = h->u; a[nt++] = 1.0;
-                for (int j = 0; j < i; j++) if (h->At[i][j] != 0.0) { xs[nt] = h->Y + (int64_t)j * vs; a[nt++] = h->At[i][j]; }
-                if (nt > 1) {
-                    if ((rc = op_lincomb(h, nt, xs, a, h->Z))) break;
-                    if ((rc = halo(h, h->Z))) break;
-                    zin = h->Z;
-                }
-            }
-            if ((rc = op_rhs(h, zin, i, h->bvec))) break;
-            if (i > 0) {
-                const double *xs[5]; double a[5]; int nt = 0;
-                xs[nt] = h->bvec; a[nt++] = 1.0;
-                for (int j = 0; j < i; j++) if (h->Ginv[i][j] != 0.0) { xs[nt] = h->Y + (int64_t)j * vs; a[nt++] = -h->Ginv[i][j] / hh; }
-                if (nt > 1 && (rc = op_lincomb(h, nt, xs, a, h->bvec))) break;
-            }
-            }
-            LinStats ls;
-            SpecGuess sg;
-            sg.n = 0;
-            {
-                if (guess_on) {
-                    if (i == 0) {
-                        if (bnorm2 < 0.0) { if ((rc = op_multidot(h, bcur, bcur, 0))) break; bnorm2 = h->hres[0]; }
-                        gb[0][0] = bnorm2;
-                    }
-                    else {
-                        // <b_i, b_j> (j0 <= j < i) and <b_i, b_i> in one pass; least squares on the (ill-conditioned but tiny) Gram system.
-                        // j0 > 0 (h->guess_max): only the most recent stages enter -- every vector of the guess costs two more full-vector
-                        // reads in the first sweep (b_j in the forward row kernel, Y_j in the inverse one) and one in this multi-dot
-                        const int j0 = std::max(0, i - h->guess_max), ng = i - j0;
-                        if (rhs_dots_done) {
-                            for (int j = 0; j < ng; j++) gb[i][j0 + j] = gb[j0 + j][i] = rhs_dot[j];
-                            gb[i][i] = bnorm2;
-                        } else {
-                            if ((rc = op_multidot(h, bcur, h->bstore + (int64_t)j0 * vs, ng))) break;
-                            for (int j = 0; j < ng; j++) gb[i][j0 + j] = gb[j0 + j][i] = h->hres[j];
-                            gb[i][i] = bnorm2 = h->hres[ng];
-                        }
-                        double M[3][4];
-                        for (int a = 0; a < ng; a++) { for (int c = 0; c < ng; c++) M[a][c] = gb[j0 + a][j0 + c]; M[a][ng] = gb[i][j0 + a]; M[a][a] *= 1.0 + 1e-13; }
-                        bool okls = ng > 0;
-                        for (int c = 0; c < ng && okls; c++) {              // Gaussian elimination with partial pivoting
-                            int pv = c;
-                            for (int a = c + 1; a < ng; a++) if (fabs(M[a][c]) > fabs(M[pv][c])) pv = a;
-                            if (!(fabs(M[pv][c]) > 0.0)) { okls = false; break; }
-                            for (int q = 0; q <= ng; q++) std::swap(M[c][q], M[pv][q]);
-                            for (int a = c + 1; a < ng; a++) { const double f = M[a][c] / M[c][c]; for (int q = c; q <= ng; q++) M[a][q] -= f * M[c][q]; }
-                        }
-                        double cf[3] = { 0, 0, 0 };
-                        for (int a = ng - 1; a >= 0 && okls; a--) { double t = M[a][ng]; for (int q = a + 1; q < ng; q++) t -= M[a][q] * cf[q]; cf[a] = t / M[a][a]; }
-                        double pred = gb[i][i];                                // ||b_i - sum c_j b_j||^2 = b.b - 2 c.g + c.G c
-                        for (int a = 0; a < ng; a++) { pred -= 2.0 * cf[a] * gb[i][j0 + a]; for (int c = 0; c < ng; c++) pred += cf[a] * cf[c] * gb[j0 + a][j0 + c]; }
-                        if (okls && pred == pred && pred < 0.09 * gb[i][i]) {
-                            for (int j = 0; j < ng; j++) if (cf[j] != 0.0) { sg.Y[sg.n] = h->Y + (int64_t)(j0 + j) * vs; sg.b[sg.n] = h->bstore + (int64_t)(j0 + j) * vs; sg.c[sg.n++] = cf[j]; }
-                        }
-                    }
-                }
-            }
-            if (direct) {
-                rc = direct_stage(h, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls);
-                st.pc_used |= 16;
-            } else if (use_spec) {
-                // defect correction with M^-1 (no Krylov vectors), flexible GMRES for the rest if it contracts slowly; the attempt
-                // is capped so that a state it does not suit costs little, then the V cycle / plain GMRES takes over
-                // (automatic choice: once a stage of this step has failed, the remaining stages go straight to the fallback, and a
-                //  re-trial after a back-off period gets a short leash -- a state the preconditioner does not suit then costs one
-                //  cheap attempt instead of four expensive ones: 440 -> 176 ms for such a step at 4096^2 x 3 fields)
-                const bool skip = spec_failed && opts->pc_type == 2;
-                if (!skip) {
-                    rc = spec_solve(h, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, bnorm2, opts->pc_type == 2 ? (h->spec.backoff > 8 ? 8 : 40) : 0, sg.n ? &sg : nullptr);
-                    st.pc_used |= 8;
-                }
-                if (skip || (rc == KSFD_ELINEAR && opts->pc_type == 2)) {
-                    if (!skip) st.linear_its += ls.its;
-                    spec_failed = true;
-                    const bool mg_here = h->mg_ok && stiff > 0.3;
-                    rc = gmres(h, h->u, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, mg_here ? 1 : 0);
-                    st.pc_used |= mg_here ? 2 : 1;
-                }
-            } else if (use_pc && sg.n) {
-                // multigrid regime, same initial guess: x0 = sum c_j Y_j, TRUE residual r0 = b - A x0 (one Jacobian action), then the
-                // correction A d = r0 to the tolerance of the original system and x = x0 + d
-                double *xi = h->Y + (int64_t)i * vs;
-                const double *xs[3]; double a[3];
-                for (int j = 0; j < sg.n; j++) { xs[j] = sg.Y[j]; a[j] = sg.c[j]; }
-                if ((rc = op_lincomb(h, sg.n, xs, a, xi)) || (rc = halo(h, xi)) || (rc = op_jvp_frozen(h, xi, 2, shift, h->Z, bcur))) break;
-                const double tol = std::max(opts->ksp_rtol * sqrt(bnorm2), opts->ksp_atol);
-                rc = dr_on ? gmres_dr(h, h->u, shift, h->Z, h->t3, opts, &ls, 1, i, tol)
-                           : gmres(h, h->u, shift, h->Z, h->t3, opts, &ls, 1, i, tol);        // stage index: the Krylov spaces of the earlier stages are projected out first
-                if (!rc) { const double *x2[2] = { xi, h->t3 }; double a2[2] = { 1.0, 1.0 }; rc = op_lincomb(h, 2, x2, a2, xi); }
-                st.pc_used |= 2;
-            } else {
-            rc = use_async ? gmres_async(h, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls)
-                 : dr_on ? gmres_dr(h, h->u, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, use_pc ? 1 : (use_poly ? 2 : 0), i)
-                           : gmres(h, h->u, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, use_pc ? 1 : (use_poly ? 2 : 0), i);
-            st.pc_used |= use_pc ? 2 : (use_poly ? 4 : 1);
-            }
-            st.linear_its += ls.its;
-            st.ksp_resid = ls.rel;
-            {
-                static const bool stage_trace = getenv("KSFD_STAGE_TRACE") != nullptr;     // iterations per stage system (diagnostics)
-                if (stage_trace) fprintf(stderr, "[stage %d] its %d rel %.2e guess %d\n", i, ls.its, ls.rel, sg.n);
-            }
-            if (rc == KSFD_ELINEAR && !direct && !use_pc && h->mg_ok && h->use_frozen && opts->pc_type) {
-                // unpreconditioned GMRES ran out of iterations: the multigrid-preconditioned solve of the same system
-                // is the remedy (the stiffness estimate above only knows the diffusion part of J)
-                rc = gmres(h, h->u, shift, bcur, h->Y + (int64_t)i * vs, opts, &ls, 1);
-                st.pc_used |= 2;
-                st.linear_its += ls.its;
-                st.ksp_resid = ls.rel;
-            }
-        }
-        if (use_spec && opts->pc_type == 2) {
-            // adaptation: > 12 iterations per stage system (or a failed attempt) means the coefficients vary too much for the
-            // constant-coefficient inverse; leave it alone for a while (doubling) and let the polynomial / V cycle work
-            if (spec_failed || st.linear_its - its_before > 48) {
-                h->spec.bad_until = h->nsteps + h->spec.backoff;
-                h->spec.backoff = std::min(2 * h->spec.backoff, 512);
-            } else h->spec.backoff = 8;
-        }
-        if (!rc && use_pc && h->sf_auto) {
-            // Shift floor of the multigrid hierarchy (gmres(): shift_pc = max(shift, floor)).  Once 1/(gamma h) has fallen below the
-            // growth rate of the chemotactic instability the V cycle of shift*I - J stops contracting and the iteration count explodes
-            // (options81 run, h ~ 350: 480 iterations per step; with a floor of 0.2: 120).  The right floor is a property of J we do
-            // not know, so it is searched online: when a step needs > 64 iterations, double the floor while that pays (> 5 % fewer
-            // iterations), else go back and try halving, else settle for 25 steps.
-            const double its = (double)(st.linear_its - its_before);
-            if (h->sf_dir == 0) {
-                if (h->sf_hold > 0) h->sf_hold--;
-                else if (its > 64.0) {
-                    h->sf_prev_its = its; h->sf_prev_floor = h->mg_shift_floor;
-                    h->mg_shift_floor = 2.0 * std::max(h->mg_shift_floor, shift);
-                    h->sf_dir = 1; h->sf_tried_down = false;
-                }
-            } else if (its < 0.95 * h->sf_prev_its) {
-                h->sf_prev_its = its; h->sf_prev_floor = h->mg_shift_floor;
-                h->mg_shift_floor = h->sf_dir > 0 ? 2.0 * h->mg_shift_floor : 0.5 * h->mg_shift_floor;
-                if (h->mg_shift_floor <= shift) { h->sf_dir = 0; h->sf_hold = 25; }          // floor no longer active
-            } else {
-                h->mg_shift_floor = h->sf_prev_floor;
-                if (h->sf_dir > 0 && !h->sf_tried_down && 0.5 * h->sf_prev_floor > shift) {
-                    h->sf_dir = -1; h->sf_tried_down = true;
-                    h->mg_shift_floor = 0.5 * h->sf_prev_floor;
-                } else { h->sf_dir = 0; h->sf_hold = 25; }
-            }
-        }
-        if (rc == KSFD_ELINEAR && opts->adapt && !single && rejects < max_rej && hh * 0.25 >= opts->dt_min) {
-            // PETSc's -ts_adapt_scale_solve_failed (0.25): a failed solve rejects the step and quarters it.  The
-            // reference disables that by setMaxSNESFailures(1) (KSFD/ksfdts.py:135) because its LU cannot fail this
-            // way; an iterative solve can, and aborting a long run for it would not be a service.
-            rejects++;
-            st.rejections = rejects;
-            prev_accept = false;
-            if ((rc = op_copy(h, h->u, h->usave))) goto out;
-            hh *= 0.25;
-            *hstep = hh;
-            if ((rc = halo(h, h->u))) goto out;
-            continue;
-        }
-        if (rc) { op_copy(h, h->u, h->usave); hipStreamSynchronize(h->st); goto out; }
-        // completion + embedded error norm
-        {
-            Scope sc(h, KC_FINISH, vbytes(h, 7));
-            hipLaunchKernelGGL(k_rosw_finish, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->Y, vs,
-                               h->bt[0], h->bt[1], h->bt[2], h->bt[3], h->b2t[0] - h->bt[0], h->b2t[1] - h->bt[1],
-                               h->b2t[2] - h->bt[2], h->b2t[3] - h->bt[3], opts->atol, opts->rtol, h->errv, h->part);
-        }
-        h->have_err = true;
-        h->coef_fresh = false;                                   // u <- u_new (a rollback below makes the planes current again)
-        if ((rc = reduce_rows(h, 1, h->nblk_vec, 0))) goto out;
-        {
-            double ntot = (double)h->G.F * (double)h->cfg.n[0] * (double)h->cfg.n[1] * (double)h->cfg.n[2];
-            st.wrms = sqrt(h->hres[0] / ntot);
-        }
-        if (!(st.wrms == st.wrms) || isinf(st.wrms)) {
-            op_copy(h, h->u, h->usave); hipStreamSynchronize(h->st);
-            h->coef_fresh = h->use_frozen;
-            rc = fail(h, KSFD_ENAN, "non-finite error norm at t=%g h=%g", *t, hh);
-            goto out;
-        }
-        bool accept = true;
-        double hnext = hh;
-        if (opts->adapt) {
-            // TSAdaptChoose_Basic
-            double safety = opts->safety;
-            if (st.wrms > 1.0) {
-                if (!prev_accept) safety *= opts->reject_safety;
-                accept = hh < (1.0 + 1.4901161193847656e-08) * opts->dt_min;   // at minimum step: accept anyway
-            }
-            double hfac = st.wrms > 0.0 ? safety * pow(st.wrms, -1.0 / 3.0) : INFINITY;
-            hfac = std::min(std::max(hfac, opts->clip_lo), opts->clip_hi);
-            hnext = std::min(std::max(hh * hfac, opts->dt_min), opts->dt_max);
-        }
-        prev_accept = accept;
-        if (accept) {
-            st.accepted = 1; st.h_used = hh;
-            *t += hh;
-            *hstep = hnext;
-            break;
-        }
-        rejects++;
-        st.rejections = rejects;
-        if ((rc = op_copy(h, h->u, h->usave))) goto out;
-        h->coef_fresh = h->use_frozen;                           // the planes were made from exactly this state
-        hh = hnext;
-        *hstep = hnext;
-        if (single) break;                                       // single attempt: report the rejection
-        if (rejects > max_rej) { rc = fail(h, KSFD_EREJECT, "step rejected %d times at t=%g", rejects, *t); break; }
-        if ((rc = halo(h, h->u))) goto out;
-    }
-out:
-    prof_resolve(h);
-    st.bytes = h->bytes_acc - bytes0;
-    st.rhs_evals = (int32_t)(h->prof.launches[KC_RHS] - rhs0);
-    st.jvp_evals = (int32_t)(h->prof.launches[KC_JVP] - jvp0);
-    {
-        int64_t l1 = 0;
-        for (int c = 0; c < KSFD_NKCLASS; c++) l1 += h->prof.launches[c];
-        st.launches = (int32_t)(l1 - launches0);
-    }
-    st.host_syncs = (int32_t)(h->n_host_sync - sync0);
-    st.predicted_final = (int32_t)(h->n_predicted - pred0);
-    st.residual_evals = (int32_t)(h->n_residual - resid0);
+    const StepCounters c0 = stats_begin(h);
+    const int rc = step_run(h, t, hstep, opts, direct, dr_on, st);
+    stats_end(h, c0, st);
     if (stats) *stats = st;
     return rc;
 }
@@ -1085,7 +831,7 @@ extern "C" int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, i
     if (!h) return KSFD_EINVAL;
     if (from_stiffness > 0.0) h->spec_from = from_stiffness;
     if (enable == 0) h->spec.user_off = true;
-    else if (enable > 0) { h->spec.user_off = false; h->spec.bad_until = 0; h->spec.backoff = 8; }
+    else if (enable > 0) { h->spec.user_off = false; h->memo.spec_bad_until = 0; h->memo.spec_backoff = 8; }
     return KSFD_OK;
 }
 extern "C" int ksfd_synchronize(ksfd_handle *h)
