@@ -103,7 +103,11 @@ typedef struct ksfd_step_opts {
                                  * Chebyshev polynomial + flexible GMRES when mildly stiff, none when not; 3 polynomial only;
                                  * 4 spectral always; 5 direct: dense LU of shift*I - J on the device, factored once per step attempt, every
                                  * stage solve checked by its true residual against max(ksp_rtol*||b||, ksp_atol) with at most two refinement
-                                 * steps (single rank, at most KSFD_DIRECT_MAX unknowns, else KSFD_EINVAL before anything is touched) */
+                                 * steps (single rank, at most KSFD_DIRECT_MAX unknowns, else KSFD_EINVAL before anything is touched);
+                                 * 6 banded: the same for 1-D grids of any size at O(N F^3) cost -- the periodic ring is folded (0, N-1, 1, N-2, ...)
+                                 * so that shift*I - J is banded with kl = ku = 5F - 1, and factored with partial pivoting inside the band
+                                 * by one workgroup; a handful of launches per step attempt (single rank, 1-D, else KSFD_EINVAL before
+                                 * anything is touched) */
     int32_t reserved;           /* flags.  bit 0: classic two-pass CGS2 instead of CGS2 with the algebraic second projection;
                                  * bit 1: single attempt per call -- a rejected step returns with accepted = 0 and *hstep = the
                                  * controller's proposal (callers that must refresh stage-time data per attempt);
@@ -119,7 +123,8 @@ typedef struct ksfd_step_stats {
                                  * inverse (sweeps of the defect correction) where pc_used has bit 8 */
     int32_t rhs_evals, jvp_evals;
     int32_t pc_used;            /* preconditioners the stage solves of this call ran with, OR of: 1 none, 2 multigrid V cycle,
-                                 * 4 Chebyshev polynomial, 8 spectral (constant-coefficient FFT), 16 direct (dense LU, pc_type 5) */
+                                 * 4 Chebyshev polynomial, 8 spectral (constant-coefficient FFT), 16 direct (dense LU, pc_type 5), 32 banded direct
+                                 * (banded LU of the folded 1-D ring, pc_type 6) */
     double wrms;                /* error norm of the last attempt */
     double h_used;              /* step actually taken (valid when accepted) */
     double ksp_resid;           /* last relative residual */
@@ -284,6 +289,9 @@ int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enab
  * ksfd_spectral_apply; KSFD_EINVAL on a handle with a halo transport or more than KSFD_DIRECT_MAX unknowns, KSFD_ELINEAR on a zero or
  * non-finite pivot.  The state and what the stepper remembers are not changed. */
 int ksfd_direct_apply(ksfd_handle *h, double shift, const double *v, double *out, int32_t layout);
+/* Banded direct solver (pc_type 6), the twin of ksfd_direct_apply for 1-D handles: any finite shift, all three layouts.  KSFD_EINVAL
+ * on a handle that is not 1-D or has a halo transport, KSFD_ELINEAR on a zero or non-finite pivot. */
+int ksfd_banded_apply(ksfd_handle *h, double shift, const double *v, double *out, int32_t layout);
 
 
 /* -- GMRES with deflated restarting (GMRES-DR; Morgan, SIAM J. Sci. Comput. 24, 2002) as the Krylov solver of the stage systems.
@@ -318,9 +326,12 @@ int32_t ksfd_basis_capacity(const ksfd_handle *h);
 int ksfd_basis_rotate(ksfd_handle *h, int32_t nin, int32_t nout, const double *P_host, const double *vin_host, double *vout_host,
                       int32_t layout);
 /* ksfd_bench_kernel classes beyond the profile's kernel classes: the rotation kernel on 31 -> 11 vectors in one pass, and the same
- * rotation composed from 11 basis combinations of 31 vectors (out of place) */
+ * rotation composed from 11 basis combinations of 31 vectors (out of place); one factorization of the banded direct solver (assembly
+ * and the read-back of info included, at the shift of the last ksfd_banded_apply or pc_type 6 attempt) and one of its solves */
 #define KSFD_BENCH_ROTATE 100
 #define KSFD_BENCH_ROTATE_COMPOSED 101
+#define KSFD_BENCH_BAND_FACTOR 102
+#define KSFD_BENCH_BAND_SOLVE 103
 
 #ifdef __cplusplus
 }

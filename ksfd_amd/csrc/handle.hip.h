@@ -71,6 +71,21 @@ struct LUState {
     double shift = 0.0;
 };
 
+// banded direct solver for 1-D grids, pc_type 6 (banded_plan.h / banded.hip.h / banded_host.hip.h): allocated on first use, factors
+// rebuilt every step attempt; the pivot indices never leave the device
+struct BandState {
+    BandPlan B = {};
+    int64_t nnz = 0;
+    double *AB = nullptr;                    // band storage of the factors (LAPACK gbtrf layout, ldab = 2 kl + ku + 1)
+    int *piv = nullptr, *info = nullptr;
+    long long *col = nullptr;                // Jacobian entries staged by k_jac_csr
+    double *val = nullptr;
+    double *z = nullptr;                     // L^-1 P b between the two sweeps of a solve
+    int threads = 0;                         // workgroup of k_band_factor (64 or 256)
+    bool valid = false;
+    double shift = 0.0;
+};
+
 struct ksfd_handle {
     ksfd_config cfg;
     int32_t lig_group[KSFD_MAXL];
@@ -195,6 +210,7 @@ struct ksfd_handle {
     ksfd_deflation_stats dr_stats = {};
 
     LUState lu;
+    BandState band;
 
     // multigrid preconditioner
     std::vector<MGLevel> mg;

@@ -18,6 +18,7 @@
 #include "mg.hip.h"
 #include "spectral.hip.h"
 #include "lu.hip.h"
+#include "banded.hip.h"
 #include "transport.h"
 #include "step_control.h"
 
@@ -28,6 +29,7 @@
 #include "krylov.hip.h"
 #include "krylov_dr.hip.h"
 #include "lu_host.hip.h"
+#include "banded_host.hip.h"
 #include "step.hip.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -63,6 +65,7 @@ extern "C" void ksfd_destroy(ksfd_handle *h)
     mg_free(h);
     spec_free(h);
     direct_free(h);
+    banded_free(h);
     delete h->tr;
     if (h->ev_ready) hipEventDestroy(h->ev_ready);
     if (h->ev_halo) hipEventDestroy(h->ev_halo);
@@ -697,9 +700,10 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
     hipSetDevice(h->device);
     // pc_type 5: dense LU of shift*I - J, factored once per attempt (lu_host.hip.h); no spectral / polynomial / multigrid / pipelined
     // solver, no stage guesses.  Its limits are checked before the state or the step-to-step memory is touched.
-    const bool direct = opts->pc_type == 5;
+    // pc_type 6: the same with the banded LU of the folded 1-D ring (banded_host.hip.h) in its place.
+    const bool direct = opts->pc_type == 5 || opts->pc_type == 6;
     if (direct) {
-        const int g = direct_guard(h);
+        const int g = opts->pc_type == 6 ? banded_guard(h) : direct_guard(h);
         if (g) return g;
     }
     // deflated restarting (krylov_dr.hip.h): the restart length is the caller's, fixed, and must leave room behind the kept vectors
@@ -786,6 +790,18 @@ extern "C" int ksfd_direct_apply(ksfd_handle *h, double shift, const double *vh,
     if ((rc = direct_guard(h))) return rc;
     if ((rc = ensure_coef(h)) || (rc = direct_factor(h, shift))) return rc;
     if ((rc = upload(h, vh, layout, h->t2)) || (rc = direct_solve(h, h->t2, h->t3))) return rc;
+    return download(h, h->t3, layout, outh);
+}
+extern "C" int ksfd_banded_apply(ksfd_handle *h, double shift, const double *vh, double *outh, int32_t layout)
+{
+    if (!h || !vh || !outh) return KSFD_EINVAL;
+    if (!isfinite(shift)) return fail(h, KSFD_EINVAL, "banded_apply: non-finite shift");
+    if (layout < 0 || layout > 2) return fail(h, KSFD_EINVAL, "bad layout %d", layout);
+    hipSetDevice(h->device);
+    int rc;
+    if ((rc = banded_guard(h))) return rc;
+    if ((rc = ensure_coef(h)) || (rc = banded_factor(h, shift))) return rc;
+    if ((rc = upload(h, vh, layout, h->t2)) || (rc = banded_solve(h, h->t2, h->t3))) return rc;
     return download(h, h->t3, layout, outh);
 }
 extern "C" int ksfd_set_deflation(ksfd_handle *h, int32_t keep, int32_t carry_stages)
@@ -904,6 +920,8 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
             for (int i = 0; i < 31; i++) coef[i] = 1.0 / 31.0;
             for (int j = 0; j < 11 && !r; j++) r = op_basis_axpy(h, h->Zb + (int64_t)j * h->vlen, h->V, 31, coef, 0.0);
         } break;
+        case KSFD_BENCH_BAND_FACTOR: r = banded_factor(h, h->band.shift); break;
+        case KSFD_BENCH_BAND_SOLVE: r = banded_solve(h, h->Y, h->t3); break;
         default: r = fail(h, KSFD_EINVAL, "bench_kernel: class %d not benchable", cls);
         }
         by = h->bytes_acc - b0;
@@ -911,6 +929,11 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
     };
     if ((cls == KSFD_BENCH_ROTATE || cls == KSFD_BENCH_ROTATE_COMPOSED) && (h->restart_alloc < 30 || !h->Zb)) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the rotation benchmark needs 31 basis vectors and the flexible basis"); goto done; }
     if (cls == KSFD_BENCH_ROTATE || cls == KSFD_BENCH_ROTATE_COMPOSED) { h->dr.valid = false; rec_reset(h); }
+    if (cls == KSFD_BENCH_BAND_FACTOR || cls == KSFD_BENCH_BAND_SOLVE) {
+        if ((rc = banded_guard(h))) goto done;
+        if (!h->band.valid) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the banded benchmark needs a factorization (ksfd_banded_apply first)"); goto done; }
+        if ((rc = ensure_coef(h, true))) goto done;
+    }
     if ((rc = halo(h, h->u))) goto done;
     if (h->use_frozen && (cls == KC_JVP || cls == KC_SPECTRAL) && (rc = ensure_coef(h, true))) goto done;
     if (cls == KC_SPECTRAL && (rc = spec_means(h))) goto done;

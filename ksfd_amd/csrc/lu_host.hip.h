@@ -159,7 +159,9 @@ static int direct_solve(ksfd_handle *h, const double *b, double *x)
 // One stage system (shift*I - J) x = b of ksfd_step: solve, then the true residual b - A x from the frozen-coefficient Jacobian action
 // against max(ksp_rtol*||b||, ksp_atol) -- the test of every other solver -- with at most two refinement steps x += A^-1 r.
 // ls->its counts the solves (refinements included), ls->rel is the last true relative residual.
-static int direct_stage(ksfd_handle *h, double shift, const double *b, double *x, const ksfd_step_opts *opts, LinStats *ls)
+// solve: the factored solver the stage runs on (direct_solve, banded_solve); what: its name in the error message.
+static int exact_stage(ksfd_handle *h, double shift, const double *b, double *x, const ksfd_step_opts *opts, LinStats *ls,
+                       int (*solve)(ksfd_handle *, const double *, double *), const char *what)
 {
     int rc;
     ls->its = 0;
@@ -167,7 +169,7 @@ static int direct_stage(ksfd_handle *h, double shift, const double *b, double *x
     if ((rc = op_multidot(h, b, b, 0))) return rc;
     const double bn = sqrt(h->hres[0]);
     const double tol = std::max(opts->ksp_rtol * bn, opts->ksp_atol);
-    if ((rc = direct_solve(h, b, x))) return rc;
+    if ((rc = solve(h, b, x))) return rc;
     ls->its = 1;
     for (int ref = 0;; ref++) {
         if ((rc = halo(h, x)) || (rc = op_jvp_frozen(h, x, 2, shift, h->t3, b)) || (rc = op_multidot(h, h->t3, h->t3, 0))) return rc;
@@ -175,11 +177,16 @@ static int direct_stage(ksfd_handle *h, double shift, const double *b, double *x
         const double rn = sqrt(h->hres[0]);
         ls->rel = bn > 0.0 ? rn / bn : rn;
         if (rn <= tol) return KSFD_OK;
-        if (ref == 2) return fail(h, KSFD_ELINEAR, "direct solve: true residual %.3e above %.3e after two refinement steps", rn, tol);
-        if ((rc = direct_solve(h, h->t3, h->t2))) return rc;
+        if (ref == 2) return fail(h, KSFD_ELINEAR, "%s solve: true residual %.3e above %.3e after two refinement steps", what, rn, tol);
+        if ((rc = solve(h, h->t3, h->t2))) return rc;
         const double *xs[2] = { x, h->t2 };
         const double a[2] = { 1.0, 1.0 };
         if ((rc = op_lincomb(h, 2, xs, a, x))) return rc;
         ls->its++;
     }
+}
+
+static int direct_stage(ksfd_handle *h, double shift, const double *b, double *x, const ksfd_step_opts *opts, LinStats *ls)
+{
+    return exact_stage(h, shift, b, x, opts, ls, direct_solve, "direct");
 }

@@ -3,7 +3,7 @@
 //   plan_attempt          regime of this attempt (choose_regime) and what it needs on the device before the stages start
 //   stage_rhs             right-hand side b_i of stage i, fused (KComb inside the RHS kernel, norm and dots from its epilogue) or unfused
 //   stage_gram_guess      Gram matrix of the right-hand sides of the attempt -> coefficients of the stage guess (stage_guess)
-//   stage_solve           direct / spectral with its fallbacks / V cycle from a guess / the GMRES variants, and the multigrid retry
+//   stage_solve           direct (dense or banded) / spectral with its fallbacks / V cycle from a guess / the GMRES variants, and the multigrid retry
 //   step_attempt          the four stages
 //   step_finish           completion u <- u + sum bt_i Y_i with the embedded error vector, and its WRMS norm
 //   stats_begin / _end    the ksfd_step_stats counters
@@ -15,7 +15,8 @@ using ksfd_ctl::StepMemo;
 // what plan_attempt decides for one attempt
 struct AttemptPlan {
     double hh, shift, stiff;
-    bool direct, dr_on;                       // pc_type 5 / deflated restarting (decided once per step)
+    bool direct, dr_on;                       // pc_type 5 or 6 / deflated restarting (decided once per step)
+    bool banded;                              // ... the direct solver is the banded one (pc_type 6)
     bool use_spec, use_pc, use_poly, use_async;
     bool fuse_stage;                          // stage argument and Zdot term folded into the RHS kernel
     bool guess_on;                            // stage guesses from the earlier stages of the attempt
@@ -59,6 +60,7 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
     int rc;
     StepMemo &m = h->memo;
     p.hh = hh; p.direct = direct; p.dr_on = dr_on;
+    p.banded = direct && opts->pc_type == 6;
     p.shift = 1.0 / (GAMMA_RA * hh);
     h->dr.valid = false;                             // every attempt has its own matrix: nothing is carried into it
     p.stiff = ksfd_ctl::stiffness(h->P.s2, h->P.lig_D, h->P.nlig, h->P.inv_h2, h->G.dim, p.shift);
@@ -188,8 +190,8 @@ static int stage_solve(ksfd_handle *h, const ksfd_step_opts *opts, const Attempt
     double *xi = h->Y + (int64_t)i * h->vlen;
     LinStats ls;
     if (p.direct) {
-        rc = direct_stage(h, shift, r.b, xi, opts, &ls);
-        st.pc_used |= 16;
+        rc = p.banded ? banded_stage(h, shift, r.b, xi, opts, &ls) : direct_stage(h, shift, r.b, xi, opts, &ls);
+        st.pc_used |= p.banded ? 32 : 16;
     } else if (p.use_spec) {
         // defect correction with M^-1 (no Krylov vectors), flexible GMRES for the rest if it contracts slowly; the attempt
         // is capped so that a state it does not suit costs little, then the V cycle / plain GMRES takes over
@@ -250,7 +252,7 @@ static int step_attempt(ksfd_handle *h, const ksfd_step_opts *opts, const Attemp
     double gb[4][4];
     // direct: the factors of shift*I - J(u_n) serve the four stages of this attempt (the coefficient planes are those of u_n here
     // also with use_frozen off: ensure_coef)
-    if (p.direct && !(rc = ensure_coef(h, true))) rc = direct_factor(h, p.shift);
+    if (p.direct && !(rc = ensure_coef(h, true))) rc = p.banded ? banded_factor(h, p.shift) : direct_factor(h, p.shift);
     for (int i = 0; i < 4 && !rc; i++) {
         StageRhs r;
         SpecGuess sg;

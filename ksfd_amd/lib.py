@@ -20,7 +20,7 @@ OK, EINVAL, EHIP, ENOMEM, ELINEAR, ENAN, EREJECT, ECOMM = range(8)
 # kernel classes of ksfd_profile / ksfd_bench_kernel
 KC_RHS, KC_JVP, KC_MULTIDOT, KC_GSUPDATE, KC_LINCOMB, KC_BASISAXPY, KC_FINISH, KC_REDUCE, \
     KC_GFIELD, KC_VELOCITY, KC_MISC, KC_HALO, KC_MG, KC_SPECTRAL = range(14)
-PC_NONE, PC_MULTIGRID, PC_POLYNOMIAL, PC_SPECTRAL, PC_DIRECT = 1, 2, 4, 8, 16      # bits of StepStats.pc_used
+PC_NONE, PC_MULTIGRID, PC_POLYNOMIAL, PC_SPECTRAL, PC_DIRECT, PC_BANDED = 1, 2, 4, 8, 16, 32      # bits of StepStats.pc_used
 DIRECT_MAX = 32768      # KSFD_DIRECT_MAX: largest F * local points of the direct solver (pc_type 5)
 
 
@@ -72,6 +72,7 @@ class DeflationStats(C.Structure):
 
 ROT_MAXIN, ROT_MAXOUT = 121, 18     # KSFD_ROT_MAXIN / KSFD_ROT_MAXOUT: limits of the basis rotation kernel
 BENCH_ROTATE, BENCH_ROTATE_COMPOSED = 100, 101      # ksfd_bench_kernel: one-pass rotation 31 -> 11 vectors / 11 basis combinations
+BENCH_BAND_FACTOR, BENCH_BAND_SOLVE = 102, 103      # ... one factorization (assembly included) / one solve of the banded direct solver
 
 _lib = None
 
@@ -83,7 +84,7 @@ ABI_SYMBOLS = [
     'ksfd_velocity', 'ksfd_velocity_max', 'ksfd_groom', 'ksfd_count_worms', 'ksfd_scale_rho', 'ksfd_mul_rho', 'ksfd_jacobian_nnz', 'ksfd_jacobian_csr', 'ksfd_set_state_random', 'ksfd_snapshot_begin', 'ksfd_snapshot_wait', 'ksfd_checkpoint',
     'ksfd_default_step_opts', 'ksfd_step', 'ksfd_get_last_error_vector', 'ksfd_set_profiling',
     'ksfd_get_profile', 'ksfd_synchronize', 'ksfd_bench_kernel', 'ksfd_set_tuning', 'ksfd_set_mg_params', 'ksfd_set_poly_params',
-    'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply',
+    'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply', 'ksfd_banded_apply',
     'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity',
 ]
 
@@ -148,6 +149,7 @@ def load():
     L.ksfd_spectral_apply.argtypes = [vp, C.c_double, dp, dp, C.c_int32]
     L.ksfd_set_spectral_params.argtypes = [vp, C.c_double, C.c_int32]
     L.ksfd_direct_apply.argtypes = [vp, C.c_double, dp, dp, C.c_int32]
+    L.ksfd_banded_apply.argtypes = [vp, C.c_double, dp, dp, C.c_int32]
     L.ksfd_set_deflation.argtypes = [vp, C.c_int32, C.c_int32]
     L.ksfd_get_deflation_stats.argtypes = [vp, C.POINTER(DeflationStats)]
     L.ksfd_basis_capacity.argtypes = [vp]
@@ -389,6 +391,14 @@ class KSFDHip:
         out = np.empty(self.nlocal)
         v = self._vec(v)
         self._chk(self.L.ksfd_direct_apply(self.h, float(shift), _dp(v), _dp(out), layout))
+        return out
+
+    def banded_apply(self, shift, v, layout=SOA):
+        """z = (shift*I - J)^-1 v by the banded LU of the folded ring (pc_type 6, 1-D handles), J = the Jacobian at the resident state
+        (test entry)"""
+        out = np.empty(self.nlocal)
+        v = self._vec(v)
+        self._chk(self.L.ksfd_banded_apply(self.h, float(shift), _dp(v), _dp(out), layout))
         return out
 
     def set_deflation(self, keep, carry_stages=False):

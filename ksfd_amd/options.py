@@ -305,7 +305,7 @@ def decode_sources(sargs, params):
 
 
 # -ksfd_pc_type spelling -> ksfd_step_opts.pc_type (include/ksfd_hip.h)
-KSFD_PC_TYPES = {'auto': 2, 'none': 0, 'mg': 1, 'poly': 3, 'spectral': 4, 'lu': 5}
+KSFD_PC_TYPES = {'auto': 2, 'none': 0, 'mg': 1, 'poly': 3, 'spectral': 4, 'lu': 5, 'banded': 6}
 
 
 def step_opts_from(params, petsc_args):
