@@ -1,7 +1,9 @@
 // libksfd_hip.so -- Chebyshev polynomial preconditioner, flexible/recycled GMRES(m), pipelined GMRES
 // (part of the single translation unit ksfd_hip.hip; included from there in this order:
-//  handle.hip.h, ops.hip.h, spectral_host.hip.h, mg_host.hip.h, krylov.hip.h, lu_host.hip.h)
+//  handle.hip.h, ops.hip.h, spectral_host.hip.h, mg_host.hip.h, krylov.hip.h, krylov_dr.hip.h, lu_host.hip.h, banded_host.hip.h,
+//  step.hip.h)
 #pragma once
+#include "krylov_small.h"
 // ------------------------------------------------------------------------------------------------
 // Polynomial preconditioner.  In the non-stiff regime (h*gamma*lambda_max(J) of order 1..10, the regime of the
 // headline benchmark) plain GMRES needs ~7 iterations per stage and spends most of its time in Gram-Schmidt, whose
@@ -106,6 +108,7 @@ static int poly_apply(ksfd_handle *h, double shift, double *v, double *z)
 // matrix-free GMRES(m) for (shift I - J(u)) x = b, x0 = 0  -- replaces -ksp_type preonly -pc_type lu
 // (options84:58-60).  Classical Gram-Schmidt applied twice (CGS2), one fused multi-dot + one fused
 // update kernel per pass; the new vector's norm comes from the second pass by Pythagoras.
+// The small host algebra (Hessenberg QR, algebraic second projection, recycling rules) is in krylov_small.h.
 // ------------------------------------------------------------------------------------------------
 struct LinStats { int its; double rel; };
 
@@ -115,35 +118,112 @@ static void rec_reset(ksfd_handle *h)
     h->rec_vtop = h->rec_ztop = 0;
 }
 
-// Least squares min ||g - H y|| for a small upper-Hessenberg H ((k+1) x k, column-major, ld = k+1); also returns H y.
-static void hess_lsq(const double *H, int k, const double *g, double *y, double *Hy)
+// A right-hand side of norm bn with nothing to iterate on: zero (x = 0 is the solution) or not finite (nan_msg: the solver's own error
+// text).  *empty: the solver returns what this returns.
+static int rhs_empty(ksfd_handle *h, double bn, double *x, const char *nan_msg, bool *empty)
 {
-    const int ld = k + 1;
-    std::vector<double> R((size_t)ld * k), q((size_t)k + 1);
-    for (int i = 0; i < ld * k; i++) R[i] = H[i];
-    for (int i = 0; i <= k; i++) q[i] = g[i];
-    for (int j = 0; j < k; j++) {
-        const double a = R[j * ld + j], b = R[j * ld + j + 1], den = hypot(a, b);
-        const double c = den > 0.0 ? a / den : 1.0, sn = den > 0.0 ? b / den : 0.0;
-        for (int l = j; l < k; l++) {
-            const double t = c * R[l * ld + j] + sn * R[l * ld + j + 1];
-            R[l * ld + j + 1] = -sn * R[l * ld + j] + c * R[l * ld + j + 1];
-            R[l * ld + j] = t;
-        }
-        const double t = c * q[j] + sn * q[j + 1];
-        q[j + 1] = -sn * q[j] + c * q[j + 1];
-        q[j] = t;
+    *empty = !(bn > 0.0);
+    if (!*empty) return KSFD_OK;
+    if (bn != bn) return fail(h, KSFD_ENAN, "%s", nan_msg);
+    HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)h->vlen, h->st));
+    return KSFD_OK;
+}
+
+// w = A M^-1 v_j.  z != NULL: where M^-1 v_j lands (pcmode 1 one multigrid V cycle for shift_pc, 2 Chebyshev polynomial p(A), 3 spectral);
+// NULL: no preconditioner.
+static int apply_AMinv(ksfd_handle *h, const double *ustate, double shift, double shift_pc, int pcmode, double *vj, double *z, double *w)
+{
+    int rc;
+    if (z) {
+        if ((rc = pcmode == 1 ? mg_precond(h, shift_pc, vj, z) : pcmode == 3 ? spec_apply(h, shift, vj, z) : poly_apply(h, shift, vj, z))) return rc;
+        return op_jvp_frozen_halo(h, z, 1, shift, w);
     }
-    for (int i = k - 1; i >= 0; i--) {
-        double t = q[i];
-        for (int l = i + 1; l < k; l++) t -= R[l * ld + i] * y[l];
-        y[i] = R[i * ld + i] != 0.0 ? t / R[i * ld + i] : 0.0;
+    if (h->use_frozen) return op_jvp_frozen_halo(h, vj, 1, shift, w);
+    return (rc = halo(h, vj)) ? rc : op_jvp(h, ustate, vj, 1, shift, w);
+}
+
+// Second Gram-Schmidt pass of w (already projected once with hcol) against V_0..k-1: measure what is left, add it to hcol, project it
+// out and normalise; *hn = the norm, from the pass's own <w,w> by Pythagoras.
+static int cgs2_second_pass(ksfd_handle *h, double *w, const double *V, int k, double *hcol, double *d, double *hn)
+{
+    int rc;
+    if ((rc = op_multidot(h, w, V, k))) return rc;
+    double s2 = 0.0;
+    for (int i = 0; i < k; i++) { d[i] = h->hres[i]; hcol[i] += d[i]; s2 += d[i] * d[i]; }
+    double hn2 = h->hres[k] - s2;          // ||w''||^2 by Pythagoras; d is O(eps) so this is accurate
+    if (hn2 < 0.0) hn2 = 0.0;
+    *hn = sqrt(hn2);
+    return op_gs_update(h, w, V, k, d, *hn > 0.0 ? 1.0 / *hn : 0.0);
+}
+
+// classic CGS2: two Gram-Schmidt passes, each = one fused multi-dot + one fused update.
+// (One pass alone loses orthogonality like eps*(||r0||/||r_j||)^2 and stalls near 1e-8.)
+// The caller has run the first multi-dot, op_multidot(h, w, V, k), and looked at <w,w>: its result is taken from h->hres.
+static int cgs2_classic(ksfd_handle *h, double *w, const double *V, int k, double *hcol, double *d, double *hn)
+{
+    int rc;
+    for (int i = 0; i < k; i++) hcol[i] = h->hres[i];
+    if ((rc = op_gs_update(h, w, V, k, hcol, 1.0))) return rc;
+    return cgs2_second_pass(h, w, V, k, hcol, d, hn);
+}
+
+// CGS2 of w = A M^-1 v_j against V_0..j with the second projection done algebraically (ksfd_krylov::cgs2_algebraic): one pass over V
+// for the dots and the Gram row of v_j (kept in Gm, leading dimension ldg), one fused update.
+static int cgs2_gram(ksfd_handle *h, double *w, const double *V, int j, double *Gm, int ldg, double *hcol, double *d, double *hn)
+{
+    int rc;
+    const int k = j + 1;
+    if ((rc = op_multidot_gram(h, w, V, k))) return rc;
+    for (int i = 0; i < k; i++) { d[i] = h->hres[i]; Gm[(size_t)i * ldg + j] = Gm[(size_t)j * ldg + i] = h->hres[k + i]; }
+    const double ww = h->hres[2 * k];
+    if (!(ww == ww)) return fail(h, KSFD_ENAN, "GMRES: Krylov vector is not finite");
+    double hn2;
+    if (ksfd_krylov::cgs2_algebraic(Gm, ldg, k, d, ww, hcol, &hn2)) {
+        *hn = sqrt(hn2);
+        return op_gs_update(h, w, V, k, hcol, 1.0 / *hn);
     }
-    for (int i = 0; i <= k; i++) {
-        double t = 0.0;
-        for (int l = 0; l < k; l++) t += H[l * ld + i] * y[l];
-        Hy[i] = t;
+    // heavy cancellation (||w|| >> ||w - Vc||): apply c, then measure and project once more
+    if ((rc = op_gs_update(h, w, V, k, hcol, 1.0))) return rc;
+    return cgs2_second_pass(h, w, V, k, hcol, d, hn);
+}
+
+// what the parts of one gmres() call share
+struct GmresRun {
+    int pcmode, stage;
+    bool use_pc, use_poly;      // multigrid, right preconditioning: w = A (M^-1 v_j), x = M^-1 (V y) / flexible GMRES (z_j = M^-1 v_j kept in Zb): 2 Chebyshev polynomial p(A), 3 spectral (spectral_host.hip.h)
+    bool rec_on, rec_full;      // ksfd_krylov::recycle_decide
+    double shift_pc;
+    int vb, zb;                 // first slot of this solve's own vectors in V / Zb (behind the kept ones)
+    double *V, *Zq;             // ... and the vectors themselves
+    std::vector<int> spaces;    // earlier stages whose kept space this solve projects on
+    std::vector<double> g_first;    // <b, V_i> over the first of them and <b,b>
+    double bn, beta;            // ||b||, norm of the residual of the current x
+    const double *rsrc;         // that residual, while it is at hand (first cycle)
+    bool x_set = false;         // x holds an iterate (else it is taken as 0 and overwritten)
+    // x0 from the recycled spaces is not written on its own: its coefficients wait (indexed by absolute slot of Zb / V) and
+    // ride in the solution update of the first cycle -- one pass over x instead of two
+    bool x0_pending = false;
+    std::vector<double> xcoef;
+};
+
+// ||b||: with a recycled space to project on, the projection's multi-dot of b returns <b,b> as well -- one pass, one
+// reduction and one host round trip less per stage
+static int rhs_norm(ksfd_handle *h, GmresRun &R, const double *b)
+{
+    int rc;
+    if (R.rec_on && R.stage > 0)
+        for (int q = 0; q < R.stage; q++)
+            if (ksfd_krylov::recycle_uses(R.stage, q, h->rec_mode, R.rec_full) && h->rec[q].valid && h->rec[q].pc == R.pcmode) R.spaces.push_back(q);
+    if (R.spaces.empty()) {
+        if ((rc = op_multidot(h, b, R.V, 0))) return rc;
+        R.bn = sqrt(h->hres[0]);
+        return KSFD_OK;
     }
+    const ksfd_handle::RecSpace &S = h->rec[R.spaces.front()];
+    if ((rc = op_multidot(h, b, h->V + (int64_t)S.vb * h->vlen, S.k + 1))) return rc;
+    R.g_first.assign(h->hres, h->hres + S.k + 2);
+    R.bn = sqrt(R.g_first[S.k + 1]);
+    return KSFD_OK;
 }
 
 // stage >= 0: Krylov recycling.  The four stage systems of a step share the matrix, and their right-hand sides are
@@ -153,282 +233,193 @@ static void hess_lsq(const double *H, int k, const double *g, double *y, double 
 // other, costs ~5 vector passes per kept vector and removes 1-2 of the 3-4 outer iterations of stages 2-4 (each
 // (d+1) Jacobian actions + Gram-Schmidt).  The iteration then continues on the true residual with the same stopping
 // test, so the result is the same to the solver tolerance.  stage < 0: plain solve from x0 = 0.
+static int recycle_project(ksfd_handle *h, GmresRun &R, const double *b, double *x)
+{
+    if (R.spaces.empty()) return KSFD_OK;
+    int rc;
+    const int64_t vs = h->vlen;
+    const bool defer_x0 = !R.use_pc;
+    bool pc_x0_pending = false;
+    double *const rbuf = (x == h->t3) ? R.V : h->t3;         // projected residual (a correction solve has its x in t3: this solve's slot 0 then, scaled in place below)
+    const int first_space = R.spaces.front(), last_space = R.spaces.back();       // the last one's residual update also returns the norm of the result
+    bool have_norm = false;
+    for (int q : R.spaces) {
+        const ksfd_handle::RecSpace &S = h->rec[q];
+        const double *Vs = h->V + (int64_t)S.vb * vs;
+        const double *Zs = R.use_poly ? h->Zb + (int64_t)S.zb * vs : Vs;
+        std::vector<double> gq_((size_t)S.k + 2), yq_((size_t)S.k + 1), Hy_((size_t)S.k + 2), neg_((size_t)S.k + 2);
+        double *gq = gq_.data(), *yq = yq_.data(), *Hy = Hy_.data(), *neg = neg_.data();
+        if (q == first_space && R.rsrc == b) {
+            for (int i = 0; i <= S.k; i++) gq[i] = R.g_first[i];                 // already computed together with ||b||
+        } else {
+            if ((rc = op_multidot(h, R.rsrc, Vs, S.k + 1))) return rc;
+            for (int i = 0; i <= S.k; i++) gq[i] = h->hres[i];
+        }
+        ksfd_krylov::hess_lsq(S.H.data(), S.k, gq, yq, Hy);
+        if (R.use_pc) {
+            // x0 = M^-1 (sum over the spaces of V_s y_s): the combinations gather in t2, one V cycle behind the loop
+            if ((rc = op_basis_axpy(h, h->t2, Vs, S.k, yq, pc_x0_pending ? 1.0 : 0.0))) return rc;
+            pc_x0_pending = true;
+        } else if (defer_x0) {
+            for (int i = 0; i < S.k; i++) R.xcoef[(R.use_poly ? S.zb : S.vb) + i] += yq[i];
+            R.x0_pending = true;
+        } else {
+            if ((rc = op_basis_axpy(h, x, Zs, S.k, yq, R.x_set ? 1.0 : 0.0))) return rc;
+            R.x_set = true;
+        }
+        for (int i = 0; i <= S.k; i++) neg[i] = -Hy[i];
+        if (R.rsrc == b && S.k + 2 <= 6) {
+            const double *xs[6] = { b }; double a[6] = { 1.0 };
+            for (int i = 0; i <= S.k; i++) { xs[i + 1] = Vs + (int64_t)i * vs; a[i + 1] = neg[i]; }
+            if ((rc = op_lincomb(h, S.k + 2, xs, a, rbuf, q == last_space))) return rc;
+            R.rsrc = rbuf;
+            have_norm = q == last_space;
+        } else {
+            if (R.rsrc == b) { if ((rc = op_copy(h, rbuf, b))) return rc; R.rsrc = rbuf; }
+            const bool nrm = q == last_space;
+            if ((rc = op_basis_axpy(h, rbuf, Vs, S.k + 1, neg, 1.0, nrm))) return rc;
+            have_norm = nrm;
+        }
+    }
+    if (pc_x0_pending) {
+        if ((rc = mg_precond(h, R.shift_pc, h->t2, h->t1)) || (rc = op_copy(h, x, h->t1))) return rc;
+        R.x_set = true;
+    }
+    if (R.x_set || R.x0_pending) {
+        if (!have_norm && (rc = op_multidot(h, R.rsrc, R.rsrc, 0))) return rc;
+        R.beta = sqrt(h->hres[0]);
+        if (!(R.beta == R.beta)) return fail(h, KSFD_ENAN, "GMRES: projected residual is not finite");
+    }
+    return KSFD_OK;
+}
+
+// x += (M^-1) V_j y at the end of a cycle; coefficients of a pending x0 ride along (j = 0: those alone)
+static int update_x(ksfd_handle *h, GmresRun &R, double *x, int j, const double *y)
+{
+    int rc;
+    if (R.use_pc) {
+        if ((rc = op_basis_axpy(h, h->t2, R.V, j, y, 0.0)) || (rc = mg_precond(h, R.shift_pc, h->t2, h->t1))) return rc;
+        if (!R.x_set) { if ((rc = op_copy(h, x, h->t1))) return rc; }
+        else { const double *xs[2] = { x, h->t1 }; double a2[2] = { 1.0, 1.0 }; if ((rc = op_lincomb(h, 2, xs, a2, x))) return rc; }
+    } else if (R.x0_pending) {
+        const int xslot0 = R.use_poly ? R.zb : R.vb;            // first slot of this solve's own vectors in the basis the solution is expanded in
+        for (int i = 0; i < j; i++) R.xcoef[xslot0 + i] = y[i];
+        if ((rc = op_basis_axpy(h, x, R.use_poly ? h->Zb : h->V, xslot0 + j, R.xcoef.data(), R.x_set ? 1.0 : 0.0))) return rc;
+        R.x0_pending = false;
+    } else if ((rc = op_basis_axpy(h, x, R.use_poly ? R.Zq : R.V, j, y, R.x_set ? 1.0 : 0.0))) return rc;
+    R.x_set = true;
+    return KSFD_OK;
+}
+
+// keep the leading vectors of this stage's Arnoldi relation (j columns, raw Hessenberg Hraw with leading dimension ld) where they are;
+// the next stage builds behind them
+static void recycle_keep(ksfd_handle *h, const GmresRun &R, int j, const double *Hraw, int ld)
+{
+    ksfd_handle::RecSpace &S = h->rec[R.stage];
+    S.k = R.rec_full ? j : std::min(j, std::min(h->rec_keep, 4));
+    S.vb = R.vb; S.zb = R.zb; S.pc = R.pcmode;
+    S.H.assign((size_t)(S.k + 1) * S.k, 0.0);
+    for (int c = 0; c < S.k; c++)
+        for (int i = 0; i <= S.k; i++) S.H[c * (S.k + 1) + i] = Hraw[(size_t)ld * c + i];
+    S.valid = true;
+    h->rec_vtop = R.vb + S.k + 1;
+    h->rec_ztop = R.zb + (R.use_poly ? S.k : 0);
+}
+
+// resolve, project on the kept spaces (recycle_project), then per cycle { start vector, per column { w = A M^-1 v_j, orthogonalise,
+// push the column }, solve, update x, keep }, restart growth, verdict
 static int gmres(ksfd_handle *h, const double *ustate, double shift, const double *b, double *x,
                  const ksfd_step_opts *o, LinStats *ls, int pcmode, int stage = -1, double tol_abs = -1.0)
 {
     // tol_abs > 0: stop at that absolute residual norm (the caller solves a correction equation A d = b - A x0 and wants the
     // tolerance of the original system)
-    const bool use_pc = pcmode == 1;       // multigrid, right preconditioning
+    GmresRun R;
+    R.pcmode = pcmode; R.stage = stage;
+    R.use_pc = pcmode == 1;
     h->dr.valid = false;                   // this solve builds in V: a relation kept by the deflated solver (krylov_dr.hip.h) is gone
     // the hierarchy may be built for a LARGER shift than the system's (h->memo.mg_shift_floor): when 1/(gamma h) falls below the growth
     // rate of the chemotactic instability, shift*I - J is indefinite and a V cycle of it is no contraction; the V cycle of the
     // positively shifted operator still is, and GMRES (true residual of the real system) takes care of the difference
-    const double shift_pc = std::max(shift, h->memo.mg_shift_floor);
-    const bool use_poly = pcmode == 2 || pcmode == 3;     // flexible GMRES (z_j = M^-1 v_j kept in Zb): 2 Chebyshev polynomial p(A), 3 spectral (spectral_host.hip.h)
-    // use_pc: right preconditioning with one multigrid V cycle, w = A (M^-1 v_j), x = M^-1 (V y)
-    auto apply_A = [&](const double *vin, double *wout) -> int {
-        return h->use_frozen ? op_jvp_frozen(h, vin, 1, shift, wout) : op_jvp(h, ustate, vin, 1, shift, wout);
-    };
+    R.shift_pc = std::max(shift, h->memo.mg_shift_floor);
+    R.use_poly = pcmode == 2 || pcmode == 3;
     const int m_opt = std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc);
     const int maxit = o->ksp_max_it > 0 ? o->ksp_max_it : 2000;
     const int64_t vs = h->vlen;
-    // With the multigrid preconditioner the LEADING vectors of an earlier stage buy nothing (measured on the 600-step 384^2 run:
-    // 20.4 s with, 18.9 s without).  Round 3 tried the other end (rec_full, KSFD_TUNE bit 20, off by default): keep the WHOLE first
-    // cycle of every stage -- the slow modes of shift*I - J that take the iterations late in a run sit in the tail of the Krylov
-    // space -- and project a later stage's right-hand side on A M^-1 V_k = V_k+1 H_k first (one multi-dot, one basis combination,
-    // ONE V cycle for all spaces together).  Measured: it does NOT pay -- aggregated state at 4096^2 x 3 (h = 4.4) 25 instead of 26
-    // iterations per step but 142 instead of 125 ms; indefinite tail of the 384^2 run (h = 400, tools/late_phase.py) 142 instead of
-    // 135 iterations per step.  What a later stage still has to resolve is not in the span of what an earlier one built.
-    const bool rec_full = use_pc && h->rec_mg && stage >= 0 && stage < 4 && h->use_frozen && h->rec_mode > 0;
-    bool rec_on = stage >= 0 && stage < 4 && h->rec_mode > 0 && h->use_frozen && (!use_pc || rec_full);
-    if (!rec_on || stage == 0 || h->restart_alloc - h->rec_vtop < (rec_full ? 16 : 6)) { if (stage != 0) rec_on = false; rec_reset(h); }
-    const int vb = rec_on ? h->rec_vtop : 0, zb = rec_on ? h->rec_ztop : 0;
+    const ksfd_krylov::RecycleChoice rcy = ksfd_krylov::recycle_decide(pcmode, stage, h->rec_mode, h->rec_mg, h->use_frozen, h->restart_alloc, h->rec_vtop);
+    if (rcy.reset) rec_reset(h);
+    R.rec_on = rcy.rec_on; R.rec_full = rcy.rec_full;
+    R.vb = R.rec_on ? h->rec_vtop : 0; R.zb = R.rec_on ? h->rec_ztop : 0;
     // Restart length.  The first cycle runs with ksp_restart (30: PETSc's default); a cycle that ends without convergence is followed by
     // one of twice the length, up to what ksfd_create could allocate (restart_alloc, <= 120).  Restarted GMRES loses most on exactly the
     // systems where it needs many iterations -- shift*I - J indefinite late in a run, 30-50 iterations per stage system -- and a longer
     // basis costs little next to the V cycle and Jacobian actions of an iteration there.  Host arrays are sized for the longest cycle.
-    const int m = h->restart_alloc - vb;
-    int m_cur = (rec_full && rec_on) ? m : std::min(m_opt, m);          // rec_full: no restart inside the space that is going to be kept
-    double *V = h->V + (int64_t)vb * vs;
-    double *Zq = use_poly ? h->Zb + (int64_t)zb * vs : nullptr;
+    const int m = h->restart_alloc - R.vb;
+    int m_cur = (R.rec_full && R.rec_on) ? m : std::min(m_opt, m);          // rec_full: no restart inside the space that is going to be kept
+    double *const V = R.V = h->V + (int64_t)R.vb * vs;
+    R.Zq = R.use_poly ? h->Zb + (int64_t)R.zb * vs : nullptr;
+    R.xcoef.assign((size_t)std::max(h->restart_alloc + 2, KSFD_MAXDOT), 0.0);
     int rc;
-    std::vector<double> H((size_t)(m + 1) * m, 0.0), Hraw((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m), hcol(m + 2), d(m + 2), Gm((size_t)(m + 1) * (m + 1), 0.0);
-    // ||b||: with a recycled space to project on, the projection's multi-dot of b returns <b,b> as well -- one pass, one
-    // reduction and one host round trip less per stage
-    static const int sel[4][3] = { { -1, -1, -1 }, { 0, -1, -1 }, { 0, -1, -1 }, { 0, 2, -1 } };
-    int first_space = -1;
-    std::vector<double> g_first((size_t)h->restart_alloc + 3, 0.0);
-    if (rec_on && stage > 0)
-        for (int q = 0; q < stage && first_space < 0; q++) {
-            bool use = h->rec_mode == 2 || rec_full;
-            for (int e = 0; e < 3; e++) use = use || sel[stage][e] == q;
-            if (use && h->rec[q].valid && h->rec[q].pc == pcmode) first_space = q;
-        }
-    if (first_space >= 0) {
-        const ksfd_handle::RecSpace &S = h->rec[first_space];
-        if ((rc = op_multidot(h, b, h->V + (int64_t)S.vb * vs, S.k + 1))) return rc;
-        for (int i = 0; i <= S.k + 1; i++) g_first[i] = h->hres[i];
-    } else if ((rc = op_multidot(h, b, V, 0))) return rc;
-    const double bn = sqrt(first_space >= 0 ? g_first[h->rec[first_space].k + 1] : h->hres[0]);
+    ksfd_krylov::HessQR qr(m);
+    std::vector<double> hcol(m + 2), d(m + 2), Gm((size_t)(m + 1) * (m + 1), 0.0);
+    if ((rc = rhs_norm(h, R, b))) return rc;
+    const double bn = R.bn;
     ls->its = 0; ls->rel = 0.0;
-    if (!(bn > 0.0)) {
-        if (bn != bn) return fail(h, KSFD_ENAN, "GMRES: right-hand side is not finite");
-        HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
-        return KSFD_OK;
-    }
+    bool empty;
+    if ((rc = rhs_empty(h, bn, x, "GMRES: right-hand side is not finite", &empty)) || empty) return rc;
     const double tol = tol_abs > 0.0 ? tol_abs : std::max(o->ksp_rtol * bn, o->ksp_atol);
-    double beta = bn, rn = bn;
+    R.beta = bn; R.rsrc = b;
+    if ((rc = recycle_project(h, R, b, x))) return rc;
+    double rn = R.beta;
     int total = 0;
     bool first = true;          // the residual of the current x is at hand (rsrc, norm beta): no A x needed
-    bool x_set = false;         // x holds an iterate (else it is taken as 0 and overwritten)
     bool restarted = false;
-    const double *rsrc = b;
-    // x0 from the recycled spaces is not written on its own: its coefficients wait (indexed by absolute slot of Zb / V) and
-    // ride in the solution update of the first cycle -- one pass over x instead of two
-    const bool defer_x0 = rec_on && !use_pc;
-    std::vector<double> xcoef((size_t)std::max(h->restart_alloc + 2, KSFD_MAXDOT), 0.0);
-    bool x0_pending = false;
-    double *const Xbase = use_poly ? h->Zb : h->V;          // slot 0 of the basis the solution is expanded in
-    const int xslot0 = use_poly ? zb : vb;                  // first slot of this solve's own vectors
-    bool pc_x0_pending = false;
-    double *const rbuf = (x == h->t3) ? V : h->t3;           // projected residual (a correction solve has its x in t3: this solve's slot 0 then, scaled in place below)
-    if (rec_on && stage > 0) {
-        int last_space = -1;                                  // its residual update also returns the norm of the result
-        for (int q = 0; q < stage; q++) {
-            bool use = h->rec_mode == 2 || rec_full;
-            for (int e = 0; e < 3; e++) use = use || sel[stage][e] == q;
-            if (use && h->rec[q].valid && h->rec[q].pc == pcmode) last_space = q;
-        }
-        bool have_norm = false;
-        for (int q = 0; q < stage; q++) {
-            bool use = h->rec_mode == 2 || rec_full;
-            for (int e = 0; e < 3; e++) use = use || sel[stage][e] == q;
-            const ksfd_handle::RecSpace &S = h->rec[q];
-            if (!use || !S.valid || S.pc != pcmode) continue;
-            const double *Vs = h->V + (int64_t)S.vb * vs;
-            const double *Zs = use_poly ? h->Zb + (int64_t)S.zb * vs : Vs;
-            std::vector<double> gq_((size_t)S.k + 2), yq_((size_t)S.k + 1), Hy_((size_t)S.k + 2), neg_((size_t)S.k + 2);
-            double *gq = gq_.data(), *yq = yq_.data(), *Hy = Hy_.data(), *neg = neg_.data();
-            if (q == first_space && rsrc == b) {
-                for (int i = 0; i <= S.k; i++) gq[i] = g_first[i];                 // already computed together with ||b||
-            } else {
-                if ((rc = op_multidot(h, rsrc, Vs, S.k + 1))) return rc;
-                for (int i = 0; i <= S.k; i++) gq[i] = h->hres[i];
-            }
-            hess_lsq(S.H.data(), S.k, gq, yq, Hy);
-            if (use_pc) {
-                // x0 = M^-1 (sum over the spaces of V_s y_s): the combinations gather in t2, one V cycle behind the loop
-                if ((rc = op_basis_axpy(h, h->t2, Vs, S.k, yq, pc_x0_pending ? 1.0 : 0.0))) return rc;
-                pc_x0_pending = true;
-            } else if (defer_x0) {
-                for (int i = 0; i < S.k; i++) xcoef[(use_poly ? S.zb : S.vb) + i] += yq[i];
-                x0_pending = true;
-            } else {
-                if ((rc = op_basis_axpy(h, x, Zs, S.k, yq, x_set ? 1.0 : 0.0))) return rc;
-                x_set = true;
-            }
-            for (int i = 0; i <= S.k; i++) neg[i] = -Hy[i];
-            if (rsrc == b && S.k + 2 <= 6) {
-                const double *xs[6] = { b }; double a[6] = { 1.0 };
-                for (int i = 0; i <= S.k; i++) { xs[i + 1] = Vs + (int64_t)i * vs; a[i + 1] = neg[i]; }
-                if ((rc = op_lincomb(h, S.k + 2, xs, a, rbuf, q == last_space))) return rc;
-                rsrc = rbuf;
-                have_norm = q == last_space;
-            } else {
-                if (rsrc == b) { if ((rc = op_copy(h, rbuf, b))) return rc; rsrc = rbuf; }
-                const bool nrm = q == last_space;
-                if ((rc = op_basis_axpy(h, rbuf, Vs, S.k + 1, neg, 1.0, nrm))) return rc;
-                have_norm = nrm;
-            }
-        }
-        if (pc_x0_pending) {
-            if ((rc = mg_precond(h, shift_pc, h->t2, h->t1)) || (rc = op_copy(h, x, h->t1))) return rc;
-            x_set = true;
-        }
-        if (x_set || x0_pending) {
-            if (!have_norm && (rc = op_multidot(h, rsrc, rsrc, 0))) return rc;
-            beta = rn = sqrt(h->hres[0]);
-            if (!(beta == beta)) return fail(h, KSFD_ENAN, "GMRES: projected residual is not finite");
-        }
-    }
     while (true) {
-        if (first && beta <= tol) {                            // the recycled spaces already hold the solution
-            if (x0_pending) {
-                if ((rc = op_basis_axpy(h, x, Xbase, xslot0, xcoef.data(), x_set ? 1.0 : 0.0))) return rc;
-                x0_pending = false; x_set = true;
-            }
+        if (first && R.beta <= tol) {                          // the recycled spaces already hold the solution
+            if (R.x0_pending && (rc = update_x(h, R, x, 0, nullptr))) return rc;
             break;
         }
         // V0 = r / beta
-        if (first) { const double *xs[1] = { rsrc }; double a[1] = { 1.0 / beta }; if ((rc = op_lincomb(h, 1, xs, a, V))) return rc; }
+        if (first) { const double *xs[1] = { R.rsrc }; double a[1] = { 1.0 / R.beta }; if ((rc = op_lincomb(h, 1, xs, a, V))) return rc; }
         else {
-            if ((rc = halo(h, x)) || (rc = apply_A(x, V))) return rc;     // V0 = A x
+            if ((rc = halo(h, x)) || (rc = h->use_frozen ? op_jvp_frozen(h, x, 1, shift, V) : op_jvp(h, ustate, x, 1, shift, V))) return rc;     // V0 = A x
             const double *xs[2] = { b, V }; double a[2] = { 1.0, -1.0 };
             if ((rc = op_lincomb(h, 2, xs, a, V))) return rc;                                  // r = b - A x
             if ((rc = op_multidot(h, V, V, 0))) return rc;
-            beta = sqrt(h->hres[0]);
-            rn = beta;
-            if (!(beta == beta)) return fail(h, KSFD_ENAN, "GMRES: residual is not finite");
-            if (beta <= tol) break;
-            const double *x1[1] = { V }; double a1[1] = { 1.0 / beta };
+            R.beta = rn = sqrt(h->hres[0]);
+            if (!(rn == rn)) return fail(h, KSFD_ENAN, "GMRES: residual is not finite");
+            if (rn <= tol) break;
+            const double *x1[1] = { V }; double a1[1] = { 1.0 / rn };
             if ((rc = op_lincomb(h, 1, x1, a1, V))) return rc;
         }
-        std::fill(g.begin(), g.end(), 0.0);
-        g[0] = beta;
+        qr.reset(R.beta);
         int j = 0;
         bool done = false;
         for (; j < m_cur && total < maxit; j++) {
             double *vj = V + (int64_t)j * vs, *w = V + (int64_t)(j + 1) * vs;
-            if (use_pc) {
-                if ((rc = mg_precond(h, shift_pc, vj, h->t1)) || (rc = op_jvp_frozen_halo(h, h->t1, 1, shift, w))) return rc;
-            } else if (use_poly) {
-                double *zj = Zq + (int64_t)j * vs;
-                if ((rc = pcmode == 3 ? spec_apply(h, shift, vj, zj) : poly_apply(h, shift, vj, zj)) || (rc = op_jvp_frozen_halo(h, zj, 1, shift, w))) return rc;
-            } else if (h->use_frozen) {
-                if ((rc = op_jvp_frozen_halo(h, vj, 1, shift, w))) return rc;
-            } else if ((rc = halo(h, vj)) || (rc = apply_A(vj, w))) return rc;
+            double *z = R.use_pc ? h->t1 : R.use_poly ? R.Zq + (int64_t)j * vs : nullptr;
+            if ((rc = apply_AMinv(h, ustate, shift, R.shift_pc, pcmode, vj, z, w))) return rc;
             const int k = j + 1;
+            double hn;
             if ((o->reserved & 1) || k > 30) {       // (the fused multi-dot + Gram-row kernel returns 2k + 1 numbers, sized for the 30 vectors of the default restart: longer cycles finish classically)
-                // classic CGS2: two Gram-Schmidt passes, each = one fused multi-dot + one fused update.
-                // (One pass alone loses orthogonality like eps*(||r0||/||r_j||)^2 and stalls near 1e-8.)
                 if ((rc = op_multidot(h, w, V, k))) return rc;
-                for (int i = 0; i < k; i++) hcol[i] = h->hres[i];
                 if (!(h->hres[k] == h->hres[k])) return fail(h, KSFD_ENAN, "GMRES: Krylov vector is not finite");
-                if ((rc = op_gs_update(h, w, V, k, hcol.data(), 1.0))) return rc;
-                if ((rc = op_multidot(h, w, V, k))) return rc;
-                double s2 = 0.0;
-                for (int i = 0; i < k; i++) { d[i] = h->hres[i]; hcol[i] += d[i]; s2 += d[i] * d[i]; }
-                double hn2 = h->hres[k] - s2;          // ||w''||^2 by Pythagoras; d is O(eps) so this is accurate
-                if (hn2 < 0.0) hn2 = 0.0;
-                const double hn = sqrt(hn2);
-                if ((rc = op_gs_update(h, w, V, k, d.data(), hn > 0.0 ? 1.0 / hn : 0.0))) return rc;
-                hcol[k] = hn;
-            } else {
-                // CGS2 with the second projection done algebraically (halves the Gram-Schmidt traffic):
-                //   d = V^T w and the Gram row g = V^T v_j come from ONE pass over V; with G = V^T V,
-                //   the twice-projected coefficients are c = d + (I - G) d, and
-                //   ||w - V c||^2 = ww - 2 c.d + c.G c.   One fused update pass applies c and normalises.
-                if ((rc = op_multidot_gram(h, w, V, k))) return rc;
-                for (int i = 0; i < k; i++) { d[i] = h->hres[i]; Gm[(size_t)i * (m + 1) + j] = Gm[(size_t)j * (m + 1) + i] = h->hres[k + i]; }
-                const double ww = h->hres[2 * k];
-                if (!(ww == ww)) return fail(h, KSFD_ENAN, "GMRES: Krylov vector is not finite");
-                for (int i = 0; i < k; i++) {
-                    double s = 0.0;
-                    for (int l = 0; l < k; l++) s += ((i == l ? 1.0 : 0.0) - Gm[(size_t)i * (m + 1) + l]) * d[l];
-                    hcol[i] = d[i] + s;
-                }
-                double cd = 0.0, cGc = 0.0;
-                for (int i = 0; i < k; i++) {
-                    cd += hcol[i] * d[i];
-                    double s = 0.0;
-                    for (int l = 0; l < k; l++) s += Gm[(size_t)i * (m + 1) + l] * hcol[l];
-                    cGc += hcol[i] * s;
-                }
-                double hn2 = ww - 2.0 * cd + cGc;
-                double hn;
-                if (hn2 > 1e-8 * ww) {
-                    hn = sqrt(hn2);
-                    if ((rc = op_gs_update(h, w, V, k, hcol.data(), 1.0 / hn))) return rc;
-                } else {
-                    // heavy cancellation (||w|| >> ||w - Vc||): apply c, then measure and project once more
-                    if ((rc = op_gs_update(h, w, V, k, hcol.data(), 1.0))) return rc;
-                    if ((rc = op_multidot(h, w, V, k))) return rc;
-                    double s2 = 0.0;
-                    for (int i = 0; i < k; i++) { d[i] = h->hres[i]; hcol[i] += d[i]; s2 += d[i] * d[i]; }
-                    hn2 = h->hres[k] - s2;
-                    if (hn2 < 0.0) hn2 = 0.0;
-                    hn = sqrt(hn2);
-                    if ((rc = op_gs_update(h, w, V, k, d.data(), hn > 0.0 ? 1.0 / hn : 0.0))) return rc;
-                }
-                hcol[k] = hn;
-            }
-            double *Hc = &H[(size_t)(m + 1) * j];
-            for (int i = 0; i <= k; i++) Hraw[(size_t)(m + 1) * j + i] = Hc[i] = hcol[i];
-            for (int i = 0; i < j; i++) { double t = cs[i] * Hc[i] + sn[i] * Hc[i + 1]; Hc[i + 1] = -sn[i] * Hc[i] + cs[i] * Hc[i + 1]; Hc[i] = t; }
-            const double den = hypot(Hc[j], Hc[j + 1]);
-            cs[j] = den > 0.0 ? Hc[j] / den : 1.0;
-            sn[j] = den > 0.0 ? Hc[j + 1] / den : 0.0;
-            Hc[j] = den; Hc[j + 1] = 0.0;
-            g[j + 1] = -sn[j] * g[j];
-            g[j] = cs[j] * g[j];
+                if ((rc = cgs2_classic(h, w, V, k, hcol.data(), d.data(), &hn))) return rc;
+            } else if ((rc = cgs2_gram(h, w, V, j, Gm.data(), m + 1, hcol.data(), d.data(), &hn))) return rc;
+            hcol[k] = hn;
+            rn = qr.push_column(j, hcol.data());
             total++;
-            rn = fabs(g[j + 1]);
             if (rn <= tol || hcol[k] == 0.0) { j++; done = true; break; }
         }
-        for (int i = j - 1; i >= 0; i--) {
-            double s = g[i];
-            for (int q = i + 1; q < j; q++) s -= H[(size_t)(m + 1) * q + i] * y[q];
-            y[i] = s / H[(size_t)(m + 1) * i + i];
-        }
-        if (use_pc) {
-            if ((rc = op_basis_axpy(h, h->t2, V, j, y.data(), 0.0)) || (rc = mg_precond(h, shift_pc, h->t2, h->t1))) return rc;
-            if (!x_set) { if ((rc = op_copy(h, x, h->t1))) return rc; }
-            else { const double *xs[2] = { x, h->t1 }; double a2[2] = { 1.0, 1.0 }; if ((rc = op_lincomb(h, 2, xs, a2, x))) return rc; }
-        } else if (x0_pending) {
-            for (int i = 0; i < j; i++) xcoef[xslot0 + i] = y[i];
-            if ((rc = op_basis_axpy(h, x, Xbase, xslot0 + j, xcoef.data(), x_set ? 1.0 : 0.0))) return rc;
-            x0_pending = false;
-        } else if ((rc = op_basis_axpy(h, x, use_poly ? Zq : V, j, y.data(), x_set ? 1.0 : 0.0))) return rc;
-        x_set = true;
-        if (rec_on && first && !restarted && done && j >= 1) {
-            // keep the leading vectors of this stage's Arnoldi relation where they are; the next stage builds behind them
-            ksfd_handle::RecSpace &S = h->rec[stage];
-            S.k = rec_full ? j : std::min(j, std::min(h->rec_keep, 4));
-            S.vb = vb; S.zb = zb; S.pc = pcmode;
-            S.H.assign((size_t)(S.k + 1) * S.k, 0.0);
-            for (int c = 0; c < S.k; c++)
-                for (int i = 0; i <= S.k; i++) S.H[c * (S.k + 1) + i] = Hraw[(size_t)(m + 1) * c + i];
-            S.valid = true;
-            h->rec_vtop = vb + S.k + 1;
-            h->rec_ztop = zb + (use_poly ? S.k : 0);
-        }
+        qr.solve(j);
+        if ((rc = update_x(h, R, x, j, qr.y.data()))) return rc;
+        if (R.rec_on && first && !restarted && done && j >= 1) recycle_keep(h, R, j, qr.Hraw.data(), qr.ld);
         if (!first) restarted = true;
         first = false;
         if (done || total >= maxit) break;
         restarted = true;
         if (h->restart_grow) m_cur = std::min(2 * m_cur, m);
     }
-    if (!x_set) HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
+    if (!R.x_set) HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
     ls->its = total;
     ls->rel = rn / ((tol_abs > 0.0 && o->ksp_rtol > 0.0) ? tol_abs / o->ksp_rtol : bn);      // correction equation: relative to the original right-hand side
     if (rn > tol) return fail(h, KSFD_ELINEAR, "GMRES did not converge: %d iterations, relative residual %.3e (tol %.3e)", total, rn / bn, tol / bn);
@@ -453,7 +444,6 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
                       const SpecGuess *guess = nullptr)
 {
     int rc;
-    const int64_t vs = h->vlen;
     ls->its = 0; ls->rel = 0.0;
     rec_reset(h);
     if (bnorm2 < 0.0) {
@@ -461,11 +451,8 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
         bnorm2 = h->hres[0];
     }
     const double bn = sqrt(bnorm2);
-    if (!(bn > 0.0)) {
-        if (bn != bn) return fail(h, KSFD_ENAN, "spectral solve: right-hand side is not finite");
-        HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
-        return KSFD_OK;
-    }
+    bool empty;
+    if ((rc = rhs_empty(h, bn, x, "spectral solve: right-hand side is not finite", &empty)) || empty) return rc;
     const double tol = std::max(o->ksp_rtol * bn, o->ksp_atol);
     const int maxit = std::min(o->ksp_max_it > 0 ? o->ksp_max_it : 2000, 24);
     double *r = h->Z;                              // residual (the fused-stage path leaves Z unused)
@@ -569,11 +556,8 @@ static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x,
     if ((rc = op_multidot(h, b, V, 0))) return rc;
     const double bn = sqrt(h->hres[0]);
     ls->its = 0; ls->rel = 0.0;
-    if (!(bn > 0.0)) {
-        if (bn != bn) return fail(h, KSFD_ENAN, "GMRES: right-hand side is not finite");
-        HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
-        return KSFD_OK;
-    }
+    bool empty;
+    if ((rc = rhs_empty(h, bn, x, "GMRES: right-hand side is not finite", &empty)) || empty) return rc;
     const double tol = std::max(o->ksp_rtol * bn, o->ksp_atol);
     double beta = bn, rn = bn;
     int total = 0;
@@ -613,10 +597,7 @@ static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x,
             const int nb = vec2(h) ? (h->nblk_vec + 1) / 2 : h->nblk_vec;
             {
                 Scope sc(h, KC_MULTIDOT, vbytes(h, k + 1));
-                if (k <= 4) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<4, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)w, (const double *)V, h->vlen, k, h->part));
-                else if (k <= 8) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<8, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)w, (const double *)V, h->vlen, k, h->part));
-                else if (k <= 16) VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<16, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)w, (const double *)V, h->vlen, k, h->part));
-                else VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<32, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)w, (const double *)V, h->vlen, k, h->part));
+                KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot_gram<KB, VW>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)w, (const double *)V, h->vlen, k, h->part)));
             }
             {
                 Scope sc(h, KC_REDUCE, 8.0 * (2 * k + 1) * (double)nb);
@@ -626,10 +607,7 @@ static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x,
             hipLaunchKernelGGL(k_gmres_coef, dim3(1), dim3(64), 0, h->st, j, h->restart_alloc, beta, (const double *)h->dres, dG, dH, dcs, dsn, dg, dcoef, dscale, dmon);
             {
                 Scope sc(h, KC_GSUPDATE, vbytes(h, k + 2));
-                if (k <= 4) VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update_dev<4, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, (const double *)V, h->vlen, k, (const double *)dcoef, (const double *)dscale));
-                else if (k <= 8) VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update_dev<8, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, (const double *)V, h->vlen, k, (const double *)dcoef, (const double *)dscale));
-                else if (k <= 16) VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update_dev<16, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, (const double *)V, h->vlen, k, (const double *)dcoef, (const double *)dscale));
-                else VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update_dev<32, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, (const double *)V, h->vlen, k, (const double *)dcoef, (const double *)dscale));
+                KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update_dev<KB, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, (const double *)V, h->vlen, k, (const double *)dcoef, (const double *)dscale)));
             }
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(hmon + 2 * j, dmon + 2 * j, 2 * sizeof(double), hipMemcpyDeviceToHost, h->st));
@@ -648,11 +626,7 @@ static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x,
         HIPCHK(h, hipMemcpyAsync(hH, dH, sizeof(double) * (size_t)ld * h->restart_alloc, hipMemcpyDeviceToHost, h->st));
         HIPCHK(h, hipMemcpyAsync(hg, dg, sizeof(double) * ld, hipMemcpyDeviceToHost, h->st));
         HIPCHK(h, hipStreamSynchronize(h->st));
-        for (int i = kused - 1; i >= 0; i--) {
-            double s = hg[i];
-            for (int q = i + 1; q < kused; q++) s -= hH[(size_t)ld * q + i] * y[q];
-            y[i] = s / hH[(size_t)ld * i + i];
-        }
+        ksfd_krylov::hess_backsolve(hH, ld, hg, kused, y.data());
         if ((rc = op_basis_axpy(h, x, V, kused, y.data(), first ? 0.0 : 1.0))) return rc;
         first = false;
         rn = hmon[2 * (kused - 1)];

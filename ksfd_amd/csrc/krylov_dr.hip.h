@@ -35,7 +35,7 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     // coarsest-grid iteration that stops on a tolerance), so x = M^-1 (V y) is not sum_j y_j M^-1 v_j, the recurrence residual of plain right
     // preconditioning misses the true one by more than the tolerance (measured: 107 failed checks in 30 steps of the 384^2 run at
     // ksp_rtol = 1e-6, every one answered with more iterations), and the update costs a V cycle of its own.
-    const bool use_pc = pcmode == 1, use_flex = pcmode == 1 || pcmode == 2;
+    const bool use_flex = pcmode == 1 || pcmode == 2;
     const double shift_pc = std::max(shift, h->memo.mg_shift_floor);
     const int m = std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc);
     const int keep = h->dr_keep;
@@ -60,16 +60,6 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     }
     K.valid = false;                                       // V is about to change; set again where a relation is left behind
 
-    auto precond_apply = [&](int j, double *w) -> int {    // w = A M^-1 v_j
-        double *vj = V + (int64_t)j * vs;
-        int r;
-        if (use_flex) {
-            double *zj = Zq + (int64_t)j * vs;
-            return (r = use_pc ? mg_precond(h, shift_pc, vj, zj) : poly_apply(h, shift, vj, zj)) ? r : op_jvp_frozen_halo(h, zj, 1, shift, w);
-        }
-        if (h->use_frozen) return op_jvp_frozen_halo(h, vj, 1, shift, w);
-        return (r = halo(h, vj)) ? r : op_jvp(h, ustate, vj, 1, shift, w);
-    };
     auto true_residual = [&](double *r) -> int {           // r = b - A x
         int q;
         if ((q = halo(h, x))) return q;
@@ -102,11 +92,8 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     if ((rc = op_copy(h, r0, b))) return rc;
     if ((rc = op_multidot(h, r0, V, kk ? kk + e : 0))) return rc;
     const double bn = sqrt(h->hres[kk ? kk + e : 0]);
-    if (!(bn > 0.0)) {
-        if (bn != bn) return fail(h, KSFD_ENAN, "GMRES-DR: right-hand side is not finite");
-        HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
-        return KSFD_OK;
-    }
+    bool empty;
+    if ((rc = rhs_empty(h, bn, x, "GMRES-DR: right-hand side is not finite", &empty)) || empty) return rc;
     const double tol = tol_abs > 0.0 ? tol_abs : std::max(o->ksp_rtol * bn, o->ksp_atol);
     const double rel_den = (tol_abs > 0.0 && o->ksp_rtol > 0.0) ? tol_abs / o->ksp_rtol : bn;
     int total = 0, stagnant = 0;
@@ -157,15 +144,11 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
             while (!converged && !broke && n < ncols && total < maxit) {
                 const int j = n, nb = j + e;               // column j: w against the nb vectors in front of it
                 double *w = V + (int64_t)nb * vs;
-                if ((rc = precond_apply(j, w))) return rc;
+                if ((rc = apply_AMinv(h, ustate, shift, shift_pc, pcmode, V + (int64_t)j * vs, use_flex ? Zq + (int64_t)j * vs : nullptr, w))) return rc;     // w = A M^-1 v_j
                 if ((rc = op_multidot(h, w, V, nb))) return rc;
-                for (int i = 0; i < nb; i++) hcol[i] = h->hres[i];
                 if (!(h->hres[nb] == h->hres[nb])) return fail(h, KSFD_ENAN, "GMRES-DR: Krylov vector is not finite");
-                if ((rc = op_gs_update(h, w, V, nb, hcol.data(), 1.0)) || (rc = op_multidot(h, w, V, nb))) return rc;
-                double s2 = 0.0;
-                for (int i = 0; i < nb; i++) { dcol[i] = h->hres[i]; hcol[i] += dcol[i]; s2 += dcol[i] * dcol[i]; }
-                const double hn = sqrt(std::max(h->hres[nb] - s2, 0.0));
-                if ((rc = op_gs_update(h, w, V, nb, dcol.data(), hn > 0.0 ? 1.0 / hn : 0.0))) return rc;
+                double hn;
+                if ((rc = cgs2_classic(h, w, V, nb, hcol.data(), dcol.data(), &hn))) return rc;
                 double *Hc = &Hb[(size_t)j * ld];
                 for (int i = 0; i < ld; i++) Hc[i] = i < nb ? hcol[i] : 0.0;
                 Hc[nb] = hn;

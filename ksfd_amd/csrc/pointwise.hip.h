@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_multidot(KVec g, const double *_
     }
 }
 
-// One-pass Gram-Schmidt data for GMRES with a lagged Gram row (see gmres() in ksfd_hip.hip):
+// One-pass Gram-Schmidt data for GMRES with a lagged Gram row (see cgs2_algebraic() in krylov_small.h):
 //   rows 0..k-1   : d[i] = <w, V_i>
 //   rows k..2k-1  : g[i] = <V_{k-1}, V_i>      (Gram row of the newest basis vector)
 //   row  2k       : <w, w>
