@@ -72,7 +72,9 @@ typedef int (*ksfd_exchange_fn)(void *ctx, const double *send_lo, const double *
                                 double *recv_lo, double *recv_hi, int64_t count);
 typedef int (*ksfd_allreduce_fn)(void *ctx, double *buf, int32_t count, int32_t op /*0 sum, 1 max*/);
 /* uniform all-to-all on host buffers: block q of `send` (bytes_per_peer bytes) goes to rank q, block r of `recv` comes from
- * rank r (the own block included).  Optional: without it the spectral solver stays single-rank under transport 2. */
+ * rank r (the own block included).  Optional: without it the spectral solver stays single-rank under transport 2.  With it (and
+ * under transport 1) 1, 2, 4 or 8 slab ranks have the solver for the same extents as one rank, 2^k or 3*2^k per axis: see
+ * ksfd_spectral_apply; other rank counts do not. */
 typedef int (*ksfd_alltoall_fn)(void *ctx, const void *send, void *recv, int64_t bytes_per_peer);
 typedef struct ksfd_dist {
     int32_t rank, size;
@@ -98,8 +100,8 @@ typedef struct ksfd_step_opts {
     double ksp_rtol, ksp_atol;  /* GMRES: stop at ||r|| <= max(ksp_rtol*||b||, ksp_atol) */
     int32_t ksp_restart, ksp_max_it;
     int32_t pc_type;            /* 0 none; 1 geometric multigrid V cycle always; 2 automatic (default): the spectral defect correction
-                                 * (constant-coefficient part of shift*I - J inverted by FFT; 2-D and 3-D, extents 2^k or 3*2^k on one
-                                 * rank; on 1, 2, 4 or 8 slab ranks see ksfd_spectral_apply) while it converges in a few sweeps, else multigrid when the step is stiff,
+                                 * (constant-coefficient part of shift*I - J inverted by FFT; 2-D and 3-D, extents 2^k or 3*2^k, on one
+                                 * rank and on 1, 2, 4 or 8 slab ranks: see ksfd_spectral_apply) while it converges in a few sweeps, else multigrid when the step is stiff,
                                  * Chebyshev polynomial + flexible GMRES when mildly stiff, none when not; 3 polynomial only;
                                  * 4 spectral always; 5 direct: dense LU of shift*I - J on the device, factored once per step attempt, every
                                  * stage solve checked by its true residual against max(ksp_rtol*||b||, ksp_atol) with at most two refinement
@@ -272,13 +274,11 @@ int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, doub
 /* Spectral preconditioner: z = (shift*I - J0)^-1 v with J0 the constant-coefficient part of the Jacobian at the resident state
  * (grid means of rho*G_rho, rho*G_Ul; the 4th-order star's exact symbol), three hand-written FFT kernels (csrc/spectral.hip.h).
  * Handles that have it: on one rank without a halo transport, every 2-D and 3-D grid whose extents are each 2^k (32..16384) or
- * 3*2^k (48..12288), through every column path (the two-phase column kernel for columns that do not fit the LDS included); 2-D
- * on 1 (ring of one), 2, 4 or 8 slab ranks over a transport with an all-to-all, ny/P >= 4 local rows (3*2^j rows travel as three
- * chunks of 2^j); 3-D with power-of-two extents on 1, 2, 4, 8 z-slab ranks with 2^j local planes.
- * Handles that do not: 1-D, other extents, other rank counts, a transport without an all-to-all, and -- on slab ranks and the ring
- * of one only -- 3-D boxes with a 3*2^k extent, and 2-D grids with a 3*2^k column extent whose 2*npair columns of a block do not
- * fit the LDS together (more than 8192 rows, or 6144 rows with three or more fields: the two-phase column kernel is power-of-two
- * only there).  Timing between different devices is unmeasured for all of them.
+ * 3*2^k (48..12288), through every column path (the two-phase column kernel for columns that do not fit the LDS included); the
+ * same grids on P = 1 (ring of one), 2, 4 or 8 slab ranks over a transport with an all-to-all: 2-D with ny/P >= 4 local rows, 3-D
+ * with nz/P >= 2 local planes (3*2^j local rows or planes travel as three chunks of 2^j, which every valid extent allows).
+ * Handles that do not: 1-D, other extents, rank counts other than 1, 2, 4, 8, a transport without an all-to-all.  Timing between
+ * different devices is unmeasured for all of them.
  * _apply is the parity/test entry (host vectors; KSFD_EINVAL where the handle has no spectral solver).  _params: stiffness
  * h*gamma*lambda_max(diffusion) from which pc_type 2 prefers it (default 0.1 where the fused 2-D residual kernel runs, 0.3
  * elsewhere; <= 0 keeps) and enable (0 = never pick it automatically, 1 = default, < 0 keeps). */

@@ -44,14 +44,14 @@ struct SpecState {
     int *posz = nullptr, *kzofpos = nullptr;
     float *lz = nullptr;
     int rb = 0, npair = 0, nyp = 0;
-    int nch = 1;                             // slab ranks with 3 * 2^j rows: 3 chunks of 2^j rows (spectral_plan.h); else 1
+    int nch = 1;                             // slab ranks with 3 * 2^j rows (3-D: z planes): 3 chunks of 2^j (spectral_plan.h); else 1
     size_t lds_rows = 0, lds_cols = 0;
     kcf *W = nullptr, *W2 = nullptr, *twx = nullptr, *twy = nullptr, *twz = nullptr;     // W: [pair][pos_x][y_local]; W2: after the all-to-all, [rank][pair][own pos][y_local] (nch = 3: [chunk] in front of [pair] in both)
     int *posy = nullptr, *kyofpos = nullptr;
     int2 *ytab = nullptr;                    // per y position: (position of -ky, bits of ly[ky]) -- symbol stage of k_spec_cols
     int lgw = -1;                            // layout of the forward work array (kspec_wt_index)
     int4 *pairtab = nullptr;          // per block of the column kernel
-    int nxl = 0, nblk_cols = 0, lg_pl = 0;   // owned positions, column-kernel blocks, log2(rows per rank)
+    int nxl = 0, nblk_cols = 0, lg_pl = 0;   // owned positions, column-kernel blocks, log2(rows (3-D: planes) per rank and chunk)
     std::vector<A2APiece> a2a_fwd_s, a2a_fwd_r, a2a_bwd_s, a2a_bwd_r;
     float *lx = nullptr, *ly = nullptr;
     double a_rr = 0.0, a_rU[KSFD_MAXL] = { 0 };

@@ -196,7 +196,7 @@ extern "C" int ksfd_create(const ksfd_config *cfg, const ksfd_dist *dist, ksfd_h
         for (auto &e : h->gm_ev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) CFAIL(KSFD_EHIP, "hipEventCreate failed");
     }
 
-    spec_build(h);                                            // leaves spec.ok = false where it does not apply (3-D, non power-of-two extents, ...)
+    spec_build(h);                                            // leaves spec.ok = false where it does not apply (1-D, extents other than 2^k or 3 * 2^k, other rank counts, ...)
     if (mg_build(h)) { mg_free(h); h->mg_ok = false; }        // out of memory for the hierarchy: run without the multigrid preconditioner
     if ((h->spec.ok || h->mg_ok) && alloc_d(h, &h->bstore, 3 * h->vlen)) { h->bstore = nullptr; h->spec_guess = false; h->err.clear(); }
     if (h->ring) {
@@ -773,7 +773,7 @@ extern "C" int ksfd_spectral_apply(ksfd_handle *h, double shift, const double *v
 {
     if (!h || !vh || !outh || !(shift > 0.0)) return KSFD_EINVAL;
     hipSetDevice(h->device);
-    if (!h->spec.ok) return fail(h, KSFD_EINVAL, "spectral preconditioner not available for this handle (needs power-of-two extents of 32 ... 16384 points; 1, 2, 4 or 8 slab ranks with an all-to-all transport)");
+    if (!h->spec.ok) return fail(h, KSFD_EINVAL, "spectral preconditioner not available for this handle (needs a 2-D or 3-D grid with every extent 2^k, 32 ... 16384, or 3*2^k, 48 ... 12288; on slab ranks 1, 2, 4 or 8 of them, an all-to-all transport, at least 4 local rows or 2 local planes)");
     int rc;
     if ((rc = upload(h, vh, layout, h->t2))) return rc;
     if ((rc = ensure_coef(h))) return rc;

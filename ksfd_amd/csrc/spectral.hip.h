@@ -723,7 +723,8 @@ __global__ void __launch_bounds__(1024) k_spec_cols(KFFTPlan PY, int nxl, int lg
 //            from W (contiguous along y in both walking directions); inverse transform; result to Wout -- a different array, since
 //            the blocks of the other field pairs still read W
 // 2 + (npair + 2) passes over a pair's columns instead of 2: the price of keeping the solver at all for such sizes.
-// R3 = true: columns of 3 * 2^k points (one rank: a column is one piece, its stride in W rounded up to the power of two of lg_pl).
+// R3 = true: columns of 3 * 2^k points (one rank: a column is one piece, its stride in W rounded up to the power of two of lg_pl; slab
+// ranks: 3 P pieces of 2^lg_pl = 2^j points, the chunks of spectral_plan.h -- the index arithmetic below only ever splits y by lg_pl).
 template <int NL, bool R3>
 __device__ __forceinline__ void kspec_cols_symbol_split(const KFFTPlan &PY, kcf *lds, int sstride, bool self, int kxA, int kxB, int p0, const kcf *__restrict__ W,
                                                         int nxl, int lg_pl, long long pstride, int jA, int jB, const int *__restrict__ posy,
@@ -793,7 +794,7 @@ __device__ __forceinline__ void kspec_cols_symbol_split1(const KFFTPlan &PY, kcf
     }
 }
 
-template <bool R3>      // R3: ny = 3 * 2^lg (one rank)
+template <bool R3>      // R3: ny = 3 * 2^lg
 __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY, int nxl, int lg_pl, long long pstride, kcf *__restrict__ W, const kcf *__restrict__ Wt, int lg_rb,
                                                          kcf *__restrict__ Wout, const kcf *__restrict__ tw, const int4 *__restrict__ pairtab, const int *__restrict__ posy,
                                                          const int *__restrict__ kyofpos, const float *__restrict__ lx, const float *__restrict__ ly, KSpecSym S)
@@ -891,7 +892,7 @@ __global__ void __launch_bounds__(1024) k_spec_cols_split(int phase, KFFTPlan PY
 //   k_spec3_y_inv : reads CZ-z segments of W2, DIT inverse along y, stores W3[pair][pos_x][z*ny + y] (contiguous runs of ny)
 // and the inverse x rows over W3.  HBM traffic 48 F N bytes per application (five kernels, four passes over the work arrays).
 // Each of the y and z kernels has two instances, chosen by ITS axis: R3 = false for 2^k points (with the fused edge stages), R3 = true for
-// 3 * 2^k (generic staging, sequences of three padded sub-sequences; one rank) -- a box may mix them.
+// 3 * 2^k (generic staging, sequences of three padded sub-sequences) -- a box may mix them.  z-slab ranks: spectral_host.hip.h.
 // ---------------------------------------------------------------------------------------------
 // global -> LDS staging in batches of 8 items per thread: all loads of a batch are issued before the first LDS store (one memory
 // latency per batch instead of one per item; the plain loop left it to the compiler, which kept them in order)
@@ -1010,8 +1011,11 @@ __device__ __forceinline__ void kspec3_z_symbol(const KFFTPlan &PZ, kcf *kspec_l
 
 // pairtab[e] = (column A, column B, kx | ky << 16, self) with column = pos_x * ny + pos_y; self: A == B is its own partner
 // Column storage as in k_spec_cols: a column consists of nz >> lg_pl pieces of 2^lg_pl elements, `pstride` elements apart (one piece
-// per z-slab rank after the all-to-all; a single piece on one rank).
-template <int NPAIR_T, bool R3>      // NPAIR_T as k_spec_cols: 1, 2 or 0 = run-time number of field pairs; R3: nz = 3 * 2^lg (one rank)
+// per z-slab rank after the all-to-all, three per rank for 3 * 2^j local planes; a single piece on one rank).
+// NPAIR_T as k_spec_cols: 1, 2 or 0 = run-time number of field pairs; R3: nz = 3 * 2^lg; ONEPIECE (the default for R3: one rank): the column
+// is one piece of exactly nz elements, which no power-of-two piece size describes.  k_spec3_z<*, true, false>: slab ranks with 3 * 2^j
+// local planes, nz = 3 * 2^lg in 3 P pieces of 2^lg_pl = 2^j elements.
+template <int NPAIR_T, bool R3, bool ONEPIECE = R3>
 __global__ void __launch_bounds__(1024) k_spec3_z(KFFTPlan PZ, int nent, int pb, long long ncol, int lg_pl, long long pstride, kcf *__restrict__ W2, const kcf *__restrict__ tw,
                                                   const int4 *__restrict__ pairtab, const int *__restrict__ posz, const int *__restrict__ kzofpos,
                                                   const float *__restrict__ lx, const float *__restrict__ ly, const float *__restrict__ lz, const int2 *__restrict__ ztab, KSpecSym S)
@@ -1028,10 +1032,10 @@ __global__ void __launch_bounds__(1024) k_spec3_z(KFFTPlan PZ, int nent, int pb,
     auto colptr = [&](int s) {                                     // start of the column's FIRST piece
         const int c = s & 1, p = (s >> 1) % npair, slot = (s >> 1) / npair;
         const int4 pt = pairtab[e0 + slot];
-        if (R3) return W2 + ((long long)p * ncol + (c ? pt.y : pt.x)) * nz;        // one piece of exactly nz elements
+        if (ONEPIECE) return W2 + ((long long)p * ncol + (c ? pt.y : pt.x)) * nz;        // one piece of exactly nz elements
         return W2 + (((long long)p * ncol + (c ? pt.y : pt.x)) << lg_pl);
     };
-    auto zoff = [&](int z) { return R3 ? (long long)z : (long long)(z >> lg_pl) * pstride + (z & plmask); };      // z even: a float4 never straddles two pieces
+    auto zoff = [&](int z) { return ONEPIECE ? (long long)z : (long long)(z >> lg_pl) * pstride + (z & plmask); };      // z even: a float4 never straddles two pieces
     const bool edge_in = !R3 && PZ.radix[0] == 16 && (PZ.flags & 1), edge_out = !R3 && PZ.radix[0] == 16 && (PZ.flags & 2);
     const int S0 = nz >> 4;
     if (edge_in) {

@@ -18,10 +18,12 @@ template <typename T> static bool spec_upload(T **dev, const std::vector<T> &hos
 }
 
 // 3-D (see spectral.hip.h): plans per axis, the column-pair table of the z kernel, two work arrays.  One rank: every extent with a plan,
-// 2^k or 3 * 2^k per axis (the y and z kernels have an instance for each: template parameter R3).  z-slab ranks (P = 2, 4, 8), 2^k only: the
-// x and y transforms are local (a rank owns whole z planes); for the z transforms every rank needs whole z columns, so
-// W[pair][pos_x][pos_y][z_local] is redistributed by an all-to-all over pos_x exactly as in 2-D (same digit ownership: the columns
-// (kx, ky) and (-kx, -ky) land on one rank), a received column consisting of P pieces of nz/P elements.
+// 2^k or 3 * 2^k per axis (the y and z kernels have an instance for each: template parameter R3).  z-slab ranks (P = 2, 4, 8, and the
+// ring of one), the same extents: the x and y transforms are local (a rank owns whole z planes); for the z transforms every rank needs
+// whole z columns, so W[pair][pos_x][pos_y][z_local] is redistributed by an all-to-all over pos_x exactly as in 2-D (same ownership,
+// spectral_plan.h: the columns (kx, ky) and (-kx, -ky) land on one rank), a received column consisting of P pieces of nz/P elements.
+// 3 * 2^j local planes are nch = 3 chunks of cs = 2^j: both work arrays are chunk-major, the row and y kernels run once per chunk, and
+// a received column is 3 P pieces of 2^j elements (k_spec3_z<*, true, false>).
 static void spec_build3d(ksfd_handle *h)
 {
     SpecState &S = h->spec;
@@ -33,12 +35,16 @@ static void spec_build3d(ksfd_handle *h)
     if (ring && (!h->tr || !h->tr->has_alltoall() || (P != 1 && P != 2 && P != 4 && P != 8) || getenv("KSFD_SPEC_SINGLE"))) return;
     const long long nzg = h->cfg.n[2], nzl = G.sloc;               // global / local z planes
     if (!spec_plan(G.nx, S.px) || !spec_plan(G.ny, S.py) || !spec_plan(nzg, S.pz)) return;
-    if (ring && (S.px.m != 1 || S.py.m != 1 || S.pz.m != 1 || (nzl & (nzl - 1)))) return;      // (3 * 2^k extents: one rank without a halo transport only)
+    SpecOwn O;
+    int nch = 1;                                                   // chunks of a rank's planes (3 on slab ranks with 3 * 2^j planes)
+    if (ring && !spec_slab3_eligible(S.px, S.pz, P, nzl, O, nch)) return;
     if (S.px.radix[0] != 16 || G.nx > 32768 || G.ny > 32768 || nzl < 2) return;
+    const long long cs = nzl / nch;                                // planes per chunk: a power of two on slab ranks
     S.dim = 3;
+    S.nch = nch;
     S.npair = (G.F + 1) / 2;
     const size_t lds_max = 160 * 1024 - 1024;
-    const long long nrows = G.ny * nzl;
+    const long long nrows = G.ny * cs;                             // x rows of a chunk
     const size_t row_bytes = sizeof(kcf) * spec_sstride(S.px);
     int rb = 16;
     while (rb > 1 && row_bytes * rb > lds_max) rb >>= 1;
@@ -50,7 +56,7 @@ static void spec_build3d(ksfd_handle *h)
     S.lds_rows = row_bytes * rb;
     const size_t ycol = sizeof(kcf) * spec_sstride(S.py) * S.npair, zcol = sizeof(kcf) * spec_sstride(S.pz) * 2 * S.npair;
     int cz = 16;
-    while (cz > 1 && (ycol * cz > lds_max / 2 || nzl % cz)) cz >>= 1;      // <= half the LDS: two blocks per CU
+    while (cz > 1 && (ycol * cz > lds_max / 2 || cs % cz)) cz >>= 1;      // <= half the LDS: two blocks per CU
     if (getenv("KSFD_SPEC_CZ")) cz = std::max(1, std::min(cz, atoi(getenv("KSFD_SPEC_CZ"))));        // experiment knob
     if (ycol * cz > lds_max) return;
     S.lg_cz = 0; while ((1 << S.lg_cz) < cz) S.lg_cz++;
@@ -68,26 +74,26 @@ static void spec_build3d(ksfd_handle *h)
         const bool y3 = S.py.m == 3, z3 = S.pz.m == 3;             // the kernel instances spec_apply launches
         if (e == hipSuccess) e = hipFuncSetAttribute(y3 ? (const void *)k_spec3_y_fwd<true> : (const void *)k_spec3_y_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_y3);
         if (e == hipSuccess) e = hipFuncSetAttribute(y3 ? (const void *)k_spec3_y_inv<true> : (const void *)k_spec3_y_inv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_y3);
-        const void *kz = S.npair == 1 ? (z3 ? (const void *)k_spec3_z<1, true> : (const void *)k_spec3_z<1, false>)
+        const void *kz = nch == 3      ? (S.npair == 1 ? (const void *)k_spec3_z<1, true, false> : S.npair == 2 ? (const void *)k_spec3_z<2, true, false> : (const void *)k_spec3_z<0, true, false>)
+                       : S.npair == 1 ? (z3 ? (const void *)k_spec3_z<1, true> : (const void *)k_spec3_z<1, false>)
                        : S.npair == 2 ? (z3 ? (const void *)k_spec3_z<2, true> : (const void *)k_spec3_z<2, false>)
                                       : (z3 ? (const void *)k_spec3_z<0, true> : (const void *)k_spec3_z<0, false>);
         if (e == hipSuccess) e = hipFuncSetAttribute(kz, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_z3);
         if (e != hipSuccess) { hipGetLastError(); return; }
     }
-    // ownership of the x positions (as in 2-D): top digit -> (rank, index of the digit in that rank's list)
-    const int nx = (int)G.nx, ny = (int)G.ny, nx16 = nx / 16, ndig = 16 / P;
-    int dig_rank[16], dig_idx[16];
-    for (int q = 0; q < P; q++) for (int di = 0; di < ndig; di++) { const int d = spec_digit_order[q * ndig + di]; dig_rank[d] = q; dig_idx[d] = di; }
+    // ownership of the x positions on slab ranks: spectral_plan.h, as in 2-D (one rank: positions are their own index)
+    const int nx = (int)G.nx, ny = (int)G.ny;
     S.nxl = nx / P;
     S.lg_pl = 0;
-    while ((1LL << S.lg_pl) < nzl) S.lg_pl++;
-    auto local_index = [&](int j) { return !ring ? j : dig_idx[j / nx16] * nx16 + (j % nx16); };
+    while ((1LL << S.lg_pl) < cs) S.lg_pl++;
+    auto mine = [&](int j) { return !ring || spec_owner(O, j) == h->rank; };
+    auto local_index = [&](int j) { return !ring ? j : spec_local_index(O, j); };
     // pairs of columns {(kx,ky), (-kx,-ky)}; a column is addressed by its (local) position pair
     const std::vector<int> posx = spec_positions(S.px), posy = spec_positions(S.py);
     std::vector<int4> ent;
     ent.reserve((size_t)S.nxl * ny / 2 + 4);
     for (int kx = 0; kx <= nx / 2; kx++) {
-        if (dig_rank[posx[kx] / nx16] != h->rank) continue;
+        if (!mine(posx[kx])) continue;
         for (int ky = 0; ky < ny; ky++) {
             const int kxm = (nx - kx) % nx, kym = (ny - ky) % ny;
             const bool self = kxm == kx && kym == ky;
@@ -98,7 +104,7 @@ static void spec_build3d(ksfd_handle *h)
     }
     std::sort(ent.begin(), ent.end(), [](const int4 &a, const int4 &b) { return a.x < b.x; });
     S.nent = (int)ent.size();
-    const size_t wbytes = sizeof(kcf) * (size_t)S.npair * G.nx * nrows;
+    const size_t wbytes = sizeof(kcf) * (size_t)S.npair * G.nx * nrows * nch;
     if (hipMalloc((void **)&S.W, wbytes) != hipSuccess || hipMalloc((void **)&S.W2, wbytes) != hipSuccess ||
         !spec_upload(&S.twx, spec_twiddles(S.px)) || !spec_upload(&S.twy, spec_twiddles(S.py)) ||
         !spec_upload(&S.posz, spec_positions(S.pz)) || !spec_upload(&S.kzofpos, spec_inverse(spec_positions(S.pz))) || !spec_upload(&S.pairtab, ent) ||
@@ -112,14 +118,14 @@ static void spec_build3d(ksfd_handle *h)
         S.twz = tz;
     } else S.twz = S.twy;
     if (ring) {
-        // pieces of the two all-to-alls: one per (peer, pair, top digit of the receiver) = nx/16 positions x ny x nzl, contiguous on both sides
-        const size_t pel = (size_t)nx16 * ny * nzl, pbytes = sizeof(kcf) * pel;
+        // blocks of the two all-to-alls: one per (peer, pair, piece of the receiver, chunk) = w positions x ny x cs planes, contiguous on
+        // both sides (spectral_plan.h; 2^k boxes: nx/16 positions x ny x all planes of the rank)
+        const size_t pbytes = sizeof(kcf) * (size_t)O.w * ny * cs;
         for (int q = 0; q < P; q++)
             for (int p = 0; p < S.npair; p++)
-                for (int di = 0; di < ndig; di++) {
-                    const int dq = spec_digit_order[q * ndig + di];
-                    kcf *mine_for_q = S.W + ((size_t)p * nx + (size_t)dq * nx16) * ny * nzl;                          // my z planes of q's columns
-                    kcf *from_q = S.W2 + (((size_t)q * S.npair + p) * S.nxl + (size_t)di * nx16) * ny * nzl;          // q's z planes of my columns
+                for (int di = 0; di < O.per; di++) for (int c = 0; c < nch; c++) {
+                    kcf *mine_for_q = S.W + spec_a2a3_src(O, nx, ny, S.npair, cs, q, p, di, c);                       // my z planes of q's columns
+                    kcf *from_q = S.W2 + spec_a2a3_dst(O, ny, S.npair, nch, cs, q, p, di, c);                         // q's z planes of my columns
                     S.a2a_fwd_s.push_back({ q, mine_for_q, pbytes });
                     S.a2a_fwd_r.push_back({ q, from_q, pbytes });
                     S.a2a_bwd_s.push_back({ q, from_q, pbytes });
@@ -143,7 +149,6 @@ static void spec_build(ksfd_handle *h)
     if (ring && (!h->tr || !h->tr->has_alltoall() || (P != 1 && P != 2 && P != 4 && P != 8) || getenv("KSFD_SPEC_SINGLE"))) return;
     const long long ny = h->cfg.n[1], nyl = G.sloc;                  // global / local rows
     if (!spec_plan(G.nx, S.px) || !spec_plan(ny, S.py)) return;
-    const bool pow2 = S.px.m == 1 && S.py.m == 1;
     SpecOwn O;
     int nch = 1;                                                     // chunks of a rank's rows (3 on slab ranks with 3 * 2^j rows)
     if (ring && !spec_slab_eligible(S.px, S.py, P, nyl, O, nch)) return;
@@ -171,7 +176,6 @@ static void spec_build(ksfd_handle *h)
         S.lds_cols = sizeof(kcf) * spec_sstride(S.py);
     }
     if (S.lds_cols > lds_max - 1024) return;
-    if (S.cols_split && !pow2 && ring) return;                       // (slab ranks: the two-phase column kernel is power-of-two only)
     if (hipFuncSetAttribute((const void *)k_spec_rows_fwd<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_spec_rows_fwd<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows) != hipSuccess ||
         hipFuncSetAttribute((const void *)k_spec_rows_inv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_rows) != hipSuccess) { hipGetLastError(); return; }
@@ -295,11 +299,12 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
     Y.den_floor = (float)(0.02 * shift);
     for (int l = 0; l < h->P.nlig; l++) { Y.a_rU[l] = (float)S.a_rU[l]; Y.s[l] = (float)h->P.lig_s[l]; Y.gam[l] = (float)h->P.lig_gamma[l]; Y.D[l] = (float)h->P.lig_D[l]; }
     const bool d3 = S.dim == 3;
-    // slab ranks with 3 * 2^j rows: the row kernels run once per chunk of 2^j rows, on that chunk's part of the vectors and of the
-    // chunk-major work array (spec_build); everywhere else nch = 1 and the loops below are one launch
-    const int nch = d3 ? 1 : S.nch;
+    // slab ranks with 3 * 2^j rows (3-D: z planes): the row kernels, and the y kernels in 3-D, run once per chunk of 2^j rows (planes), on
+    // that chunk's part of the vectors and of the chunk-major work arrays (spec_build); everywhere else nch = 1 and the loops below
+    // are one launch
+    const int nch = S.nch;
     const int ntiles = (int)((d3 ? G.ny * G.sloc : G.sloc) / S.rb) / nch;     // 3-D: the x rows are the nz*ny rows of the box
-    const long long rows_off = G.sloc / nch * G.nx, w_off = (long long)S.npair * G.nx * S.nyp;      // a chunk's rows in a plane / in W
+    const long long rows_off = G.sloc / nch * G.inner, w_off = (long long)S.npair * G.nx * S.nyp;      // a chunk's rows in a plane (inner = nx in 2-D, nx * ny in 3-D) / in W
     const long long goff = (long long)G.ng * G.inner;                // the row kernels address owned rows only
     KSpecLin ex, add;
     memset(&ex, 0, sizeof ex); memset(&add, 0, sizeof add);
@@ -340,7 +345,7 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
     }
     if (d3) {
         const int cz = 1 << S.lg_cz;
-        const long long nzg = h->cfg.n[2], nzl = G.sloc;
+        const long long nzg = h->cfg.n[2], nzc = G.sloc / nch;      // planes of a chunk
         // (whole waves: 3 * 2^k extents with three or more field pairs give odd multiples of 32)
         const int thr_y = (int)std::min<long long>(1024, std::max<long long>(256, ((long long)S.npair * cz * G.ny / 16 + 63) & ~63LL));
         int thr_z = (int)std::min<long long>(1024, std::max<long long>(128, ((long long)2 * S.npair * S.pb * nzg / 16 + 63) & ~63LL));
@@ -351,9 +356,9 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
         py3.flags = pz3.flags = fuse3 & 3;
         {
             Scope sc(h, KC_SPECTRAL, 2.0 * pn, 0.0);
-#define KSPEC_YF_LAUNCH(R3) hipLaunchKernelGGL(k_spec3_y_fwd<R3>, dim3((unsigned)(nzl / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzl, S.lg_cz, S.npair, S.lg_rb3, \
-                               (const kcf *)S.W2, S.W, (const kcf *)S.twy)
-            if (py3.m == 3) KSPEC_YF_LAUNCH(true); else KSPEC_YF_LAUNCH(false);
+#define KSPEC_YF_LAUNCH(R3) hipLaunchKernelGGL(k_spec3_y_fwd<R3>, dim3((unsigned)(nzc / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzc, S.lg_cz, S.npair, S.lg_rb3, \
+                               (const kcf *)S.W2 + c * w_off, S.W + c * w_off, (const kcf *)S.twy)
+            for (int c = 0; c < nch; c++) { if (py3.m == 3) KSPEC_YF_LAUNCH(true); else KSPEC_YF_LAUNCH(false); }
 #undef KSPEC_YF_LAUNCH
         }
         kcf *Wz = S.W;
@@ -365,10 +370,12 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
         {
             Scope sc(h, KC_SPECTRAL, 2.0 * pn, 0.0);
             const long long pstride = (long long)S.npair * S.nxl * G.ny << S.lg_pl;
-#define KSPEC_Z_LAUNCH(NP) hipLaunchKernelGGL((k_spec3_z<NP, R3>), dim3((unsigned)((S.nent + S.pb - 1) / S.pb)), dim3(thr_z), S.lds_z3, h->st, pz3, S.nent, S.pb, (long long)S.nxl * G.ny, S.lg_pl, pstride, Wz, \
+#define KSPEC_Z_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, dim3((unsigned)((S.nent + S.pb - 1) / S.pb)), dim3(thr_z), S.lds_z3, h->st, pz3, S.nent, S.pb, (long long)S.nxl * G.ny, S.lg_pl, pstride, Wz, \
                                (const kcf *)S.twz, (const int4 *)S.pairtab, (const int *)S.posz, (const int *)S.kzofpos, (const float *)S.lx, (const float *)S.ly, (const float *)S.lz, (const int2 *)S.ytab, Y)
-            if (pz3.m == 3) { constexpr bool R3 = true; if (S.npair == 1) KSPEC_Z_LAUNCH(1); else if (S.npair == 2) KSPEC_Z_LAUNCH(2); else KSPEC_Z_LAUNCH(0); }
-            else { constexpr bool R3 = false; if (S.npair == 1) KSPEC_Z_LAUNCH(1); else if (S.npair == 2) KSPEC_Z_LAUNCH(2); else KSPEC_Z_LAUNCH(0); }
+            const int np = S.npair <= 2 ? S.npair : 0;               // template argument: 1, 2 or 0 = run-time count
+            if (nch == 3) { if (np == 1) KSPEC_Z_LAUNCH((k_spec3_z<1, true, false>)); else if (np == 2) KSPEC_Z_LAUNCH((k_spec3_z<2, true, false>)); else KSPEC_Z_LAUNCH((k_spec3_z<0, true, false>)); }
+            else if (pz3.m == 3) { if (np == 1) KSPEC_Z_LAUNCH((k_spec3_z<1, true>)); else if (np == 2) KSPEC_Z_LAUNCH((k_spec3_z<2, true>)); else KSPEC_Z_LAUNCH((k_spec3_z<0, true>)); }
+            else { if (np == 1) KSPEC_Z_LAUNCH((k_spec3_z<1, false>)); else if (np == 2) KSPEC_Z_LAUNCH((k_spec3_z<2, false>)); else KSPEC_Z_LAUNCH((k_spec3_z<0, false>)); }
 #undef KSPEC_Z_LAUNCH
         }
         if (h->ring) {
@@ -377,12 +384,12 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
         }
         {
             Scope sc(h, KC_SPECTRAL, 2.0 * pn, 0.0);
-#define KSPEC_YI_LAUNCH(R3) hipLaunchKernelGGL(k_spec3_y_inv<R3>, dim3((unsigned)(nzl / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzl, S.lg_cz, S.npair, \
-                               (const kcf *)S.W, S.W2, (const kcf *)S.twy)
-            if (py3.m == 3) KSPEC_YI_LAUNCH(true); else KSPEC_YI_LAUNCH(false);
+#define KSPEC_YI_LAUNCH(R3) hipLaunchKernelGGL(k_spec3_y_inv<R3>, dim3((unsigned)(nzc / cz), (unsigned)G.nx), dim3(thr_y), S.lds_y3, h->st, py3, (int)G.nx, (int)nzc, S.lg_cz, S.npair, \
+                               (const kcf *)S.W + c * w_off, S.W2 + c * w_off, (const kcf *)S.twy)
+            for (int c = 0; c < nch; c++) { if (py3.m == 3) KSPEC_YI_LAUNCH(true); else KSPEC_YI_LAUNCH(false); }
 #undef KSPEC_YI_LAUNCH
         }
-        // the inverse x rows read W3 = S.W2 ([pair][pos_x][z*ny + y]) below
+        // the inverse x rows read W3 = S.W2 ([chunk][pair][pos_x][z*ny + y]) below
     } else {
     kcf *Wc = S.W;
     if (h->ring) {                                                    // rows of everybody's columns -> whole columns of mine

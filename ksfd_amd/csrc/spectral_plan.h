@@ -99,6 +99,32 @@ static size_t spec_a2a_dst(const SpecOwn &O, int npair, int nch, long long cs, i
     return ((((size_t)sender * nch + c) * npair + p) * ((size_t)O.per * O.w) + (size_t)i * O.w) * cs;
 }
 
+// 3-D on z-slab ranks, the same scheme one axis up: x and y are local, the z columns are completed by an all-to-all over the x
+// positions (ownership of px as above, so the columns (kx, ky) and (-kx, -ky) land on one rank).  nx, ny, nz each 2^k or 3 * 2^k;
+// P = 1, 2, 4, 8 with P * nzl = nz; nz = 3 * 2^k gives a rank 3 * 2^j planes, handled as nch = 3 chunks of cs = 2^j planes (cs >= 2:
+// the z kernel moves two elements at a time), else one chunk of nzl = 2^j >= 2 planes.
+static bool spec_slab3_eligible(const KFFTPlan &px, const KFFTPlan &pz, int P, long long nzl, SpecOwn &O, int &nch)
+{
+    if (!spec_ownership(px, P, O)) return false;
+    nch = pz.m;
+    if (nzl < 2 || nzl * P != pz.n || nzl % nch) return false;
+    const long long cs = nzl / nch;
+    return cs >= 2 && !(cs & (cs - 1));
+}
+// Blocks (peer, field pair p, piece i of the receiver, chunk c) of w positions x ny x cs planes, contiguous on both sides.  Sender:
+// W[chunk][pair][pos_x][pos_y][plane in chunk] (k_spec3_y_fwd's store, once per chunk); receiver:
+// W2[sender * nch + chunk][pair][own pos_x][pos_y][plane in chunk]: a z column is P * nch pieces of cs elements at one stride
+// (npair * nxl * ny * cs), piece number = global plane / cs, as k_spec3_z addresses it.  A (pos_x, pos_y) column of cs planes takes
+// the place of a 2-D row-chunk element, so the offsets are the 2-D ones with ny * cs for cs.
+static size_t spec_a2a3_src(const SpecOwn &O, int nx, int ny, int npair, long long cs, int peer, int p, int i, int c)
+{
+    return spec_a2a_src(O, nx, npair, ny * cs, peer, p, i, c);
+}
+static size_t spec_a2a3_dst(const SpecOwn &O, int ny, int npair, int nch, long long cs, int sender, int p, int i, int c)
+{
+    return spec_a2a_dst(O, npair, nch, ny * cs, sender, p, i, c);
+}
+
 // exp(-2 pi i j / 2^lg), j < 2^lg, for the power-of-two stages; behind it, for 3 * 2^lg, exp(-2 pi i j / n), j < 2^lg (radix-3 stage)
 static std::vector<kcf> spec_twiddles(const KFFTPlan &P)
 {
