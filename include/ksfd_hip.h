@@ -237,7 +237,8 @@ int ksfd_synchronize(ksfd_handle *h);
  * timed with HIP events on the compute stream; returns average ms per launch. */
 int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, double *avg_ms, double *bytes_per_launch);
 /* use_fused: bit0 fused kernels, bit1 set = recompute (non-frozen) Jacobian action, bit2 set = no halo/compute overlap,
- * bit3 set = pipelined GMRES with device-resident Hessenberg/Givens state (off by default);
+ * bit3 set = pipelined GMRES with device-resident Hessenberg/Givens state (off by default); its cycles are at most 32 iterations long,
+ * which is what its kernels hold: a longer ksp_restart (and restart growth) runs as cycles of 32;
  * bit4 set = no Krylov recycling across the four stage systems of a step, bit5 set = recycle from every earlier stage
  * (default: from the stages measured to matter: 1 for 2 and 3, 1 and 3 for 4), bits 6-8 = leading Arnoldi vectors kept
  * per stage (1..4, 0 keeps the default 3); bit9 set = keep the polynomial preconditioner's temporaries and coefficient
@@ -325,6 +326,32 @@ int32_t ksfd_basis_capacity(const ksfd_handle *h);
  * untouched -- so that a test can assert exactly that. */
 int ksfd_basis_rotate(ksfd_handle *h, int32_t nin, int32_t nout, const double *P_host, const double *vin_host, double *vout_host,
                       int32_t layout);
+/* Parity/test entry of the Krylov vector kernels, the twin of ksfd_basis_rotate: host vectors of ksfd_local_size doubles in `layout` are
+ * uploaded into the leading slots of the Krylov basis, ONE operation runs through the launch wrappers the stage solvers call (basis-size
+ * ladder 4 | 8 | 16 | 32, chunks of 32 vectors above that, the block-partial reduction), and results are downloaded.  The k basis vectors
+ * are slots 0 .. k-1 and the vector w the operation measures or updates is slot k, as in the solvers; vecs_host holds all nvec slots in
+ * that order and out_vecs_host receives ALL of them back, so a test can assert that what an operation does not write is untouched.
+ * cap = ksfd_basis_capacity.  KSFD_EINVAL for a k outside the limits, before anything is touched; the state and what the stepper
+ * remembers from step to step are unchanged.
+ *   LINCOMB        nvec = k = 1..6: slot 0 <- sum_t coef[t] * slot t (output aliasing input 0); want_norm: scalars[0] = ||result||^2
+ *   MULTIDOT       k = 0..cap-1, nvec = k+1: scalars[i] = <w, V_i>, i < k; scalars[k] = <w, w>
+ *   MULTIDOT_GRAM  k = 1..min(32, cap-1), nvec = k+1: scalars[i] = <w, V_i>; scalars[k+i] = <V_{k-1}, V_i>, i < k; scalars[2k] = <w, w>
+ *   GS_UPDATE      k = 1..cap-1, nvec = k+1: w <- (w - sum_i coef[i] V_i) * alpha
+ *   BASIS_AXPY     k = 1..cap-1, nvec = k+1: w <- beta * w + sum_i coef[i] V_i (beta = 0: w is not read; coef[i] = 0: V_i is not read);
+ *                  want_norm: scalars[0] = ||result||^2
+ *   GS_UPDATE_DEV  k = 1..min(32, cap-1), nvec = k+1: GS_UPDATE by the pipelined solver's kernel; coef and alpha are first put where its
+ *                  small-algebra kernel leaves coefficients and scale on the device
+ *   GMRES_COEF     k = 1..min(32, cap-1), no vectors: the pipelined solver's small-algebra kernel for columns j = 0..k-1 in sequence on the
+ *                  handle's device block.  coef_host = the reduced rows of every column one after the other, column j in the order of
+ *                  MULTIDOT_GRAM with j+1 vectors (2j+3 numbers); beta = norm of the start residual.  scalars: per column k+3 numbers
+ *                  [coef[0..k) (the first j+1 are the column's), scale = 1/hn, residual estimate, hn], then the triangular factor the Givens
+ *                  rotations have made of the Hessenberg matrix, column c at [c*(k+1), (c+1)*(k+1)), then the rotated right-hand side
+ *                  g[0..k]: k*(k+3) + k*(k+1) + k+1 numbers in all.
+ * want_norm != 0 on another operation: KSFD_EINVAL. */
+enum { KSFD_KOP_LINCOMB = 0, KSFD_KOP_MULTIDOT = 1, KSFD_KOP_MULTIDOT_GRAM = 2, KSFD_KOP_GS_UPDATE = 3, KSFD_KOP_BASIS_AXPY = 4,
+       KSFD_KOP_GS_UPDATE_DEV = 5, KSFD_KOP_GMRES_COEF = 6 };
+int ksfd_krylov_op(ksfd_handle *h, int32_t op, int32_t k, int32_t want_norm, const double *coef_host, double alpha, double beta,
+                   const double *vecs_host, double *out_vecs_host, double *scalars_out, int32_t layout);
 /* ksfd_bench_kernel classes beyond the profile's kernel classes: the rotation kernel on 31 -> 11 vectors in one pass, and the same
  * rotation composed from 11 basis combinations of 31 vectors (out of place); one factorization of the banded direct solver (assembly
  * and the read-back of info included, at the shift of the last ksfd_banded_apply or pc_type 6 attempt) and one of its solves */

@@ -541,16 +541,42 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
 // extrapolated estimate says "this one converges"), so the GPU never idles and at most one iteration is wasted.
 // Pays when an iteration is latency-bound: small grids, many slab ranks.  Unpreconditioned, frozen Jacobian only.
 // ------------------------------------------------------------------------------------------------
+// the device block of the small algebra (h->gm_dev, sized by ksfd_create for restart_alloc columns; handle.hip.h has the layout)
+struct GmDev { double *G, *H, *cs, *sn, *g, *coef, *scale, *mon; int ld; };
+static GmDev gm_dev_block(const ksfd_handle *h)
+{
+    GmDev D;
+    const int m = h->restart_alloc;
+    D.ld = m + 1;
+    D.G = h->gm_dev; D.H = D.G + (size_t)D.ld * D.ld; D.cs = D.H + (size_t)D.ld * m; D.sn = D.cs + m;
+    D.g = D.sn + m; D.coef = D.g + D.ld; D.scale = D.coef + KSFD_MAXDOT; D.mon = D.scale + 1;
+    return D;
+}
+// small algebra of column j on the device (k_gmres_coef): reads the reduced rows in h->dres
+static void launch_gmres_coef(ksfd_handle *h, const GmDev &D, int j, double beta)
+{
+    hipLaunchKernelGGL(k_gmres_coef, dim3(1), dim3(64), 0, h->st, j, h->restart_alloc, beta, (const double *)h->dres, D.G, D.H, D.cs, D.sn, D.g, D.coef, D.scale, D.mon);
+}
+// w = (w - sum_{i<k} coef[i] V_i) * (*scale) with coefficients and scale in device memory (k <= KSFD_ASYNC_MAXK)
+static void launch_gs_update_dev(ksfd_handle *h, double *w, const double *V, int k, const double *coef, const double *scale)
+{
+    Scope sc(h, KC_GSUPDATE, vbytes(h, k + 2));
+    KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update_dev<KB, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, V, h->vlen, k, coef, scale)));
+}
+
 static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x, const ksfd_step_opts *o, LinStats *ls)
 {
     rec_reset(h);
-    const int m = std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc);
+    // Cycle length: what the kernels of an iteration hold, whatever the basis has room for.  k_multidot_gram / k_gs_update_dev stop at the
+    // top of the KB ladder (32 vectors), k_gmres_coef keeps its coefficients in KSFD_MAXDOT slots: a longer ksp_restart runs as cycles of
+    // KSFD_ASYNC_MAXK (gmres() goes on classically and in chunks beyond that length; there is no such path here).
+    const int m = std::min(std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc), KSFD_ASYNC_MAXK);
     const int maxit = o->ksp_max_it > 0 ? o->ksp_max_it : 2000;
     const int64_t vs = h->vlen;
     const int ld = h->restart_alloc + 1;
     double *V = h->V;
-    double *dG = h->gm_dev, *dH = dG + (size_t)ld * ld, *dcs = dH + (size_t)ld * h->restart_alloc, *dsn = dcs + h->restart_alloc,
-           *dg = dsn + h->restart_alloc, *dcoef = dg + ld, *dscale = dcoef + KSFD_MAXDOT, *dmon = dscale + 1;
+    const GmDev D = gm_dev_block(h);
+    double *dH = D.H, *dg = D.g, *dmon = D.mon;
     double *hmon = h->gm_host, *hH = hmon + 2 * ld, *hg = hH + (size_t)ld * h->restart_alloc;
     int rc;
     if ((rc = op_multidot(h, b, V, 0))) return rc;
@@ -604,11 +630,8 @@ static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x,
                 hipLaunchKernelGGL(k_reduce_rows, dim3(2 * k + 1), dim3(KSFD_BLOCK), 0, h->st, (const double *)h->part, nb, 0, h->dres);
             }
             if (h->ring && h->tr->allreduce(h->dres, 2 * k + 1, 0, h->st)) return fail(h, KSFD_ECOMM, "allreduce failed: %s", h->tr->error().c_str());
-            hipLaunchKernelGGL(k_gmres_coef, dim3(1), dim3(64), 0, h->st, j, h->restart_alloc, beta, (const double *)h->dres, dG, dH, dcs, dsn, dg, dcoef, dscale, dmon);
-            {
-                Scope sc(h, KC_GSUPDATE, vbytes(h, k + 2));
-                KB_DISPATCH(k, VW_DISPATCH(h, hipLaunchKernelGGL((k_gs_update_dev<KB, VW>), vgridw(h, VW), dim3(KSFD_BLOCK), 0, h->st, h->kv, w, (const double *)V, h->vlen, k, (const double *)dcoef, (const double *)dscale)));
-            }
+            launch_gmres_coef(h, D, j, beta);
+            launch_gs_update_dev(h, w, V, k, D.coef, D.scale);
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(hmon + 2 * j, dmon + 2 * j, 2 * sizeof(double), hipMemcpyDeviceToHost, h->st));
             HIPCHK(h, hipEventRecord(h->gm_ev[j], h->st));

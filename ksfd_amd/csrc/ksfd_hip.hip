@@ -842,6 +842,90 @@ extern "C" int ksfd_basis_rotate(ksfd_handle *h, int32_t nin, int32_t nout, cons
         if ((rc = download(h, h->V + (int64_t)i * h->vlen, layout, vout + (int64_t)i * nl))) return rc;
     return KSFD_OK;
 }
+// Parity/test entry of the Krylov vector kernels (include/ksfd_hip.h has the contract of every op).  Everything goes through the
+// wrappers the solvers call (op_lincomb, op_multidot, op_multidot_gram, op_gs_update, op_basis_axpy, launch_gs_update_dev,
+// launch_gmres_coef), in the Krylov basis V and the pipelined solver's device block, so dispatch, chunking and reduce_rows are what a
+// stage solve runs.
+extern "C" int ksfd_krylov_op(ksfd_handle *h, int32_t op, int32_t k, int32_t want_norm, const double *coef, double alpha, double beta,
+                              const double *vecs, double *out_vecs, double *scalars, int32_t layout)
+{
+    if (!h) return KSFD_EINVAL;
+    if (layout < 0 || layout > 2) return fail(h, KSFD_EINVAL, "bad layout %d", layout);
+    const int cap = h->restart_alloc + 1;                  // ksfd_basis_capacity
+    const int kdev = std::min(KSFD_ASYNC_MAXK, h->restart_alloc);
+    int kmin = 1, kmax = 0, nvec = 0, nscal = 0;
+    bool need_coef = true;
+    switch (op) {
+    case KSFD_KOP_LINCOMB: kmax = std::min(6, cap); nvec = k; nscal = want_norm ? 1 : 0; break;
+    case KSFD_KOP_MULTIDOT: kmin = 0; kmax = cap - 1; nvec = k + 1; nscal = k + 1; need_coef = false; break;
+    case KSFD_KOP_MULTIDOT_GRAM: kmax = std::min(32, cap - 1); nvec = k + 1; nscal = 2 * k + 1; need_coef = false; break;
+    case KSFD_KOP_GS_UPDATE: kmax = cap - 1; nvec = k + 1; break;
+    case KSFD_KOP_BASIS_AXPY: kmax = cap - 1; nvec = k + 1; nscal = want_norm ? 1 : 0; break;
+    case KSFD_KOP_GS_UPDATE_DEV: kmax = kdev; nvec = k + 1; break;
+    case KSFD_KOP_GMRES_COEF: kmax = kdev; nvec = 0; nscal = 1; break;
+    default: return fail(h, KSFD_EINVAL, "krylov_op: unknown operation %d", (int)op);
+    }
+    if (k < kmin || k > kmax) return fail(h, KSFD_EINVAL, "krylov_op %d: k = %d outside %d .. %d (basis capacity %d)", (int)op, (int)k, kmin, kmax, cap);
+    if ((need_coef && !coef) || (nvec && (!vecs || !out_vecs)) || (nscal && !scalars)) return fail(h, KSFD_EINVAL, "krylov_op %d: missing buffer", (int)op);
+    if (want_norm && op != KSFD_KOP_LINCOMB && op != KSFD_KOP_BASIS_AXPY) return fail(h, KSFD_EINVAL, "krylov_op %d has no norm epilogue", (int)op);
+    hipSetDevice(h->device);
+    h->dr.valid = false;
+    rec_reset(h);
+    int rc;
+    const GmDev D = gm_dev_block(h);
+    if (op == KSFD_KOP_GMRES_COEF) {
+        // columns j = 0 .. k-1 in sequence; the caller's rows stand in for what k_reduce_rows leaves in h->dres
+        const double *row = coef;
+        double *so = scalars;
+        HIPCHK(h, hipMemsetAsync(D.coef, 0, sizeof(double) * KSFD_MAXDOT, h->st));        // what no column writes comes back as zero
+        HIPCHK(h, hipMemsetAsync(D.H, 0, sizeof(double) * (size_t)D.ld * k, h->st));
+        for (int j = 0; j < k; j++) {
+            const int nrow = 2 * (j + 1) + 1;
+            HIPCHK(h, hipMemcpyAsync(h->dres, row, sizeof(double) * nrow, hipMemcpyHostToDevice, h->st));
+            launch_gmres_coef(h, D, j, beta);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(so, D.coef, sizeof(double) * k, hipMemcpyDeviceToHost, h->st));
+            HIPCHK(h, hipMemcpyAsync(so + k, D.scale, sizeof(double), hipMemcpyDeviceToHost, h->st));
+            HIPCHK(h, hipMemcpyAsync(so + k + 1, D.mon + 2 * j, 2 * sizeof(double), hipMemcpyDeviceToHost, h->st));
+            HIPCHK(h, hipStreamSynchronize(h->st));
+            row += nrow; so += k + 3;
+        }
+        for (int c = 0; c < k; c++) HIPCHK(h, hipMemcpyAsync(so + (size_t)c * (k + 1), D.H + (size_t)D.ld * c, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipMemcpyAsync(so + (size_t)k * (k + 1), D.g, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
+        return KSFD_OK;
+    }
+    const int64_t nl = (int64_t)h->G.F * h->G.nloc, vs = h->vlen;
+    for (int i = 0; i < nvec; i++) {
+        if ((rc = upload(h, vecs + (int64_t)i * nl, layout, h->V + (int64_t)i * vs))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->st));            // the staging buffer of upload() is reused by the next vector
+    }
+    double *const w = h->V + (int64_t)k * vs;              // where the solvers have the new vector: behind the k basis vectors
+    switch (op) {
+    case KSFD_KOP_LINCOMB: {
+        const double *xs[6];
+        for (int t = 0; t < k; t++) xs[t] = h->V + (int64_t)t * vs;
+        rc = op_lincomb(h, k, xs, coef, h->V, want_norm != 0);       // out aliases input 0
+    } break;
+    case KSFD_KOP_MULTIDOT: rc = op_multidot(h, w, h->V, k); break;
+    case KSFD_KOP_MULTIDOT_GRAM: rc = op_multidot_gram(h, w, h->V, k); break;
+    case KSFD_KOP_GS_UPDATE: rc = op_gs_update(h, w, h->V, k, coef, alpha); break;
+    case KSFD_KOP_BASIS_AXPY: rc = op_basis_axpy(h, w, h->V, k, coef, beta, want_norm != 0); break;
+    default: {                                             // KSFD_KOP_GS_UPDATE_DEV: coefficients and scale where k_gmres_coef leaves them
+        HIPCHK(h, hipMemcpyAsync(D.coef, coef, sizeof(double) * k, hipMemcpyHostToDevice, h->st));
+        HIPCHK(h, hipMemcpyAsync(D.scale, &alpha, sizeof(double), hipMemcpyHostToDevice, h->st));
+        launch_gs_update_dev(h, w, h->V, k, D.coef, D.scale);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamSynchronize(h->st));            // coef / alpha are the caller's pageable memory
+        rc = KSFD_OK;
+    } break;
+    }
+    if (rc) return rc;
+    for (int i = 0; i < nscal; i++) scalars[i] = h->hres[i];
+    for (int i = 0; i < nvec; i++)                         // every uploaded slot comes back: what the operation does not write, as uploaded
+        if ((rc = download(h, h->V + (int64_t)i * vs, layout, out_vecs + (int64_t)i * nl))) return rc;
+    return KSFD_OK;
+}
 extern "C" int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enable)
 {
     if (!h) return KSFD_EINVAL;

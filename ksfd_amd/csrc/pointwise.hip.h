@@ -574,7 +574,11 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_to_host_layout(KGeom G, int layo
 //   c = d + (I - G) d ,  hn^2 = ww - 2 c.d + c.G c     (CGS2 with the second projection done algebraically)
 //   Hessenberg column [c; hn] -> previous Givens rotations -> new rotation -> residual estimate |g_{j+1}|
 // Outputs: coef[0..k) and scale = 1/hn for the fused update kernel, mon[2j] = residual estimate, mon[2j+1] = hn.
-// One thread: k <= 32, i.e. < 3k FMAs.
+// One thread: k <= KSFD_ASYNC_MAXK = 32 (c[] below and the coef block of the handle have KSFD_MAXDOT slots; gmres_async clamps its cycles to
+// it), i.e. < 3k^2 FMAs.
+#define KSFD_ASYNC_MAXK 32
+static_assert(KSFD_ASYNC_MAXK <= KSFD_MAXDOT, "k_gmres_coef keeps k coefficients in KSFD_MAXDOT slots");
+static_assert(KSFD_ASYNC_MAXK <= 32, "k_multidot_gram and k_gs_update_dev are instantiated for at most 32 basis vectors (KB_DISPATCH)");
 __global__ void k_gmres_coef(int j, int m, double beta, const double *__restrict__ dres, double *__restrict__ Gm,
                              double *__restrict__ H, double *__restrict__ cs, double *__restrict__ sn,
                              double *__restrict__ g, double *__restrict__ coef, double *__restrict__ scale,

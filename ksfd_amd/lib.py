@@ -72,6 +72,9 @@ class DeflationStats(C.Structure):
 
 ROT_MAXIN, ROT_MAXOUT = 121, 18     # KSFD_ROT_MAXIN / KSFD_ROT_MAXOUT: limits of the basis rotation kernel
 BENCH_ROTATE, BENCH_ROTATE_COMPOSED = 100, 101      # ksfd_bench_kernel: one-pass rotation 31 -> 11 vectors / 11 basis combinations
+# operations of ksfd_krylov_op (KSFD_KOP_*), and the longest cycle of the pipelined solver (KSFD_ASYNC_MAXK)
+KOP_LINCOMB, KOP_MULTIDOT, KOP_MULTIDOT_GRAM, KOP_GS_UPDATE, KOP_BASIS_AXPY, KOP_GS_UPDATE_DEV, KOP_GMRES_COEF = range(7)
+ASYNC_MAXK = 32
 BENCH_BAND_FACTOR, BENCH_BAND_SOLVE = 102, 103      # ... one factorization (assembly included) / one solve of the banded direct solver
 
 _lib = None
@@ -85,7 +88,7 @@ ABI_SYMBOLS = [
     'ksfd_default_step_opts', 'ksfd_step', 'ksfd_get_last_error_vector', 'ksfd_set_profiling',
     'ksfd_get_profile', 'ksfd_synchronize', 'ksfd_bench_kernel', 'ksfd_set_tuning', 'ksfd_set_mg_params', 'ksfd_set_poly_params',
     'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply', 'ksfd_banded_apply',
-    'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity',
+    'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity', 'ksfd_krylov_op',
 ]
 
 
@@ -155,6 +158,7 @@ def load():
     L.ksfd_basis_capacity.argtypes = [vp]
     L.ksfd_basis_capacity.restype = C.c_int32
     L.ksfd_basis_rotate.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32]
+    L.ksfd_krylov_op.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, C.c_double, C.c_double, dp, dp, dp, C.c_int32]
     _lib = L
     return L
 
@@ -428,6 +432,36 @@ class KSFDHip:
         out = np.empty((nin, self.nlocal))
         self._chk(self.L.ksfd_basis_rotate(self.h, nin, nout, _dp(P), _dp(vin), _dp(out), layout))
         return out
+
+    def krylov_op(self, op, k, vecs=None, coef=None, alpha=1.0, beta=0.0, want_norm=False, layout=SOA):
+        """one Krylov vector kernel through the solvers' launch wrappers (test entry, ksfd_krylov_op): vecs (nvec, nlocal) with the basis
+        in rows 0..k-1 and w in row k (LINCOMB: its k inputs); returns (all nvec rows as the device left them, scalars).  KOP_GMRES_COEF:
+        coef = the reduced rows of columns 0..k-1 one after the other, no vectors; returns (None, scalars)."""
+        k = int(k)
+        if op == KOP_GMRES_COEF:
+            rows = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+            if k >= 0 and rows.size != k * k + 2 * k:
+                raise ValueError('expected %d reduced numbers, got %d' % (k * k + 2 * k, rows.size))
+            sc = np.full(max(k, 0) * (k + 3) + max(k, 0) * (k + 1) + k + 1 + 1, np.nan)
+            self._chk(self.L.ksfd_krylov_op(self.h, op, k, 0, _dp(rows), float(alpha), float(beta), None, None, _dp(sc), layout))
+            return None, sc[:-1]
+        vecs = np.ascontiguousarray(vecs, dtype=np.float64)
+        if vecs.ndim != 2 or vecs.shape[1] != self.nlocal:
+            raise ValueError('expected vecs of shape (nvec, %d), got %r' % (self.nlocal, vecs.shape))
+        nvec = k if op == KOP_LINCOMB else k + 1
+        cap = self.basis_capacity()
+        kmax = {KOP_LINCOMB: min(6, cap), KOP_MULTIDOT: cap - 1, KOP_MULTIDOT_GRAM: min(32, cap - 1), KOP_GS_UPDATE: cap - 1,
+                KOP_BASIS_AXPY: cap - 1, KOP_GS_UPDATE_DEV: min(ASYNC_MAXK, cap - 1)}.get(op, -1)
+        if (0 if op == KOP_MULTIDOT else 1) <= k <= kmax and vecs.shape[0] != nvec:      # a k the library takes: it will read nvec vectors
+            raise ValueError('operation %d with k = %d takes %d vectors, got %d' % (op, k, nvec, vecs.shape[0]))
+        c = np.ascontiguousarray(coef if coef is not None else np.zeros(max(k, 1)), dtype=np.float64).reshape(-1)
+        if c.size < k:
+            raise ValueError('expected %d coefficients, got %d' % (k, c.size))
+        out = np.empty_like(vecs)
+        sc = np.full(2 * max(k, 0) + 2, np.nan)
+        self._chk(self.L.ksfd_krylov_op(self.h, op, k, int(bool(want_norm)), _dp(c), float(alpha), float(beta), _dp(vecs), _dp(out), _dp(sc), layout))
+        n = {KOP_MULTIDOT: k + 1, KOP_MULTIDOT_GRAM: 2 * k + 1}.get(op, 1 if want_norm else 0)
+        return out, sc[:n]
 
     def set_spectral_params(self, from_stiffness=0.0, enable=-1):
         self._chk(self.L.ksfd_set_spectral_params(self.h, float(from_stiffness), int(enable)))
