@@ -26,6 +26,7 @@ extern "C" {
 #endif
 
 #define KSFD_DIRECT_MAX 32768  /* largest F * local points the direct solver (pc_type 5) takes: 8 * 32768^2 B = 8.6 GB of dense factors */
+#define KSFD_MG_DIRECT_MAX 2048   /* largest F * points of a level the direct coarse solver of the V cycle takes (32 MB inverse) */
 #define KSFD_MAX_LIG 12  /* ligand fields after the reference's fourier_series() expansion (KSFD/ksfdligand.py:315-388 has no cap;
                           * 12 = the dispatch width of the kernels, params.h: KSFD_MAXL) */
 
@@ -126,7 +127,8 @@ typedef struct ksfd_step_stats {
     int32_t rhs_evals, jvp_evals;
     int32_t pc_used;            /* preconditioners the stage solves of this call ran with, OR of: 1 none, 2 multigrid V cycle,
                                  * 4 Chebyshev polynomial, 8 spectral (constant-coefficient FFT), 16 direct (dense LU, pc_type 5), 32 banded direct
-                                 * (banded LU of the folded 1-D ring, pc_type 6) */
+                                 * (banded LU of the folded 1-D ring, pc_type 6), 64 a V cycle of this call ended in a direct coarse
+                                 * solve (ksfd_set_mg_coarse kind 1; set together with 2) */
     double wrms;                /* error norm of the last attempt */
     double h_used;              /* step actually taken (valid when accepted) */
     double ksp_resid;           /* last relative residual */
@@ -265,6 +267,25 @@ int ksfd_set_tuning(ksfd_handle *h, int32_t use_fused, int32_t yseg_rhs, int32_t
 /* multigrid knobs (<=0 keeps): smoothing sweeps per side, cap on coarsest-grid sweeps, power iterations for the
  * Chebyshev bound, smoothing interval ratio lambda_max/lambda_min, coarsest-grid reduction target */
 int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_max, int32_t power_its, double ratio, double coarse_tol);
+/* Coarse solve of the multigrid V cycle.
+ * kind 0: Chebyshev on the coarsest level (default, bit-for-bit the cycle without this call; max_unknowns is ignored);
+ * kind 1: exact solve: shift*I - J_c assembled from the level's restricted coefficient planes, dense LU, explicit inverse, rebuilt
+ *         once per set-up of the hierarchy and applied in one launch inside the cycle.  A set-up whose factorization meets a zero or
+ *         non-finite pivot runs the Chebyshev solve on that level instead (counted in fallbacks); the step does not fail.
+ * max_unknowns <= 0: the cycle ends on the hierarchy's own coarsest level; > 0: it ends on the FINEST level below level 0
+ * whose F * points <= max_unknowns (levels below it stay allocated and unused).
+ * KSFD_EINVAL, nothing changed: kind 1 on a handle with a halo transport, without a hierarchy, when the chosen level has more than
+ * KSFD_MG_DIRECT_MAX unknowns or no level qualifies, max_unknowns > KSFD_MG_DIRECT_MAX. */
+int ksfd_set_mg_coarse(ksfd_handle *h, int32_t kind, int32_t max_unknowns);
+typedef struct ksfd_mg_coarse_info { int32_t kind, level, nlevels, F; int64_t n[3]; int64_t unknowns;
+                                     int32_t factorizations, solves, fallbacks, reserved; } ksfd_mg_coarse_info;
+/* valid with kind 0 too: describes the level the cycle ends on; the counters run over the life of the handle */
+int ksfd_get_mg_coarse_info(ksfd_handle *h, ksfd_mg_coarse_info *info);
+/* parity/test entry on the level the cycle ends on, at the resident state (single rank).  Host vectors of F * points doubles, SoA of
+ * that level (x fastest, field slowest, no ghosts).  op 0: out = (shift*I - J_c) v by the level's own operator kernels (what the
+ * smoother applies); op 1 (kind 1 only): out = the direct coarse solve of v, through the same set-up and apply wrappers the cycle
+ * calls (KSFD_ELINEAR on a zero or non-finite pivot).  State and step memory untouched. */
+int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double *v_host, double *out_host);
 /* The hierarchy is built for max(shift, floor)*I - J; the floor is searched online by ksfd_step when 1/(gamma h) has fallen
  * below the growth rate of the instability and the iteration count explodes.  Environment KSFD_PC_SIGMA=<x> fixes it
  * instead (0 = no floor) -- an experiment knob, not part of the ABI. */
@@ -359,6 +380,12 @@ int ksfd_krylov_op(ksfd_handle *h, int32_t op, int32_t k, int32_t want_norm, con
 #define KSFD_BENCH_ROTATE_COMPOSED 101
 #define KSFD_BENCH_BAND_FACTOR 102
 #define KSFD_BENCH_BAND_SOLVE 103
+/* exact coarse solve of the V cycle (ksfd_set_mg_coarse kind 1 first), at a shift of 1: one set-up (assembly, factorization with one launch
+ * per panel, inversion, the host wait for the flag), one apply, and for comparison assembly + the two-launches-per-column factorization
+ * of pc_type 5 on the same matrix */
+#define KSFD_BENCH_MGC_SETUP 104
+#define KSFD_BENCH_MGC_APPLY 105
+#define KSFD_BENCH_MGC_FACTOR_COLUMNS 106
 
 #ifdef __cplusplus
 }

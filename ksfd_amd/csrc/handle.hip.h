@@ -71,6 +71,21 @@ struct LUState {
     double shift = 0.0;
 };
 
+// exact solve on the level the V cycle ends on (ksfd_set_mg_coarse; mg_coarse_plan.h, lu.hip.h, mgc_* in lu_host.hip.h).  The buffers are
+// allocated when kind 1 is set and live as long as the handle does; the factors and the inverse are rebuilt by every mg_setup_shift
+// from the level's restricted coefficient planes, so nothing of this joins a checkpoint.
+struct MGCoarse {
+    int kind = 0;                            // 0 Chebyshev on the coarsest level, 1 exact solve
+    int max_unknowns = 0;
+    int level = -1;                          // level the cycle ends on (mg_build: the coarsest)
+    LUState lu;                              // shift*I - J_c and its factors
+    double *inv = nullptr;                   // (shift*I - J_c)^-1, row-major
+    bool ready = false;                      // inv belongs to the set-up in force (false: that set-up fell back to Chebyshev)
+    int info_h = 0;
+    int32_t factorizations = 0, solves = 0, fallbacks = 0;
+    int32_t graph_solves = 0;                // coarse solves inside the captured part of the cycle, counted at every replay
+};
+
 // banded direct solver for 1-D grids, pc_type 6 (banded_plan.h / banded.hip.h / banded_host.hip.h): allocated on first use, factors
 // rebuilt every step attempt; the pivot indices never leave the device
 struct BandState {
@@ -211,6 +226,7 @@ struct ksfd_handle {
 
     LUState lu;
     BandState band;
+    MGCoarse mgc;
 
     // multigrid preconditioner
     std::vector<MGLevel> mg;

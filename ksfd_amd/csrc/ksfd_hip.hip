@@ -21,6 +21,7 @@
 #include "banded.hip.h"
 #include "transport.h"
 #include "step_control.h"
+#include "mg_coarse_plan.h"
 
 #include "handle.hip.h"
 #include "ops.hip.h"
@@ -717,8 +718,10 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
     ksfd_step_stats st;
     memset(&st, 0, sizeof st);
     const StepCounters c0 = stats_begin(h);
+    const int32_t coarse0 = h->mgc.solves;
     const int rc = step_run(h, t, hstep, opts, direct, dr_on, st);
     stats_end(h, c0, st);
+    if (h->mgc.solves != coarse0) st.pc_used |= 64;
     if (stats) *stats = st;
     return rc;
 }
@@ -758,6 +761,81 @@ extern "C" int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_ma
     if (coarse_tol > 0.0) h->mg_coarse_tol = coarse_tol;
     h->mg_use_graph = power_its != -7 && !h->ring;     // power_its = -7: eager launches (debug / A-B timing); slab ranks: collectives inside the cycle
     h->mg_shift = -1.0;
+    return KSFD_OK;
+}
+// level the cycle would end on for (kind, max_unknowns), or -1 (mg_coarse_plan.h)
+static int mg_coarse_choice(const ksfd_handle *h, int32_t kind, int32_t max_unknowns)
+{
+    std::vector<long long> unk;
+    for (const MGLevel &L : h->mg) unk.push_back((long long)L.G.F * L.G.nloc);
+    return ksfd_ctl::mg_coarse_level(unk.data(), h->mg_ok ? (int)unk.size() : 0, kind, max_unknowns, KSFD_MG_DIRECT_MAX);
+}
+extern "C" int ksfd_set_mg_coarse(ksfd_handle *h, int32_t kind, int32_t max_unknowns)
+{
+    if (!h) return KSFD_EINVAL;
+    if (kind != 0 && kind != 1) return fail(h, KSFD_EINVAL, "mg_coarse: kind %d is neither 0 (Chebyshev) nor 1 (exact solve)", (int)kind);
+    if (kind == 1) {
+        if (h->ring) return fail(h, KSFD_EINVAL, "mg_coarse: the exact coarse solve is single rank only (this handle has a halo transport)");
+        if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_coarse: this handle has no multigrid hierarchy");
+        if (max_unknowns > KSFD_MG_DIRECT_MAX) return fail(h, KSFD_EINVAL, "mg_coarse: max_unknowns = %d above KSFD_MG_DIRECT_MAX = %d", (int)max_unknowns, KSFD_MG_DIRECT_MAX);
+    } else if (!h->mg_ok) return KSFD_OK;               // nothing to switch off
+    const int level = mg_coarse_choice(h, kind, max_unknowns);
+    if (level < 0) {
+        const MGLevel &Lc = h->mg.back();
+        return fail(h, KSFD_EINVAL, "mg_coarse: no level below level 0 has at most %d unknowns (the coarsest of %d levels has %lld)",
+                    max_unknowns > 0 ? (int)max_unknowns : KSFD_MG_DIRECT_MAX, (int)h->mg.size(), (long long)Lc.G.F * Lc.G.nloc);
+    }
+    hipSetDevice(h->device);
+    if (kind == 1) { int rc = mgc_alloc(h, level); if (rc) return rc; }      // before anything changes
+    if (kind == h->mgc.kind && level == h->mgc.level) { h->mgc.max_unknowns = kind == 1 ? max_unknowns : 0; return KSFD_OK; }
+    h->mgc.kind = kind; h->mgc.level = level; h->mgc.max_unknowns = kind == 1 ? max_unknowns : 0;
+    h->mgc.ready = false;
+    h->mg_shift = -1.0;                                  // the next V cycle sets the hierarchy up again, and with it captures its graph again
+    if (h->mg_graph) { HIPCHK(h, hipStreamSynchronize(h->st)); hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
+    return KSFD_OK;
+}
+extern "C" int ksfd_get_mg_coarse_info(ksfd_handle *h, ksfd_mg_coarse_info *info)
+{
+    if (!h || !info) return KSFD_EINVAL;
+    memset(info, 0, sizeof *info);
+    if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_coarse: this handle has no multigrid hierarchy");
+    const MGLevel &L = h->mg[mg_end(h)];
+    info->kind = h->mgc.kind; info->level = (int32_t)mg_end(h); info->nlevels = (int32_t)h->mg.size(); info->F = L.G.F;
+    // extents per axis of that level (the 1-D level keeps its extent in nx)
+    info->n[0] = L.G.nx; info->n[1] = L.G.dim >= 2 ? L.G.ny : 1; info->n[2] = L.G.dim >= 3 ? L.G.nz : 1;
+    info->unknowns = (int64_t)L.G.F * L.G.nloc;
+    info->factorizations = h->mgc.factorizations; info->solves = h->mgc.solves; info->fallbacks = h->mgc.fallbacks;
+    return KSFD_OK;
+}
+extern "C" int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double *vh, double *outh)
+{
+    if (!h || !vh || !outh) return KSFD_EINVAL;
+    if (!isfinite(shift)) return fail(h, KSFD_EINVAL, "mg_coarse_apply: non-finite shift");
+    if (op != 0 && op != 1) return fail(h, KSFD_EINVAL, "mg_coarse_apply: op %d is neither 0 (operator) nor 1 (solve)", (int)op);
+    if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_coarse: this handle has no multigrid hierarchy");
+    if (op == 1 && h->mgc.kind != 1) return fail(h, KSFD_EINVAL, "mg_coarse_apply: op 1 needs ksfd_set_mg_coarse(kind 1)");
+    if (h->ring) return fail(h, KSFD_EINVAL, "mg_coarse_apply: single rank only (this handle has a halo transport)");
+    hipSetDevice(h->device);
+    int rc;
+    if ((rc = ensure_coef(h))) return rc;
+    if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
+    MGLevel &L = h->mg[mg_end(h)];                        // never level 0: L.b and L.x are the level's own
+    const size_t nb = sizeof(double) * (size_t)L.G.nloc;
+    for (int f = 0; f < L.G.F; f++)
+        HIPCHK(h, hipMemcpyAsync(L.b + (int64_t)f * L.G.plane + L.kv.off, vh + (int64_t)f * L.G.nloc, nb, hipMemcpyHostToDevice, h->st));
+    if (op == 0) rc = mg_op(h, L, L.b, 1, shift, L.x, nullptr);
+    else {
+        bool ok = false;
+        h->mg_shift = -1.0;                              // the coarse factors now belong to this shift: the next cycle sets up again
+        if ((rc = mgc_setup(h, L, shift, &ok))) return rc;
+        if (!ok) return fail(h, KSFD_ELINEAR, "coarse solve: zero or non-finite pivot in column %d of shift*I - J_c (shift %.6g, %lld unknowns)", h->mgc.info_h - 1, shift, (long long)h->mgc.lu.n);
+        rc = mgc_apply(h, L, L.b, L.x);
+        h->mgc.ready = false;
+    }
+    if (rc) return rc;
+    for (int f = 0; f < L.G.F; f++)
+        HIPCHK(h, hipMemcpyAsync(outh + (int64_t)f * L.G.nloc, L.x + (int64_t)f * L.G.plane + L.kv.off, nb, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     return KSFD_OK;
 }
 extern "C" int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, double mg_threshold)
@@ -1006,6 +1084,14 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         } break;
         case KSFD_BENCH_BAND_FACTOR: r = banded_factor(h, h->band.shift); break;
         case KSFD_BENCH_BAND_SOLVE: r = banded_solve(h, h->Y, h->t3); break;
+        case KSFD_BENCH_MGC_SETUP: { bool ok = false; MGLevel &L = h->mg[mg_end(h)]; r = mgc_setup(h, L, 1.0, &ok); if (!r && !ok) r = fail(h, KSFD_ELINEAR, "bench_kernel: the coarse factorization is flagged"); } break;
+        case KSFD_BENCH_MGC_APPLY: { MGLevel &L = h->mg[mg_end(h)]; r = mgc_apply(h, L, L.b, L.x); } break;
+        case KSFD_BENCH_MGC_FACTOR_COLUMNS: {
+            MGLevel &L = h->mg[mg_end(h)];
+            const LUSys Y{ &L.G, &L.P, L.coef, (long long)L.G.sloc, 0, KC_MG };
+            h->mgc.ready = false;
+            if (!(r = lu_assemble(h, h->mgc.lu, Y, 1.0))) r = lu_factor_blocks(h, h->mgc.lu, KC_MG, false);
+        } break;
         default: r = fail(h, KSFD_EINVAL, "bench_kernel: class %d not benchable", cls);
         }
         by = h->bytes_acc - b0;
@@ -1017,6 +1103,12 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         if ((rc = banded_guard(h))) goto done;
         if (!h->band.valid) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the banded benchmark needs a factorization (ksfd_banded_apply first)"); goto done; }
         if ((rc = ensure_coef(h, true))) goto done;
+    }
+    if (cls >= KSFD_BENCH_MGC_SETUP && cls <= KSFD_BENCH_MGC_FACTOR_COLUMNS) {
+        if (h->mgc.kind != 1 || !h->mg_ok) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the coarse-solve benchmark needs ksfd_set_mg_coarse(kind 1)"); goto done; }
+        if ((rc = ensure_coef(h)) || (!h->mg_coef_valid && (rc = mg_restrict_coefs(h)))) goto done;
+        h->mg_shift = -1.0;                                  // the coarse factors no longer belong to the hierarchy's set-up
+        if (cls == KSFD_BENCH_MGC_APPLY) { bool ok = false; if ((rc = mgc_setup(h, h->mg[mg_end(h)], 1.0, &ok))) goto done; if (!ok) { rc = fail(h, KSFD_ELINEAR, "bench_kernel: the coarse factorization is flagged"); goto done; } }
     }
     if ((rc = halo(h, h->u))) goto done;
     if (h->use_frozen && (cls == KC_JVP || cls == KC_SPECTRAL) && (rc = ensure_coef(h, true))) goto done;

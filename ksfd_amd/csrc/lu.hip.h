@@ -255,3 +255,183 @@ __global__ void __launch_bounds__(KSFD_LU_ROWS) k_lu_bwd(const double *__restric
     for (int c = 0; c < kw; c++) s -= a[(long long)c * n] * x[c];
     z[i] = s;
 }
+
+// ---- exact coarse-level solve of the multigrid V cycle (ksfd_set_mg_coarse kind 1; host side: mgc_setup / mgc_apply in
+// lu_host.hip.h) ----------------------------------------------------------------------------------------------------------------
+// The coarse matrix has at most KSFD_MG_DIRECT_MAX unknowns, so the per-column launch pairs of the factorization above are pure
+// launch latency there.  k_lu_panel factors a whole panel in one launch, k_lu_invert forms the explicit inverse from the factors
+// (applied 20 ... 130 times per step as a preconditioner), k_mgc_gemv applies it in one launch inside the cycle.
+#define KSFD_LU_PANT 1024       // threads of the panel kernel
+#define KSFD_MGC_COLS 16        // identity columns per block of the inversion
+#define KSFD_MGC_ROWS 8         // rows per block of the apply (two per wave)
+
+// Columns [k0, k1) of the factorization in ONE workgroup: per column the pivot search (k_lu_pivot's rule: largest |a_ij|, lowest row on
+// ties; NaN never wins; zero / non-finite pivot sets *info = column + 1 and ends the kernel), the row interchange inside the panel,
+// the scaling below the pivot and the rank-1 update of the panel columns to the right.  The pivot row and the scaled pivot column
+// stay in the LDS for the update; the panel itself (at most 2048 x 64 doubles = 1 MB) streams from L2.  n <= KSFD_MG_DIRECT_MAX.
+__global__ void __launch_bounds__(KSFD_LU_PANT) k_lu_panel(double *A, long long n, long long k0, long long k1,
+                                                           int *__restrict__ piv, int *__restrict__ info)
+{
+    constexpr int NW = KSFD_LU_PANT / KSFD_WAVE;
+    __shared__ double sv[NW];
+    __shared__ int si[NW];
+    __shared__ int pr;
+    __shared__ double prow[KSFD_LU_NB];
+    __shared__ double lcol[KSFD_MG_DIRECT_MAX];
+    if (*info) return;
+    const int t = threadIdx.x;
+    const int tr = t & 255, tc = t >> 8;
+    for (long long j = k0; j < k1; j++) {
+        const double *a = A + j * n;
+        double best = -1.0;
+        int bi = (int)n;
+        for (long long i = j + t; i < n; i += KSFD_LU_PANT) {
+            const double v = fabs(a[i]);
+            if (v > best) { best = v; bi = (int)i; }   // rows ascend per thread: the first maximum stays
+        }
+        for (int o = KSFD_WAVE / 2; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(best, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        }
+        if ((t & (KSFD_WAVE - 1)) == 0) { sv[t / KSFD_WAVE] = best; si[t / KSFD_WAVE] = bi; }
+        __syncthreads();
+        if (t == 0) {
+            for (int q = 1; q < NW; q++)
+                if (sv[q] > best || (sv[q] == best && si[q] < bi)) { best = sv[q]; bi = si[q]; }
+            if (!(best > 0.0) || !isfinite(best) || bi >= n) { *info = (int)j + 1; pr = -1; }
+            else { piv[j] = bi; pr = bi; }
+        }
+        __syncthreads();
+        const long long p = pr;
+        if (p < 0) return;                              // the whole workgroup reads the same pr
+        if (t < k1 - k0) {                              // interchange inside the panel; the pivot row goes to the LDS
+            const long long c = k0 + t;
+            double vj = A[j + c * n];
+            if (p != j) { const double vp = A[p + c * n]; A[j + c * n] = vp; A[p + c * n] = vj; vj = vp; }
+            prow[t] = vj;
+        }
+        __syncthreads();
+        const double ajj = prow[j - k0];
+        for (long long i = j + 1 + t; i < n; i += KSFD_LU_PANT) {
+            const double l = A[i + j * n] / ajj;
+            A[i + j * n] = l;
+            lcol[i - j - 1] = l;
+        }
+        __syncthreads();
+        // a_ic -= l_i a_jc: 256 row lanes x 4 column lanes, so a narrow remainder of the panel still fills the workgroup
+        for (long long i = j + 1 + tr; i < n; i += 256) {
+            const double l = lcol[i - j - 1];
+            for (long long c = j + 1 + tc; c < k1; c += 4) A[i + c * n] -= l * prow[c - k0];
+        }
+        __syncthreads();
+    }
+}
+
+// X = A^-1, ROW-major (X[i*n + c]), from the factors P A = L U (column-major, lda = n) and the interchanges piv.  Each block owns
+// KSFD_MGC_COLS columns of the identity and runs both substitutions for them in place in its own columns of X: thread (rl, c) = 16 row
+// lanes x 16 columns; block column by block column the 64 x 64 diagonal block is solved in the LDS, then the rows outside it take
+// x_i -= sum_q a_iq x_q (the factors come from L2, the block's columns of X are contiguous 128 B per row).
+// The right-hand side P e_c is a single one: its row is found by walking column c's index through the interchanges.
+__global__ void __launch_bounds__(KSFD_BLOCK) k_lu_invert(const double *__restrict__ A, long long n, const int *__restrict__ piv,
+                                                          double *X)
+{
+    constexpr int NB = KSFD_LU_NB, NC = KSFD_MGC_COLS, NR = KSFD_BLOCK / KSFD_MGC_COLS;
+    __shared__ double D[NB][NB + 1];
+    __shared__ double xb[NB][NC];
+    __shared__ int pos[NC];
+    const int t = threadIdx.x, c = t % NC, rl = t / NC;
+    const long long col = (long long)blockIdx.x * NC + c;
+    const bool live = col < n;
+    if (t < NC) {
+        long long q = (long long)blockIdx.x * NC + t;
+        if (q < n)
+            for (long long j = 0; j < n; j++) {
+                const long long pj = piv[j];
+                if (q == j) q = pj;
+                else if (q == pj) q = j;
+            }
+        pos[t] = (int)q;
+    }
+    __syncthreads();
+    if (live)
+        for (long long i = rl; i < n; i += NR) X[i * n + col] = (i == pos[c]) ? 1.0 : 0.0;
+    __syncthreads();
+    const long long nbk = (n + NB - 1) / NB;
+    // L y = P e_c (unit lower)
+    for (long long kb = 0; kb < nbk; kb++) {
+        const long long k0 = kb * NB;
+        const int kw = (int)min((long long)NB, n - k0);
+        for (int e = t; e < kw * kw; e += KSFD_BLOCK) {
+            const int r = e % kw, q = e / kw;
+            D[r][q] = A[(k0 + r) + (k0 + q) * n];
+        }
+        for (int q = rl; q < kw; q += NR) xb[q][c] = live ? X[(k0 + q) * n + col] : 0.0;
+        __syncthreads();
+        for (int q = 0; q < kw - 1; q++) {
+            const double xq = xb[q][c];
+            for (int r = q + 1 + rl; r < kw; r += NR) xb[r][c] -= D[r][q] * xq;
+            __syncthreads();
+        }
+        if (live) {
+            for (int q = rl; q < kw; q += NR) X[(k0 + q) * n + col] = xb[q][c];
+            for (long long i = k0 + kw + rl; i < n; i += NR) {
+                double s = X[i * n + col];
+                const double *a = A + i + k0 * n;
+                for (int q = 0; q < kw; q++) s -= a[(long long)q * n] * xb[q][c];
+                X[i * n + col] = s;
+            }
+        }
+        __syncthreads();
+    }
+    // U x = y
+    for (long long kb = nbk - 1; kb >= 0; kb--) {
+        const long long k0 = kb * NB;
+        const int kw = (int)min((long long)NB, n - k0);
+        for (int e = t; e < kw * kw; e += KSFD_BLOCK) {
+            const int r = e % kw, q = e / kw;
+            D[r][q] = A[(k0 + r) + (k0 + q) * n];
+        }
+        for (int q = rl; q < kw; q += NR) xb[q][c] = live ? X[(k0 + q) * n + col] : 0.0;
+        __syncthreads();
+        for (int q = kw - 1; q >= 0; q--) {
+            if (rl == 0) xb[q][c] /= D[q][q];
+            __syncthreads();
+            const double xq = xb[q][c];
+            for (int r = rl; r < q; r += NR) xb[r][c] -= D[r][q] * xq;
+            __syncthreads();
+        }
+        if (live) {
+            for (int q = rl; q < kw; q += NR) X[(k0 + q) * n + col] = xb[q][c];
+            for (long long i = rl; i < k0; i += NR) {
+                double s = X[i * n + col];
+                const double *a = A + i + k0 * n;
+                for (int q = 0; q < kw; q++) s -= a[(long long)q * n] * xb[q][c];
+                X[i * n + col] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// x = X b with the row-major inverse X of k_lu_invert: b is gathered from, x scattered to the level's ghosted SoA planes (KLUVec).  The
+// right-hand side goes through the LDS once per block; one wave per row reads it coalesced, every lane sums its columns in ascending
+// order and a butterfly of fixed shape adds the 64 partial sums: no atomics, the same bits on every run.  n <= KSFD_MG_DIRECT_MAX.
+__global__ void __launch_bounds__(KSFD_BLOCK) k_mgc_gemv(const double *__restrict__ X, int n, KLUVec V, const double *__restrict__ b,
+                                                         double *__restrict__ x)
+{
+    __shared__ double bs[KSFD_MG_DIRECT_MAX];
+    for (int q = threadIdx.x; q < n; q += KSFD_BLOCK) bs[q] = b[klu_off(V, q)];
+    __syncthreads();
+    const int lane = threadIdx.x & (KSFD_WAVE - 1), w = threadIdx.x / KSFD_WAVE;
+    constexpr int per_wave = KSFD_MGC_ROWS / (KSFD_BLOCK / KSFD_WAVE);
+    for (int rr = 0; rr < per_wave; rr++) {
+        const int i = blockIdx.x * KSFD_MGC_ROWS + w * per_wave + rr;
+        if (i >= n) break;                              // the same for the whole wave
+        const double *a = X + (long long)i * n;
+        double s = 0.0;
+        for (int q = lane; q < n; q += KSFD_WAVE) s += a[q] * bs[q];
+        for (int o = KSFD_WAVE / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) x[klu_off(V, i)] = s;
+    }
+}

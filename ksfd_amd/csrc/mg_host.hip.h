@@ -5,8 +5,20 @@
 // ------------------------------------------------------------------------------------------------
 // multigrid preconditioner (host side; kernels and rationale in mg.hip.h)
 // ------------------------------------------------------------------------------------------------
+// exact solve on the level the cycle ends on (lu_host.hip.h, after the dense LU it is built from)
+static void mgc_free(ksfd_handle *h);
+static int mgc_setup(ksfd_handle *h, MGLevel &L, double shift, bool *ok);
+static int mgc_apply(ksfd_handle *h, MGLevel &L, const double *b, double *x);
+
+// level the V cycle ends on: the coarsest one unless ksfd_set_mg_coarse chose a finer one for the exact solve
+static inline size_t mg_end(const ksfd_handle *h) { return h->mgc.kind == 1 ? (size_t)h->mgc.level : h->mg.size() - 1; }
+// level l runs the fp32 cycle (the level of an exact coarse solve stays in fp64, like the coarsest level of the Chebyshev cycle)
+static inline bool mg_f32(const ksfd_handle *h, size_t l) { return h->mg[l].f32 && !(h->mgc.kind == 1 && l == (size_t)h->mgc.level); }
+
 static void mg_free(ksfd_handle *h)
 {
+    mgc_free(h);
+    h->mgc = MGCoarse();
     if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
     for (size_t l = 0; l < h->mg.size(); l++) {
         MGLevel &L = h->mg[l];
@@ -55,6 +67,7 @@ static int mg_build(ksfd_handle *h)
         for (int a = 0; a < 3; a++) { P.inv_h[a] *= 0.5; P.inv_h2[a] *= 0.25; }
     }
     h->mg_ok = h->mg.size() >= 2;
+    h->mgc.level = (int)h->mg.size() - 1;
     if (h->ring) h->mg_use_graph = false;           // collectives inside the cycle: keep eager launches
     // fp32 level vectors (mg_vcycle32): 2-D, levels the strip kernel serves, never the coarsest one (its many Chebyshev sweeps
     // stay in fp64 with the kernels they have)
@@ -214,10 +227,19 @@ static int mg_restrict_coefs(ksfd_handle *h)
 static int mg_setup_shift(ksfd_handle *h, double shift)
 {
     int rc;
-    for (size_t l = 0; l < h->mg.size(); l++) {
+    const size_t end = mg_end(h);           // levels below it are not part of the cycle
+    for (size_t l = 0; l <= end; l++) {
         MGLevel &L = h->mg[l];
         const int F = L.G.F;
         int nb = point_blocks(L.G);
+        if (l == end && h->mgc.kind == 1) {
+            // exact solve: no smoother on this level, so no block diagonal, power iteration or ratio estimate -- unless the
+            // factorization is flagged, then this set-up runs the Chebyshev solve here like the default cycle on its coarsest level
+            bool ok = false;
+            if ((rc = mgc_setup(h, L, shift, &ok))) return rc;
+            if (ok) break;
+            h->mgc.fallbacks++;
+        }
         {
             Scope sc(h, KC_MG, 8.0 * (3 + h->P.nlig + F * F) * L.G.nloc);
             NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_blockdiag_inv<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G, L.P, (const double *)L.coef, shift, L.dinv));
@@ -252,7 +274,7 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
         if (v != L.pv) HIPCHK(h, hipMemcpyAsync(L.pv, v, sizeof(double) * (size_t)L.vlen, hipMemcpyDeviceToDevice, h->st));
         L.pv_norm = (nv > 0.0 && nv == nv) ? nv : 0.0;
         L.lam_max = 1.15 * lam;
-        if (l + 1 == h->mg.size()) {
+        if (l == end) {
             int nbr = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 256);
             hipLaunchKernelGGL(k_ratio_est, dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, (long long)L.G.nloc, (const float *)(L.dinv + L.kv.off), shift, h->part);
             if ((rc = reduce_rows(h, 1, nbr, 1))) return rc;
@@ -369,6 +391,7 @@ static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool 
         if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
         hipGraph_t g = nullptr;
         const double b0 = h->bytes_acc;
+        const int32_t s0 = h->mgc.solves;
         HIPCHK(h, hipStreamBeginCapture(h->st, hipStreamCaptureModeThreadLocal));
         h->capturing = true;
         rc = body();
@@ -381,12 +404,15 @@ static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool 
         if (e != hipSuccess) { h->mg_graph = nullptr; return fail(h, KSFD_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
         h->mg_graph_bytes = h->bytes_acc - b0;
         h->bytes_acc = b0;
+        h->mgc.graph_solves = h->mgc.solves - s0;
+        h->mgc.solves = s0;
         h->mg_graph_shift = shift;
         h->mg_graph_x = xkey;
         h->mg_graph_f32 = f32;
     }
     Scope sc(h, KC_MG, h->mg_graph_bytes);
     HIPCHK(h, hipGraphLaunch(h->mg_graph, h->st));
+    h->mgc.solves += h->mgc.graph_solves;
     return KSFD_OK;
 }
 
@@ -394,7 +420,8 @@ static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const double *b, do
 {
     int rc;
     MGLevel &L = h->mg[l];
-    if (l + 1 == h->mg.size()) {
+    if (l == mg_end(h)) {
+        if (h->mgc.kind == 1 && h->mgc.ready) return mgc_apply(h, L, b, x);
         // coarsest grid: Chebyshev over the whole spectrum, enough sweeps for a ~1e-2 reduction
         int sweeps = (int)ceil(0.5 * sqrt(L.ratio) * log(2.0 / h->mg_coarse_tol));
         sweeps = std::min(std::max(sweeps, 4), h->mg_ncoarse);
@@ -451,19 +478,20 @@ static int mg_coarse_correction32(ksfd_handle *h, size_t l, double shift)
     const int F = L.G.F;
     const int nbr = point_blocks(Lc.G);
     const int nbp = point_blocks(L.G);
+    const bool c32 = mg_f32(h, l + 1);
     if ((rc = mg_halo32(h, L, L.r32, F))) return rc;                    // restriction reads fine rows -1 and sloc
     {
-        Scope sc(h, KC_MG, F * (4.0 * L.G.nloc + (Lc.f32 ? 4.0 : 8.0) * Lc.G.nloc));
-        if (Lc.f32) hipLaunchKernelGGL((k_restrict2d<float, float>), dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)L.r32, L.G.plane, L.kv.off, Lc.b32, Lc.G.plane, Lc.kv.off);
+        Scope sc(h, KC_MG, F * (4.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
+        if (c32) hipLaunchKernelGGL((k_restrict2d<float, float>), dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)L.r32, L.G.plane, L.kv.off, Lc.b32, Lc.G.plane, Lc.kv.off);
         else hipLaunchKernelGGL((k_restrict2d<float, double>), dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)L.r32, L.G.plane, L.kv.off, Lc.b, Lc.G.plane, Lc.kv.off);
     }
-    if (Lc.f32) rc = mg_vcycle32(h, l + 1, shift, nullptr, nullptr);
+    if (c32) rc = mg_vcycle32(h, l + 1, shift, nullptr, nullptr);
     else rc = mg_vcycle(h, l + 1, shift, Lc.b, Lc.x);
     if (rc) return rc;
-    if ((rc = Lc.f32 ? mg_halo32(h, Lc, Lc.x32, F) : mg_halo(h, Lc, Lc.x, F))) return rc;      // prolongation reads coarse row sloc_c
+    if ((rc = c32 ? mg_halo32(h, Lc, Lc.x32, F) : mg_halo(h, Lc, Lc.x, F))) return rc;      // prolongation reads coarse row sloc_c
     {
-        Scope sc(h, KC_MG, F * (8.0 * L.G.nloc + (Lc.f32 ? 4.0 : 8.0) * Lc.G.nloc));
-        if (Lc.f32) hipLaunchKernelGGL((k_prolong_add2d<float, float>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)Lc.x32, Lc.G.plane, Lc.kv.off, L.x32, L.G.plane, L.kv.off);
+        Scope sc(h, KC_MG, F * (8.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
+        if (c32) hipLaunchKernelGGL((k_prolong_add2d<float, float>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)Lc.x32, Lc.G.plane, Lc.kv.off, L.x32, L.G.plane, L.kv.off);
         else hipLaunchKernelGGL((k_prolong_add2d<double, float>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const double *)Lc.x, Lc.G.plane, Lc.kv.off, L.x32, L.G.plane, L.kv.off);
     }
     HIPCHK(h, hipGetLastError());

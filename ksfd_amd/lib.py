@@ -21,7 +21,10 @@ OK, EINVAL, EHIP, ENOMEM, ELINEAR, ENAN, EREJECT, ECOMM = range(8)
 KC_RHS, KC_JVP, KC_MULTIDOT, KC_GSUPDATE, KC_LINCOMB, KC_BASISAXPY, KC_FINISH, KC_REDUCE, \
     KC_GFIELD, KC_VELOCITY, KC_MISC, KC_HALO, KC_MG, KC_SPECTRAL = range(14)
 PC_NONE, PC_MULTIGRID, PC_POLYNOMIAL, PC_SPECTRAL, PC_DIRECT, PC_BANDED = 1, 2, 4, 8, 16, 32      # bits of StepStats.pc_used
+PC_MG_COARSE_DIRECT = 64    # ... a V cycle of the call ended in a direct coarse solve (set_mg_coarse kind 1)
 DIRECT_MAX = 32768      # KSFD_DIRECT_MAX: largest F * local points of the direct solver (pc_type 5)
+MG_DIRECT_MAX = 2048    # KSFD_MG_DIRECT_MAX: largest F * points of a level the direct coarse solver of the V cycle takes
+MG_COARSE_CHEB, MG_COARSE_LU = 0, 1      # kind of set_mg_coarse
 
 
 class KSFDError(RuntimeError):
@@ -70,11 +73,18 @@ class DeflationStats(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class MGCoarseInfo(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('level', C.c_int32), ('nlevels', C.c_int32), ('F', C.c_int32), ('n', C.c_int64 * 3),
+                ('unknowns', C.c_int64), ('factorizations', C.c_int32), ('solves', C.c_int32), ('fallbacks', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 ROT_MAXIN, ROT_MAXOUT = 121, 18     # KSFD_ROT_MAXIN / KSFD_ROT_MAXOUT: limits of the basis rotation kernel
 BENCH_ROTATE, BENCH_ROTATE_COMPOSED = 100, 101      # ksfd_bench_kernel: one-pass rotation 31 -> 11 vectors / 11 basis combinations
 # operations of ksfd_krylov_op (KSFD_KOP_*), and the longest cycle of the pipelined solver (KSFD_ASYNC_MAXK)
 KOP_LINCOMB, KOP_MULTIDOT, KOP_MULTIDOT_GRAM, KOP_GS_UPDATE, KOP_BASIS_AXPY, KOP_GS_UPDATE_DEV, KOP_GMRES_COEF = range(7)
 ASYNC_MAXK = 32
+BENCH_MGC_SETUP, BENCH_MGC_APPLY, BENCH_MGC_FACTOR_COLUMNS = 104, 105, 106    # ... set-up / apply of the exact coarse solve, per-column factorization of the same matrix
 BENCH_BAND_FACTOR, BENCH_BAND_SOLVE = 102, 103      # ... one factorization (assembly included) / one solve of the banded direct solver
 
 _lib = None
@@ -89,6 +99,7 @@ ABI_SYMBOLS = [
     'ksfd_get_profile', 'ksfd_synchronize', 'ksfd_bench_kernel', 'ksfd_set_tuning', 'ksfd_set_mg_params', 'ksfd_set_poly_params',
     'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply', 'ksfd_banded_apply',
     'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity', 'ksfd_krylov_op',
+    'ksfd_set_mg_coarse', 'ksfd_get_mg_coarse_info', 'ksfd_mg_coarse_apply',
 ]
 
 
@@ -159,6 +170,9 @@ def load():
     L.ksfd_basis_capacity.restype = C.c_int32
     L.ksfd_basis_rotate.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32]
     L.ksfd_krylov_op.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, C.c_double, C.c_double, dp, dp, dp, C.c_int32]
+    L.ksfd_set_mg_coarse.argtypes = [vp, C.c_int32, C.c_int32]
+    L.ksfd_get_mg_coarse_info.argtypes = [vp, C.POINTER(MGCoarseInfo)]
+    L.ksfd_mg_coarse_apply.argtypes = [vp, C.c_double, C.c_int32, dp, dp]
     _lib = L
     return L
 
@@ -403,6 +417,31 @@ class KSFDHip:
         out = np.empty(self.nlocal)
         v = self._vec(v)
         self._chk(self.L.ksfd_banded_apply(self.h, float(shift), _dp(v), _dp(out), layout))
+        return out
+
+    def set_mg_coarse(self, kind, max_unknowns=0):
+        """Coarse solve of the multigrid V cycle.  kind 0 (MG_COARSE_CHEB): Chebyshev on the coarsest level, the default; 1 (MG_COARSE_LU):
+        exact solve (dense LU + explicit inverse, rebuilt per set-up).  max_unknowns > 0: the cycle ends on the finest level below level 0
+        with at most that many unknowns (<= MG_DIRECT_MAX), else on the coarsest.  KSFDError(EINVAL) leaves the handle as it was."""
+        self._chk(self.L.ksfd_set_mg_coarse(self.h, int(kind), int(max_unknowns)))
+
+    def mg_coarse_info(self):
+        """the level the V cycle ends on and the counters of the exact coarse solve over the life of the handle:
+        dict(kind, level, nlevels, F, n (3 extents), unknowns, factorizations, solves, fallbacks)"""
+        s = MGCoarseInfo()
+        self._chk(self.L.ksfd_get_mg_coarse_info(self.h, C.byref(s)))
+        return dict(kind=s.kind, level=s.level, nlevels=s.nlevels, F=s.F, n=tuple(int(x) for x in s.n), unknowns=int(s.unknowns),
+                    factorizations=s.factorizations, solves=s.solves, fallbacks=s.fallbacks)
+
+    def mg_coarse_apply(self, shift, v, op=1):
+        """on the level the V cycle ends on, at the resident state (test entry): op 0: (shift*I - J_c) v by the level's operator kernels,
+        op 1: the direct coarse solve of v.  v, result: F * points of that level, SoA (x fastest, field slowest)"""
+        n = self.mg_coarse_info()['unknowns']
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if v.size != n:
+            raise ValueError('mg_coarse_apply: vector of %d entries, the level has %d unknowns' % (v.size, n))
+        out = np.empty(n)
+        self._chk(self.L.ksfd_mg_coarse_apply(self.h, float(shift), int(op), _dp(v), _dp(out)))
         return out
 
     def set_deflation(self, keep, carry_stages=False):

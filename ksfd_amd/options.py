@@ -381,6 +381,34 @@ def deflation_from(petsc_args):
     return (DGMRES_EIGEN_DEFAULT if eigen is None else eigen, DGMRES_CARRY_DEFAULT if carry is None else carry)
 
 
+# -ksfd_mg_coarse: coarse solve of the multigrid V cycle (ksfd_set_mg_coarse).  cheb = Chebyshev on the coarsest level, lu = exact solve
+KSFD_MG_COARSE = {'cheb': 0, 'lu': 1}
+MG_COARSE_MAX_LIMIT = 2048      # KSFD_MG_DIRECT_MAX
+
+
+def mg_coarse_from(petsc_args):
+    """(kind, max_unknowns) for KSFDHip.set_mg_coarse from -ksfd_mg_coarse cheb|lu and -ksfd_mg_coarse_max <N>, or None when the list
+    names neither flag (what such a list does today: the handle is left alone)."""
+    a = list(petsc_args)
+    kind, nmax = None, None
+    for i, k in enumerate(a):
+        nxt = a[i + 1] if i + 1 < len(a) else None
+        if k == '-ksfd_mg_coarse':
+            if nxt not in KSFD_MG_COARSE:
+                raise ValueError('-ksfd_mg_coarse must be one of %s, got %s' % ('/'.join(KSFD_MG_COARSE), nxt))
+            kind = KSFD_MG_COARSE[nxt]
+        elif k == '-ksfd_mg_coarse_max':
+            try:
+                nmax = int(nxt)
+            except (TypeError, ValueError):
+                nmax = -1
+            if not 0 <= nmax <= MG_COARSE_MAX_LIMIT:
+                raise ValueError('-ksfd_mg_coarse_max must be an integer 0..%d, got %s' % (MG_COARSE_MAX_LIMIT, nxt))
+    if kind is None and nmax is None:
+        return None
+    return (0 if kind is None else kind, 0 if nmax is None else nmax)
+
+
 def _isnum(s):
     try:
         float(s.split(',')[0])

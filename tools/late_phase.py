@@ -19,6 +19,10 @@ if KSP_TYPE == 'dgmres':
     ks.set_deflation(EIGEN, CARRY)
 if os.environ.get('KSFD_MG_NU'):
     ks.set_mg_params(nu=int(os.environ['KSFD_MG_NU']), ratio=float(os.environ.get('KSFD_MG_RATIO', '0')))
+if os.environ.get('MG_COARSE'):               # cheb | lu | lu:N  (ksfd_set_mg_coarse: exact coarse solve, N = max_unknowns)
+    _kind, _, _max = os.environ['MG_COARSE'].partition(':')
+    ks.set_mg_coarse({'cheb': 0, 'lu': 1}[_kind], int(_max or 0))
+    print('mg_coarse', ks.mg_coarse_info(), flush=True)
 if os.environ.get('KSFD_MG_POWER'):
     ks.set_mg_params(power_its=int(os.environ['KSFD_MG_POWER']))
 import os
@@ -35,5 +39,7 @@ for s in range(nst):
     if rc: print('rc', rc, ks.last_error()); break
 ks.synchronize(); wall = time.perf_counter() - T0
 print('%d steps: t %.5g h %.4g  %.1f its/step  %.1f ms/step  rejections %d' % (s + 1, t, h, its / (s + 1), 1e3 * wall / (s + 1), rej))
+if os.environ.get('MG_COARSE'):
+    print('mg_coarse', ks.mg_coarse_info(), 'pc_used of the last step', st.pc_used)
 if KSP_TYPE == 'dgmres':
     print('dgmres eigen %d carry %d: %d deflated restarts, %d failed true-residual checks' % (EIGEN, CARRY, drs['restarts'], drs['true_resid_fail']))
