@@ -1,6 +1,5 @@
 // libksfd_hip.so -- the handle: device buffers, solver state, error reporting, HIP-event profiling scopes, tableau and physics tables
-// (part of the single translation unit ksfd_hip.hip; included from there in this order:
-//  handle.hip.h, ops.hip.h, mg_host.hip.h, krylov.hip.h)
+// (part of the single translation unit ksfd_hip.hip, first of its host-side headers: the include list there gives the order)
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // kernel classes for the profile
@@ -373,14 +372,4 @@ static int alloc_d(ksfd_handle *h, double **p, int64_t n)
 {
     if (hipMalloc((void **)p, sizeof(double) * (size_t)n) != hipSuccess) return fail(h, KSFD_ENOMEM, "hipMalloc of %lld doubles failed", (long long)n);
     return KSFD_OK;
-}
-
-static bool fused_ok(const ksfd_handle *h)
-{
-    return h->use_fused && h->G.dim == 2 && (h->G.nx % 2 == 0) && h->G.nx >= 4 && h->G.sloc >= 4 && h->P.nlig <= 4;
-}
-// 3-D z-marching strip kernels (k_jvp3d_frozen, k_rhs3d_strip)
-static bool strip3d_ok(const ksfd_handle *h)
-{
-    return h->use_fused && h->G.dim == 3 && (h->G.nx % 2 == 0) && h->G.nx >= 4 && h->P.nlig <= 4;
 }

@@ -1,10 +1,6 @@
 // libksfd_hip.so -- host side of the geometric multigrid preconditioner (kernels and rationale: mg.hip.h)
-// (part of the single translation unit ksfd_hip.hip; included from there in this order:
-//  handle.hip.h, ops.hip.h, spectral_host.hip.h, mg_host.hip.h, krylov.hip.h, lu_host.hip.h)
+// (part of the single translation unit ksfd_hip.hip, after ops.hip.h: the include list there gives the order)
 #pragma once
-// ------------------------------------------------------------------------------------------------
-// multigrid preconditioner (host side; kernels and rationale in mg.hip.h)
-// ------------------------------------------------------------------------------------------------
 // exact solve on the level the cycle ends on (lu_host.hip.h, after the dense LU it is built from)
 static void mgc_free(ksfd_handle *h);
 static int mgc_setup(ksfd_handle *h, MGLevel &L, double shift, bool *ok);
@@ -14,6 +10,15 @@ static int mgc_apply(ksfd_handle *h, MGLevel &L, const double *b, double *x);
 static inline size_t mg_end(const ksfd_handle *h) { return h->mgc.kind == 1 ? (size_t)h->mgc.level : h->mg.size() - 1; }
 // level l runs the fp32 cycle (the level of an exact coarse solve stays in fp64, like the coarsest level of the Chebyshev cycle)
 static inline bool mg_f32(const ksfd_handle *h, size_t l) { return h->mg[l].f32 && !(h->mgc.kind == 1 && l == (size_t)h->mgc.level); }
+
+// The frozen Jacobian action on level L (ops.hip.h: JvpSys, jvp_path).  Level 0 is the handle's grid: booked as its Jacobian actions are,
+// and its fp32 coefficient copy is the handle's.  The levels have no launch of the second-generation 3-D kernel: the strip kernel serves
+static JvpSys mg_sys(const ksfd_handle *h, const MGLevel &L)
+{
+    const bool l0 = &L == &h->mg[0];
+    return { &L.G, &L.P, L.coef, l0 ? (h->poly_fp32 ? h->coef32 : nullptr) : L.coef32, L.dG, l0 ? KC_JVP : KC_MG };
+}
+static JvpPath mg_path(const ksfd_handle *h, const MGLevel &L) { const JvpPath p = jvp_path(h, L.G, h->P.nlig, JVP_NX_LEVEL); return p == JP_LDS3D ? JP_STRIP3D : p; }
 
 static void mg_free(ksfd_handle *h)
 {
@@ -71,10 +76,10 @@ static int mg_build(ksfd_handle *h)
     if (h->ring) h->mg_use_graph = false;           // collectives inside the cycle: keep eager launches
     // fp32 level vectors (mg_vcycle32): 2-D, levels the strip kernel serves, never the coarsest one (its many Chebyshev sweeps
     // stay in fp64 with the kernels they have)
-    if (h->mg_ok && dim == 2 && h->use_fused && nl <= 4) {
+    if (h->mg_ok) {
         for (size_t l = 0; l + 1 < h->mg.size(); l++) {
             MGLevel &L = h->mg[l];
-            if ((L.G.nx % 2) || L.G.nx < 16) break;
+            if (mg_path(h, L) != JP_STRIP2D) break;
             const size_t nb = sizeof(float) * (size_t)L.vlen;
             if (hipMalloc((void **)&L.x32, nb) != hipSuccess || hipMalloc((void **)&L.b32, nb) != hipSuccess ||
                 hipMalloc((void **)&L.r32, nb) != hipSuccess || hipMalloc((void **)&L.d32, nb) != hipSuccess) { (void)hipGetLastError(); break; }
@@ -115,30 +120,20 @@ static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, 
                            coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
 }
 
-// ghost rows of a level vector (np field planes) from the ring neighbours
-static int mg_halo(ksfd_handle *h, MGLevel &L, double *v, int np)
+// ghost rows of a level vector (np field planes) from the ring neighbours.  An fp32 vector travels through the double-typed transport as
+// half as many doubles (nx is even on the levels that have one)
+template <typename T>
+static int mg_halo(ksfd_handle *h, MGLevel &L, T *v, int np)
 {
     if (!h->ring) return KSFD_OK;
-    Scope sc(h, KC_HALO, 4.0 * 8.0 * np * (double)L.G.inner * 2.0);
-    if (h->tr->exchange(v, np, L.G.plane, L.G.inner, L.G.sloc, L.G.ng, h->st)) return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
+    const long long scale = sizeof(double) / sizeof(T);
+    Scope sc(h, KC_HALO, 4.0 * sizeof(T) * np * (double)L.G.inner * 2.0);
+    if (h->tr->exchange(reinterpret_cast<double *>(v), np, L.G.plane / scale, L.G.inner / scale, L.G.sloc, L.G.ng, h->st)) return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
     return KSFD_OK;
 }
 
-// ... of an fp32 level vector: it travels through the double-typed transport as half as many doubles (nx is even on these levels)
-static int mg_halo32(ksfd_handle *h, MGLevel &L, float *v, int np)
-{
-    if (!h->ring) return KSFD_OK;
-    Scope sc(h, KC_HALO, 4.0 * 4.0 * np * (double)L.G.inner * 2.0);
-    if (h->tr->exchange(reinterpret_cast<double *>(v), np, L.G.plane / 2, L.G.inner / 2, L.G.sloc, L.G.ng, h->st)) return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
-    return KSFD_OK;
-}
-
-static bool mg_can_fuse(const ksfd_handle *h, const MGLevel &L)
-{
-    const KGeom &G = L.G;
-    const bool strip3d = G.dim == 3 && h->use_fused && (G.nx % 2 == 0) && G.nx >= 16 && h->P.nlig <= 4;
-    return h->mg_fuse && !strip3d;
-}
+// smoother algebra in the epilogue of the Jacobian action: the 2-D strip kernel and the generic kernel have it
+static bool mg_can_fuse(const ksfd_handle *h, const MGLevel &L) { return h->mg_fuse && mg_path(h, L) != JP_STRIP3D; }
 
 // out = J v | shift v - J v | yadd - (shift v - J v) on level L
 // sm != NULL: modes 5 / 6, smoother algebra in the epilogue (2-D strip kernel and generic kernel only: see mg_can_fuse)
@@ -147,33 +142,23 @@ static int mg_op(ksfd_handle *h, MGLevel &L, const double *v, int mode, double s
 {
     const KGeom &G = L.G;
     if (h->ring) { int rch = mg_halo(h, L, const_cast<double *>(v), G.F); if (rch) return rch; }
-    const int cls = (&L == &h->mg[0]) ? KC_JVP : KC_MG;
+    const JvpSys Y = mg_sys(h, L);
+    const JvpPath path = mg_path(h, L);
     // planes moved: coefficients + v, plus per mode: 1/2: out (+ yadd); 5: yadd, Dinv, r, d; 6: Dinv, rr, x in and out
     const double by = 8.0 * ((3 + h->P.nlig) + G.F + (mode == 5 ? 3.0 * G.F + 0.5 * G.F * G.F : mode == 6 ? 3.0 * G.F + 0.5 * G.F * G.F : G.F + (mode == 2 ? G.F : 0))) * (double)G.nloc;
     const KSmooth S = sm ? *sm : KSmooth{};
-    if (G.dim == 2 && h->use_fused && (G.nx % 2 == 0) && G.nx >= 16 && h->P.nlig <= 4) {
+    if (path == JP_STRIP2D) {
         const KStrips K = strips_for(G, h->yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
-        // level 0 reads the fp32 copy of the coefficient planes when there is one (the V cycle is a preconditioner: see poly_apply)
-        const float *c32 = (&L == &h->mg[0] && h->poly_fp32) ? h->coef32 : nullptr;
-        Scope sc(h, cls, by - (c32 ? 4.0 * (3 + h->P.nlig) * (double)G.nloc : 0.0));
-        if (sm && c32) {
-            NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, float, double, double, double, 1, true>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, c32, v, mode, shift, out, yadd, 0.0, 0.0, S));
-        } else if (sm) {
-            NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, double, double, double, double, 1, true>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, (const double *)L.coef, v, mode, shift, out, yadd, 0.0, 0.0, S));
-        } else if (c32) {
-            NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, float, double, double, double>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, c32, v, mode, shift, out, yadd));
-        } else
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, (const double *)L.coef, v, mode, shift, out, yadd));
-    } else if (G.dim == 3 && h->use_fused && (G.nx % 2 == 0) && G.nx >= 16 && h->P.nlig <= 4) {
-        const K3D K = k3d_for(G, 4, 0, h->zseg, 1024);
-        Scope sc(h, cls, by + 8.0 * G.plane);
-        dg_pass(h, G, L.coef, v, L.dG, -1);
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp3d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, (const double *)L.coef, v, (const double *)L.dG, mode, shift, out, yadd));
+        // fp64 level vectors: level 0 alone reads an fp32 copy of the coefficient planes (the V cycle is a preconditioner: see poly_apply)
+        const float *c32 = Y.cls == KC_JVP ? Y.coef32 : nullptr;
+        Scope sc(h, Y.cls, by - (c32 ? 4.0 * (3 + h->P.nlig) * (double)G.nloc : 0.0));
+        auto launch = [&](auto *C) { sm ? jvp2d_launch<true>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, S, nullptr) : jvp2d_launch<false>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, S, nullptr); };
+        if (c32) launch(c32); else launch(Y.coef);
     } else {
-        Scope sc(h, cls, by + 8.0 * G.plane);
-        dg_pass(h, G, L.coef, v, L.dG, -1);
-        // (on plane_blocks, not point_blocks as op_jvp_frozen has it: both are grid-stride launches)
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, L.P, (const double *)L.coef, v, (const double *)(L.coef + G.plane), (const double *)L.dG, mode, shift, out, yadd, 0.0, 0.0, S));
+        Scope sc(h, Y.cls, by + 8.0 * G.plane);
+        dg_pass(h, Y, v, -1);
+        if (path == JP_STRIP3D) jvp3d_launch<double>(h, Y, k3d_for(G, 4, 0, h->zseg, 1024), v, mode, shift, out, yadd, 0.0, 0.0, nullptr);
+        else jvpgen_launch(h, Y, plane_blocks(G), v, mode, shift, out, yadd, 0.0, 0.0, S);
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
@@ -215,7 +200,7 @@ static int mg_restrict_coefs(ksfd_handle *h)
                 hipLaunchKernelGGL((k_restrict2d<double, float>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
                                    (const double *)Lf.coef, Lf.G.plane, Lf.kv.off, Lc.coef32, Lc.G.plane, Lc.kv.off);
             }
-            if ((rc = mg_halo32(h, Lc, Lc.coef32, np))) return rc;
+            if ((rc = mg_halo(h, Lc, Lc.coef32, np))) return rc;
         }
     }
     HIPCHK(h, hipGetLastError());
@@ -447,23 +432,15 @@ static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const double *b, do
 static int mg_op32(ksfd_handle *h, MGLevel &L, const float *v, int mode, double shift, float *out, const float *yadd, const KSmoothT<float> *sm)
 {
     const KGeom &G = L.G;
-    if (h->ring) { int rch = mg_halo32(h, L, const_cast<float *>(v), G.F); if (rch) return rch; }
-    const int cls = (&L == &h->mg[0]) ? KC_JVP : KC_MG;
-    const float *c32 = (&L == &h->mg[0]) ? (h->poly_fp32 ? h->coef32 : nullptr) : L.coef32;
+    if (h->ring) { int rch = mg_halo(h, L, const_cast<float *>(v), G.F); if (rch) return rch; }
+    const JvpSys Y = mg_sys(h, L);
+    const float *c32 = Y.coef32;                                  // fp32 level vectors: every level reads its fp32 copy where it has one
     // planes moved (in units of 8 B per point): coefficients, v, per mode: 2: yadd + out; 5: yadd, Dinv, r, d; 6: Dinv, rr, x in and out
     const double by = ((c32 ? 4.0 : 8.0) * (3 + h->P.nlig) + 4.0 * G.F + (mode == 2 ? 8.0 * G.F : 12.0 * G.F + 4.0 * G.F * G.F + ((sm && sm->x64) ? 4.0 * G.F : 0.0))) * (double)G.nloc;
     const KStrips K = strips_for(G, h->yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
-    const KSmoothT<float> S = sm ? *sm : KSmoothT<float>{};
-    Scope sc(h, cls, by);
-    if (sm && c32) {
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, float, float, float, float, 1, true, float>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, c32, v, mode, shift, out, yadd, 0.0, 0.0, S));
-    } else if (sm) {
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, double, float, float, float, 1, true, float>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, (const double *)L.coef, v, mode, shift, out, yadd, 0.0, 0.0, S));
-    } else if (c32) {
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, float, float, float, float>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, c32, v, mode, shift, out, yadd));
-    } else {
-        NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, double, float, float, float>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, L.P, K, (const double *)L.coef, v, mode, shift, out, yadd));
-    }
+    Scope sc(h, Y.cls, by);
+    auto launch = [&](auto *C) { sm ? jvp2d_launch<true>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, *sm, nullptr) : jvp2d_launch<false>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, KSmooth{}, nullptr); };
+    if (c32) launch(c32); else launch(Y.coef);
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
 }
@@ -479,7 +456,7 @@ static int mg_coarse_correction32(ksfd_handle *h, size_t l, double shift)
     const int nbr = point_blocks(Lc.G);
     const int nbp = point_blocks(L.G);
     const bool c32 = mg_f32(h, l + 1);
-    if ((rc = mg_halo32(h, L, L.r32, F))) return rc;                    // restriction reads fine rows -1 and sloc
+    if ((rc = mg_halo(h, L, L.r32, F))) return rc;                    // restriction reads fine rows -1 and sloc
     {
         Scope sc(h, KC_MG, F * (4.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
         if (c32) hipLaunchKernelGGL((k_restrict2d<float, float>), dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)L.r32, L.G.plane, L.kv.off, Lc.b32, Lc.G.plane, Lc.kv.off);
@@ -488,7 +465,7 @@ static int mg_coarse_correction32(ksfd_handle *h, size_t l, double shift)
     if (c32) rc = mg_vcycle32(h, l + 1, shift, nullptr, nullptr);
     else rc = mg_vcycle(h, l + 1, shift, Lc.b, Lc.x);
     if (rc) return rc;
-    if ((rc = c32 ? mg_halo32(h, Lc, Lc.x32, F) : mg_halo(h, Lc, Lc.x, F))) return rc;      // prolongation reads coarse row sloc_c
+    if ((rc = c32 ? mg_halo(h, Lc, Lc.x32, F) : mg_halo(h, Lc, Lc.x, F))) return rc;      // prolongation reads coarse row sloc_c
     {
         Scope sc(h, KC_MG, F * (8.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
         if (c32) hipLaunchKernelGGL((k_prolong_add2d<float, float>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)Lc.x32, Lc.G.plane, Lc.kv.off, L.x32, L.G.plane, L.kv.off);

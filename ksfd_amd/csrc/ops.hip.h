@@ -1,6 +1,5 @@
 // libksfd_hip.so -- halo exchange, host-visible reductions, launch geometry, launch wrappers of every kernel class, host<->device layouts
-// (part of the single translation unit ksfd_hip.hip; included from there in this order:
-//  handle.hip.h, ops.hip.h, spectral_host.hip.h, mg_host.hip.h, krylov.hip.h, lu_host.hip.h)
+// (part of the single translation unit ksfd_hip.hip, after handle.hip.h: the include list there gives the order)
 #pragma once
 // ---- halo exchange (DMDA globalToLocal stand-in, KSFD/ksfdsym.py:919-920) -----------------------
 static int halo(ksfd_handle *h, double *vec)
@@ -125,40 +124,63 @@ static K3D k3d_for(const KGeom &G, int rows, int sync, int zseg, long long block
 }
 // rows of y per block of the 3-D strip kernels (K3D).  Measured at 512^3 (bench.py --dim 3, ms per step): 4 rows 110.6, 4 rows with a
 // barrier per plane 107.8, 8 rows 111.9, 8 rows + barrier 115.5 -- so 4 rows marching in step; KSFD_ROWS3D=8 / KSFD_SYNC3D=0 for measurements
-static int rows3d(const ksfd_handle *h, long long ny)
+static int rows3d(const ksfd_handle *h)
 {
     static const int env = getenv("KSFD_ROWS3D") ? atoi(getenv("KSFD_ROWS3D")) : 0;
-    (void)ny;
     return (env == 8 && h->P.nlig == 1) ? 8 : 4;
 }
 static K3D make_k3d(const ksfd_handle *h)
 {
     static const int sync_env = getenv("KSFD_SYNC3D") ? atoi(getenv("KSFD_SYNC3D")) : 1;
-    const int rows = rows3d(h, h->G.ny);
+    const int rows = rows3d(h);
     return k3d_for(h->G, rows, sync_env && (h->G.ny % rows == 0), h->zseg, rows == 8 ? 512 : 1024);
 }
 
-// second-generation 3-D Jacobian action (k_jvp3d_lds: y-neighbours through the LDS, dG on the fly): one or two ligands, ny a multiple of
-// its 8 rows per block; KSFD_J3L=0 keeps the first generation (dG plane pass + k_jvp3d_frozen)
-static bool j3l_ok(ksfd_handle *h)
+// ---- frozen Jacobian action shift*v - J v: where it runs and which kernel serves it ---------------
+// The action is a function of (geometry, physics, coefficient planes, dG scratch plane): the handle's grid and every level of the
+// multigrid hierarchy (mg_host.hip.h: mg_sys) describe themselves this way and share the launch helpers below
+struct JvpSys {
+    const KGeom *G; const KPhys *P;
+    const double *coef;                      // [rho, G, G_rho, G_U..] planes of that grid
+    const float *coef32;                     // their fp32 copy, NULL where there is none
+    double *dG;                              // scratch plane of the dG pass (3-D strip and generic kernels)
+    int cls;                                 // kernel class the launches are booked under
+};
+static JvpSys jvp_sys(const ksfd_handle *h) { return { &h->G, &h->P, h->coef, h->poly_fp32 ? h->coef32 : nullptr, h->dGb, KC_JVP }; }
+
+enum JvpPath { JP_STRIP2D, JP_LDS3D, JP_STRIP3D, JP_GENERIC };     // k_jvp2d_frozen, k_jvp3d_lds, dG pass + k_jvp3d_frozen, dG pass + k_jvp_generic
+// fewest columns the strip kernels serve
+static const int JVP_NX_GRID = 4;         // the handle's grid: what the five-point window of a periodic row needs
+static const int JVP_NX_LEVEL = 16;       // multigrid levels: coarse levels of 8..14 columns should not march 124-column strips
+// The one rule.  use_fused = 0, an odd nx, fewer than min_nx columns, more than 4 ligands or a 1-D grid: generic.  2-D: the strip kernel
+// (4 slow units at least: every level of a hierarchy has them, mg_build).  3-D: the second generation for one or two ligands where ny is
+// a multiple of its 8 rows per block (KSFD_J3L=0 keeps the first generation), else the first-generation strip kernel
+static JvpPath jvp_path(const ksfd_handle *h, const KGeom &G, int nlig, int min_nx)
 {
-    static const int env = getenv("KSFD_J3L") ? atoi(getenv("KSFD_J3L")) : 1;
-    if (!env || !strip3d_ok(h) || h->P.nlig > 2 || h->G.ny % KSFD_J3L_ROWS) return false;
-    if (!h->j3l_attr_set) {
-        hipError_t e = hipSuccess;
-        if (h->P.nlig == 1) {
-            e = hipFuncSetAttribute((const void *)k_jvp3d_lds<1, double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ksfd_j3l_lds_bytes<1>());
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_jvp3d_lds<1, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ksfd_j3l_lds_bytes<1>());
-        } else {
-            e = hipFuncSetAttribute((const void *)k_jvp3d_lds<2, double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ksfd_j3l_lds_bytes<2>());
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_jvp3d_lds<2, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ksfd_j3l_lds_bytes<2>());
-        }
-        h->j3l_attr_set = true;
-        h->j3l_usable = e == hipSuccess;
-        if (e != hipSuccess) hipGetLastError();
-    }
-    return h->j3l_usable;
+    static const int j3l_env = getenv("KSFD_J3L") ? atoi(getenv("KSFD_J3L")) : 1;
+    if (!h->use_fused || G.dim < 2 || (G.nx % 2) || G.nx < min_nx || nlig > 4) return JP_GENERIC;
+    if (G.dim == 2) return G.sloc >= 4 ? JP_STRIP2D : JP_GENERIC;
+    return (j3l_env && nlig <= 2 && G.ny % KSFD_J3L_ROWS == 0) ? JP_LDS3D : JP_STRIP3D;
 }
+// the handle's own grid: strip kernels of the RHS and of the Jacobian action alike (k_rhs2d_fused / k_rhs3d_strip follow the same rule)
+static bool fused_ok(const ksfd_handle *h) { return jvp_path(h, h->G, h->P.nlig, JVP_NX_GRID) == JP_STRIP2D; }
+static bool strip3d_ok(const ksfd_handle *h) { const JvpPath p = jvp_path(h, h->G, h->P.nlig, JVP_NX_GRID); return p == JP_LDS3D || p == JP_STRIP3D; }
+
+// path of the handle's grid.  k_jvp3d_lds (y-neighbours through the LDS, dG on the fly) needs its dynamic LDS size registered, once per
+// handle; where that fails the first generation serves the grid
+static JvpPath grid_path(ksfd_handle *h)
+{
+    const JvpPath p = jvp_path(h, h->G, h->P.nlig, JVP_NX_GRID);
+    if (p == JP_LDS3D && !h->j3l_attr_set) {
+        auto reg = [](const void *k, size_t lds) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; };
+        h->j3l_usable = h->P.nlig == 1 ? reg((const void *)k_jvp3d_lds<1, double>, ksfd_j3l_lds_bytes<1>()) && reg((const void *)k_jvp3d_lds<1, float>, ksfd_j3l_lds_bytes<1>())
+                                       : reg((const void *)k_jvp3d_lds<2, double>, ksfd_j3l_lds_bytes<2>()) && reg((const void *)k_jvp3d_lds<2, float>, ksfd_j3l_lds_bytes<2>());
+        h->j3l_attr_set = true;
+        if (!h->j3l_usable) hipGetLastError();
+    }
+    return (p == JP_LDS3D && !h->j3l_usable) ? JP_STRIP3D : p;
+}
+static bool j3l_ok(ksfd_handle *h) { return grid_path(h) == JP_LDS3D; }
 // (one block per CU: four rounds of blocks at least)
 static K3D make_k3d_lds(const ksfd_handle *h) { return k3d_for(h->G, KSFD_J3L_ROWS, 0, h->zseg, 1024); }
 
@@ -183,14 +205,39 @@ static KSrc src_of(const ksfd_handle *h, int stage)
     return s;
 }
 
-// dG plane of the direction v from the frozen coefficient planes: the pass in front of the 3-D (first generation) and generic
+// dG plane of the direction v from the frozen coefficient planes of Y: the pass in front of the 3-D (first generation) and generic
 // Jacobian-action kernels.  cls < 0: the launch rides in the caller's Scope (multigrid levels charge both kernels as one)
-static void dg_pass(ksfd_handle *h, const KGeom &G, const double *coef, const double *v, double *dG, int cls = KC_GFIELD)
+static void dg_pass(ksfd_handle *h, const JvpSys &Y, const double *v, int cls = KC_GFIELD)
 {
-    auto launch = [&] { NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, coef, v, dG)); };
+    const KGeom &G = *Y.G;
+    auto launch = [&] { NL_DISPATCH(Y.P->nlig, hipLaunchKernelGGL((k_dg_frozen<NL>), dim3(plane_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, Y.coef, v, Y.dG)); };
     if (cls < 0) return launch();
-    Scope sc(h, cls, 8.0 * (2 + h->P.nlig + G.F) * (double)G.plane);
+    Scope sc(h, cls, 8.0 * (2 + Y.P->nlig + G.F) * (double)G.plane);
     launch();
+}
+
+// The one launch of each kernel of the frozen action, on the system Y, inside the caller's Scope.  k_jvp2d_frozen on the strips K.  The storage types of C, v, yadd and out come from the pointers.  Every (types, SMOOTH) combination is a
+// kernel of its own, so the coefficient type and SMOOTH are compile-time choices of the caller (a run-time flag in here would build
+// smoother kernels for the type combinations of the polynomial preconditioner).  sm: KSmooth{} without a smoother
+template <bool SMOOTH, typename TC, typename TV, typename TY, typename TO, typename TS>
+static void jvp2d_launch(ksfd_handle *h, const JvpSys &Y, const KStrips &K, const TC *C, const TV *v, int mode, double shift, TO *out, const TY *yadd, double alpha, double beta, const KSmoothT<TS> &sm, double *normpart)
+{
+    static_assert(SMOOTH || std::is_same<TS, double>::value, "no smoother: pass KSmooth{}");
+    NL_DISPATCH(Y.P->nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, TC, TV, TY, TO, 1, SMOOTH, TS>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st,
+                                                                     *Y.G, *Y.P, K, C, v, mode, shift, out, yadd, alpha, beta, sm, normpart));
+}
+// k_jvp3d_frozen on the blocks K, behind a dg_pass; TO: storage type of out.  8 rows per block exist for one ligand only (rows3d)
+template <typename TO>
+static void jvp3d_launch(ksfd_handle *h, const JvpSys &Y, const K3D &K, const double *v, int mode, double shift, TO *out, const double *yadd, double alpha, double beta, double *normpart)
+{
+    if (K.rows == 8) hipLaunchKernelGGL((k_jvp3d_frozen<1, TO, 8>), dim3(K.nblocks), dim3(8 * KSFD_WAVE), 0, h->st, *Y.G, *Y.P, K, Y.coef, v, (const double *)Y.dG, mode, shift, out, yadd, alpha, beta, normpart);
+    else NL_DISPATCH(Y.P->nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp3d_frozen<NL, TO>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, *Y.G, *Y.P, K, Y.coef, v, (const double *)Y.dG, mode, shift, out, yadd, alpha, beta, normpart));
+}
+// k_jvp_generic behind a dg_pass, as a grid-stride launch of nblocks blocks (point_blocks on the handle's grid, plane_blocks on the
+// multigrid levels).  The kernel reads rho from plane 0 of its `u` argument (already clamped in the coefficient planes) and G from plane 1
+static void jvpgen_launch(ksfd_handle *h, const JvpSys &Y, int nblocks, const double *v, int mode, double shift, double *out, const double *yadd, double alpha, double beta, const KSmooth &sm)
+{
+    NL_DISPATCH(Y.P->nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(nblocks), dim3(KSFD_BLOCK), 0, h->st, *Y.G, *Y.P, Y.coef, v, Y.coef + Y.G->plane, (const double *)Y.dG, mode, shift, out, yadd, alpha, beta, sm));
 }
 
 // Bytes per point a Jacobian action moves, by the storage types of its operands: impl = ncoef coefficient planes + v + out (+ yadd in
@@ -361,54 +408,15 @@ static int ensure_coef(ksfd_handle *h, bool ghosts_done = false)
     return KSFD_OK;
 }
 
-// Jacobian action from the frozen coefficients (see stencil.hip.h, "Frozen-Jacobian path")
-// want_norm (fused 2-D path only): ||out||^2 -> h->hres[0]
-static int op_jvp_frozen(ksfd_handle *h, const double *v, int mode, double shift, double *out,
-                         const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0, bool want_norm = false)
-{
-    const KGeom &G = h->G;
-    const JvpBytes B = jvp_bytes(G, mode, 3 + h->P.nlig), Bdg = jvp_bytes(G, mode, 3);
-    if (fused_ok(h)) {
-        KStrips K = make_strips(h, true);
-        const long long nwaves = strip_waves(h, true);
-        if (want_norm && nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_jvp_frozen: too many waves for the fused norm");
-        {
-            Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
-            NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, K, (const double *)h->coef, v, mode, shift, out, yadd, alpha, beta, KSmooth{}, want_norm ? h->part : (double *)nullptr));
-        }
-        HIPCHK(h, hipGetLastError());
-        return want_norm ? reduce_rows(h, 1, (int)nwaves, 0) : KSFD_OK;
-    } else if (!want_norm && j3l_ok(h)) {
-        K3D K = make_k3d_lds(h);
-        Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
-        j3l_launch<double>(h, K, v, mode, shift, out, yadd, alpha, beta, nullptr);
-    } else if (h->use_fused && G.dim == 3 && (G.nx % 2 == 0) && G.nx >= 4 && h->P.nlig <= 4) {
-        dg_pass(h, G, h->coef, v, h->dGb);
-        K3D K = make_k3d(h);
-        Scope sc(h, KC_JVP, Bdg.impl * (double)G.nloc, Bdg.alg * (double)G.nloc);
-        if (K.rows == 8) hipLaunchKernelGGL((k_jvp3d_frozen<1, double, 8>), dim3(K.nblocks), dim3(8 * KSFD_WAVE), 0, h->st, G, h->P, K, (const double *)h->coef, v, (const double *)h->dGb, mode, shift, out, yadd, alpha, beta);
-        else NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp3d_frozen<NL>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, K, (const double *)h->coef, v, (const double *)h->dGb, mode, shift, out, yadd, alpha, beta));
-    } else {
-        dg_pass(h, G, h->coef, v, h->dGb);
-        Scope sc(h, KC_JVP, Bdg.impl * (double)G.nloc, Bdg.alg * (double)G.nloc);
-        // the generic stencil kernel reads rho from plane 0 of its `u` argument (already clamped in C) and G from C
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jvp_generic<NL>), dim3(point_blocks(G)), dim3(KSFD_BLOCK), 0, h->st, G, h->P, (const double *)h->coef, v, (const double *)(h->coef + G.plane), (const double *)h->dGb, mode, shift, out, yadd, alpha, beta));
-    }
-    HIPCHK(h, hipGetLastError());
-    return KSFD_OK;
-}
-
 // The 2-D strip kernel of the frozen Jacobian action on `frac` of the segments, for any storage types of its operands (fp32
 // coefficient copy / Horner temporaries of the polynomial preconditioner, fp32 residual of the spectral solver)
 template <typename TC, typename TV, typename TY, typename TO>
-static int jvp2d_launch_t(ksfd_handle *h, const KStrips &K, double frac, const TC *C, const TV *v, int mode, double shift,
-                          TO *out, const TY *yadd, double alpha, double beta, double *normpart = nullptr)
+static int jvp2d_launch_t(ksfd_handle *h, const KStrips &K, double frac, const TC *C, const TV *v, int mode, double shift, TO *out, const TY *yadd, double alpha, double beta, double *normpart = nullptr)
 {
     const KGeom &G = h->G;
     const JvpBytes B = jvp_bytes<TC, TV, TY, TO>(G, mode, 3 + h->P.nlig);
     Scope sc(h, KC_JVP, B.impl * (double)G.nloc * frac, B.alg * (double)G.nloc * frac);
-    NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp2d_frozen<NL, TC, TV, TY, TO>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st,
-                                                                     G, h->P, K, C, (const TV *)v, mode, shift, out, yadd, alpha, beta, KSmooth{}, normpart));
+    jvp2d_launch<false>(h, jvp_sys(h), K, C, v, mode, shift, out, yadd, alpha, beta, KSmooth{}, normpart);
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
 }
@@ -429,10 +437,30 @@ static int jvp2d_halo_t(ksfd_handle *h, const TC *C, TV *v, int mode, double shi
     }, launch);
 }
 
+// Jacobian action from the frozen coefficients (see stencil.hip.h, "Frozen-Jacobian path")
+static int op_jvp_frozen(ksfd_handle *h, const double *v, int mode, double shift, double *out, const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0)
+{
+    const KGeom &G = h->G;
+    const JvpSys Y = jvp_sys(h);
+    const JvpBytes B = jvp_bytes(G, mode, 3 + h->P.nlig), Bdg = jvp_bytes(G, mode, 3);
+    const JvpPath path = grid_path(h);
+    if (path == JP_STRIP2D) return jvp2d_launch_t(h, make_strips(h, true), 1.0, Y.coef, v, mode, shift, out, yadd, alpha, beta);
+    if (path == JP_LDS3D) {
+        Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
+        j3l_launch<double>(h, make_k3d_lds(h), v, mode, shift, out, yadd, alpha, beta, nullptr);
+    } else {
+        dg_pass(h, Y, v);
+        Scope sc(h, KC_JVP, Bdg.impl * (double)G.nloc, Bdg.alg * (double)G.nloc);
+        if (path == JP_STRIP3D) jvp3d_launch<double>(h, Y, make_k3d(h), v, mode, shift, out, yadd, alpha, beta, nullptr);
+        else jvpgen_launch(h, Y, point_blocks(G), v, mode, shift, out, yadd, alpha, beta, KSmooth{});
+    }
+    HIPCHK(h, hipGetLastError());
+    return KSFD_OK;
+}
+
 // Jacobian action on a vector whose ghost rows have NOT been exchanged yet: behind the interior rows where the 2-D strip kernel
 // runs with at least 3 segments, else exchange first and op_jvp_frozen (which also serves the 3-D and generic kernels)
-static int op_jvp_frozen_halo(ksfd_handle *h, double *v, int mode, double shift, double *out,
-                              const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0)
+static int op_jvp_frozen_halo(ksfd_handle *h, double *v, int mode, double shift, double *out, const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0)
 {
     if (!h->ring) return op_jvp_frozen(h, v, mode, shift, out, yadd, alpha, beta);
     if (!h->overlap || !fused_ok(h) || make_strips(h, true).nseg < 3 || h->P.nlig > 4) {
@@ -443,32 +471,25 @@ static int op_jvp_frozen_halo(ksfd_handle *h, double *v, int mode, double shift,
 }
 
 // r32 = b - A x stored in fp32 (its only reader is the spectral preconditioner, which works in fp32 anyway) with ||r||^2 in
-// fp64 from the store epilogue -> h->hres[0].  Single rank or slab ranks (2-D), strip kernels.
+// fp64 from the store epilogue -> h->hres[0].  Single rank or slab ranks (2-D: the ghost rows of x travel while the interior segments are
+// computed, the caller has NOT exchanged them), strip kernels.
 static int op_residual32(ksfd_handle *h, const double *x, double shift, const double *b, float *r32)
 {
     const KGeom &G = h->G;
     const long long nwaves = G.dim == 3 ? k3d_waves(h) : strip_waves(h, true);
+    if (nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_residual32: too many waves for the fused norm");
     if (G.dim == 3) {
         // second generation, or: dG plane, then the z-marching Jacobian action in residual mode; fp32 output and the norm in the epilogue
+        const JvpSys Y = jvp_sys(h);
         const bool j3l = j3l_ok(h);
-        if (!j3l) dg_pass(h, G, h->coef, x, h->dGb);
-        if (nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_residual32: too many waves for the fused norm");
+        if (!j3l) dg_pass(h, Y, x);
         // (the second generation charges one more fp64 vector than its operands: kept as it has always been reported)
         const JvpBytes B = j3l ? jvp_bytes<double, double, double, float>(G, 2, 3 + h->P.nlig, 8.0 * G.F) : jvp_bytes<double, double, double, float>(G, 2, 3);
-        const K3D K = j3l ? make_k3d_lds(h) : make_k3d(h);
-        {
-            Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
-            if (j3l) j3l_launch<float>(h, K, x, 2, shift, r32, b, 0.0, 0.0, h->part);
-            else if (K.rows == 8) hipLaunchKernelGGL((k_jvp3d_frozen<1, float, 8>), dim3(K.nblocks), dim3(8 * KSFD_WAVE), 0, h->st, G, h->P, K, (const double *)h->coef, x, (const double *)h->dGb, 2, shift, r32, b, 0.0, 0.0, h->part);
-            else NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_jvp3d_frozen<NL, float>), dim3(K.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, h->P, K, (const double *)h->coef, x, (const double *)h->dGb, 2, shift, r32, b, 0.0, 0.0, h->part));
-        }
-        HIPCHK(h, hipGetLastError());
-        return reduce_rows(h, 1, (int)nwaves, 0);
-    }
-    if (nwaves > part_capacity()) return fail(h, KSFD_EINVAL, "op_residual32: too many waves for the fused norm");
-    // slab ranks: the ghost rows of x travel while the interior segments are computed (the caller has NOT exchanged them)
-    int rc = jvp2d_halo_t<double, double, double, float>(h, (const double *)h->coef, const_cast<double *>(x), 2, shift, r32, b, 0.0, 0.0, h->part);
-    if (rc) return rc;
+        Scope sc(h, KC_JVP, B.impl * (double)G.nloc, B.alg * (double)G.nloc);
+        if (j3l) j3l_launch<float>(h, make_k3d_lds(h), x, 2, shift, r32, b, 0.0, 0.0, h->part);
+        else jvp3d_launch<float>(h, Y, make_k3d(h), x, 2, shift, r32, b, 0.0, 0.0, h->part);
+    } else if (int rc = jvp2d_halo_t(h, h->coef, const_cast<double *>(x), 2, shift, r32, b, 0.0, 0.0, h->part)) return rc;
+    HIPCHK(h, hipGetLastError());
     return reduce_rows(h, 1, (int)nwaves, 0);
 }
 

@@ -438,6 +438,34 @@ def test_multigrid_cycle_with_fp32_level_vectors(shape, nlig):
         assert rel_l2(out['fp32'][1], un) < 5e-6
 
 
+@pytest.mark.parametrize('shape,nlig', [((32, 16), 1)])
+def test_fp32_cycle_without_the_fp32_coefficient_copy(shape, nlig):
+    """tuning bit 9 takes the fp32 copy of the coefficient planes away: level 0 of the fp32 cycle then reads the fp64 planes with fp32
+    level vectors, the one combination of storage types of the 2-D strip kernel that no other test launches.  32x16 is the smallest grid
+    with a level below level 0 (16x8).  Bounds of test_multigrid_cycle_with_fp32_level_vectors: the fp64 cycle to 2e-7, the oracle's LU
+    step to 5e-6, iteration counts within one per stage."""
+    cfg = ProblemConfig.standard(2, shape, L=tuple(0.0025 * n for n in shape), nlig=nlig)
+    rng = np.random.default_rng(41)
+    rho = 9000 + 90 * rng.standard_normal(cfg.N)
+    u = np.concatenate([rho] + [rho * cfg.lig_s[l] / cfg.lig_gamma[l] for l in range(nlig)])
+    h = 10.0
+    out = {}
+    for name, tune in (('fp32', 1 | 512), ('fp64', 1 | 512 | 524288)):
+        k = klib.KSFDHip(cfg)
+        k.set_tuning(use_fused=tune)
+        k.set_state(u)
+        t, hn, st, rc = k.step(0.0, h, klib.default_step_opts(adapt=0, atol=0.01, rtol=1e-6, ksp_rtol=1e-7, pc_type=1))
+        assert st.pc_used & 2
+        out[name] = (st.linear_its, k.get_state())
+        k.close()
+    un, _, _, _ = ko.Oracle(cfg).rosw_step(u, h, 0.01, 1e-6, solver='lu')
+    print('fp32 cycle, no fp32 coefficients: its %d / %d, vs fp64 cycle %.2e, vs LU %.2e' %
+          (out['fp32'][0], out['fp64'][0], rel_l2(out['fp32'][1], out['fp64'][1]), rel_l2(out['fp32'][1], un)))
+    assert abs(out['fp32'][0] - out['fp64'][0]) <= 4, (out['fp32'][0], out['fp64'][0])
+    assert rel_l2(out['fp32'][1], out['fp64'][1]) < 2e-7
+    assert rel_l2(out['fp32'][1], un) < 5e-6
+
+
 @pytest.mark.parametrize('n,h', [(96, 5.0), (384, 50.0), (130, 2.0)])
 def test_multigrid_1d_stiff_step_vs_oracle_lu(n, h):
     """1-D hierarchy (weights 1/4, 1/2, 1/4 / linear interpolation; four of the six option files the reference ships are 1-D)"""
