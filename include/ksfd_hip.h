@@ -286,6 +286,49 @@ int ksfd_get_mg_coarse_info(ksfd_handle *h, ksfd_mg_coarse_info *info);
  * smoother applies); op 1 (kind 1 only): out = the direct coarse solve of v, through the same set-up and apply wrappers the cycle
  * calls (KSFD_ELINEAR on a zero or non-finite pivot).  State and step memory untouched. */
 int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double *v_host, double *out_host);
+/* Parity/test entry of the PARTS of the V cycle, the twin of ksfd_mg_coarse_apply and ksfd_krylov_op: one part of the cycle runs on
+ * host vectors through the wrappers the cycle itself calls (mg_restrict_coefs, mg_setup_shift, mg_launch_restrict / _prolong and their
+ * 2-D storage-type forms, mg_halo, mg_op, mg_op32, mg_dinv_apply, mg_smooth, mg_precond), never through a kernel launch of its own, so a
+ * wrong launch argument shows.  Host vectors are SoA of the level (x fastest, field slowest), OWNED points only: F * points doubles,
+ * points = ksfd_mg_level_info_t.points.  fp32 operands are rounded to float on the host before upload and come back as doubles.
+ * Handles with a halo transport: every call is collective, each rank passes its slab of the level (sloc slow units).
+ * Both calls work at the resident state (its coefficient planes are made and restricted if they are not current) and leave the state and
+ * what the stepper remembers from step to step untouched.  After either call the hierarchy counts as NOT set up: shift forgotten, captured
+ * graph dropped, power-iteration vectors forgotten -- so the next real set-up starts its power iteration cold, as on a fresh handle, and so
+ * does every set-up these calls run themselves: two calls with the same arguments agree bit for bit.
+ * KSFD_EINVAL, nothing touched: no hierarchy, level out of range, a part or variant the level does not have, nu outside 1 .. 5, ratio <= 1,
+ * a missing buffer, a non-finite shift.
+ *
+ * ksfd_mg_level_info: geometry and kernel choice of one level; setup != 0: after a cold set-up at `shift` also lam_max, ratio and the
+ * Chebyshev sweeps mg_vcycle runs on the level the cycle ends on (have_setup = 0 and zeros on a level below the end of the cycle or on
+ * the level of an exact coarse solve).
+ *   path: 0 2-D strip kernel, 2 3-D strip kernel, 3 generic kernel (what mg_path picks)
+ *   f32: the level has fp32 level vectors;  coef32: bit 0 = the operator of the fp64 cycle reads an fp32 coefficient copy (level 0, unless
+ *   tuning bit 9 is set), bit 1 = the level has such a copy (the fp32 cycle reads it);  can_fuse: mg_can_fuse holds
+ *
+ * ksfd_mg_part: `level` is the level the part runs on; transfers run between `level` (fine) and level + 1.
+ *   COEF         out0 = the 3 + nlig coefficient planes the level's operator reads, after ensure_coef + mg_restrict_coefs; out1 (may be
+ *                NULL) = the fp32 copy where info.coef32 bit 1 is set
+ *   RESTRICT     out0 (level + 1) = R in0 (level).  variant 0: fp64 (mg_launch_restrict); 1 (f32 levels): the launch of the fp32 cycle, fine
+ *                fp32 and coarse fp32 where level + 1 runs in fp32, else fp64; 2 (2-D, level + 1 an f32 level): fine fp64, coarse fp32 (the
+ *                launch that makes the fp32 coefficient copy)
+ *   PROLONG_ADD  out0 = in0 (level) + P in1 (level + 1).  variant 0: fp64 (mg_launch_prolong); 1 (f32 levels): fine fp32, coarse as above
+ *   OPERATOR     variant 1: out0 = (shift*I - J_l) in0; 2: out0 = in1 - (shift*I - J_l) in0 (mg_op modes 1, 2); 32 (f32 levels): mode 2 of
+ *                mg_op32 on fp32 vectors
+ *   DINV         out0 = the F*F planes k_blockdiag_inv leaves after mg_setup_shift(shift) (row-major blocks, fp32 values)
+ *   DINV_APPLY   k_dinv_apply with scale 1/nu (nu = 0: 1): out0 = z, out1 = [z2 | rcopy] (2 F points).  variant 0: fp64 in and out;
+ *                1 (f32 levels): fp64 in, fp32 out (entry of the fp32 cycle)
+ *   SMOOTH       out0 = mg_smooth(level, shift, b = in0, x0 = in1 or NULL for the zero guess, nu = 1 .. 5, ratio) after a set-up at shift
+ *   CYCLE        level 0: out0 = mg_precond(shift, in0); variant 0: fp64 level vectors, 1: fp32 level vectors (what ksp_rtol >= 1e-7
+ *                selects in ksfd_step; KSFD_EINVAL where the handle would not run that cycle).  Captured graph or eager launches as the
+ *                handle is set (ksfd_set_mg_params). */
+typedef struct ksfd_mg_level_info_t { int32_t level, nlevels, end_level, F; int64_t n[3]; int64_t sloc, points;
+                                      int32_t path, f32, coef32, can_fuse, have_setup, coarse_sweeps; double lam_max, ratio; } ksfd_mg_level_info_t;
+enum { KSFD_MGP_COEF = 0, KSFD_MGP_RESTRICT = 1, KSFD_MGP_PROLONG_ADD = 2, KSFD_MGP_OPERATOR = 3, KSFD_MGP_DINV = 4, KSFD_MGP_DINV_APPLY = 5,
+       KSFD_MGP_SMOOTH = 6, KSFD_MGP_CYCLE = 7 };
+int ksfd_mg_level_info(ksfd_handle *h, int32_t level, int32_t setup, double shift, ksfd_mg_level_info_t *info);
+int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t variant, int32_t nu, double shift, double ratio,
+                 const double *in0, const double *in1, double *out0, double *out1);
 /* The hierarchy is built for max(shift, floor)*I - J; the floor is searched online by ksfd_step when 1/(gamma h) has fallen
  * below the growth rate of the instability and the iteration count explodes.  Environment KSFD_PC_SIGMA=<x> fixes it
  * instead (0 = no floor) -- an experiment knob, not part of the ABI. */

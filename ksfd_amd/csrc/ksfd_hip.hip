@@ -838,6 +838,206 @@ extern "C" int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, co
     HIPCHK(h, hipStreamSynchronize(h->st));
     return KSFD_OK;
 }
+// ---- parity/test entry of the parts of the V cycle (include/ksfd_hip.h has the contract) ------------------------------------------------
+// host vector (np planes of the level's owned points, SoA) -> a device vector in the level's ghosted layout; ghosts zero.  T = float:
+// rounded on the host
+template <typename T>
+static int mgp_put(ksfd_handle *h, const MGLevel &L, int np, const double *host, T *dev)
+{
+    HIPCHK(h, hipMemsetAsync(dev, 0, sizeof(T) * (size_t)np * L.G.plane, h->st));
+    std::vector<T> tmp((size_t)np * L.G.nloc);
+    for (size_t i = 0; i < tmp.size(); i++) tmp[i] = (T)host[i];
+    for (int f = 0; f < np; f++)
+        HIPCHK(h, hipMemcpyAsync(dev + (int64_t)f * L.G.plane + L.kv.off, tmp.data() + (int64_t)f * L.G.nloc, sizeof(T) * (size_t)L.G.nloc, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return KSFD_OK;
+}
+template <typename T>
+static int mgp_get(ksfd_handle *h, const MGLevel &L, int np, const T *dev, double *host)
+{
+    std::vector<T> tmp((size_t)np * L.G.nloc);
+    for (int f = 0; f < np; f++)
+        HIPCHK(h, hipMemcpyAsync(tmp.data() + (int64_t)f * L.G.nloc, dev + (int64_t)f * L.G.plane + L.kv.off, sizeof(T) * (size_t)L.G.nloc, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    for (size_t i = 0; i < tmp.size(); i++) host[i] = (double)tmp[i];
+    return KSFD_OK;
+}
+// coefficient planes of every level at the resident state; setup: block diagonals and Chebyshev bounds at `shift` from a cold power iteration
+static int mgp_begin(ksfd_handle *h, bool setup, double shift)
+{
+    int rc;
+    if ((rc = ensure_coef(h))) return rc;
+    if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
+    if (setup) {
+        for (MGLevel &L : h->mg) L.pv_norm = 0.0;
+        h->mg_shift = -1.0;
+        if ((rc = mg_setup_shift(h, shift))) return rc;
+    }
+    return KSFD_OK;
+}
+// the hierarchy counts as not set up afterwards: the next real set-up starts cold and captures its graph again
+static void mgp_end(ksfd_handle *h)
+{
+    hipStreamSynchronize(h->st);
+    h->mg_shift = -1.0;
+    h->mg_graph_shift = -1.0;
+    if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
+    for (MGLevel &L : h->mg) L.pv_norm = 0.0;
+    h->mgc.ready = false;
+}
+// the level has a smoother after a set-up: it is part of the cycle, and not the level of an exact solve that succeeded
+static bool mgp_smoothed(const ksfd_handle *h, size_t l) { return l <= mg_end(h) && !(l == mg_end(h) && h->mgc.kind == 1 && h->mgc.ready); }
+
+extern "C" int ksfd_mg_level_info(ksfd_handle *h, int32_t level, int32_t setup, double shift, ksfd_mg_level_info_t *info)
+{
+    if (!h || !info) return KSFD_EINVAL;
+    memset(info, 0, sizeof *info);
+    if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_part: this handle has no multigrid hierarchy");
+    if (level < 0 || level >= (int)h->mg.size()) return fail(h, KSFD_EINVAL, "mg_part: level %d outside 0 .. %d", (int)level, (int)h->mg.size() - 1);
+    if (setup && !isfinite(shift)) return fail(h, KSFD_EINVAL, "mg_part: non-finite shift");
+    hipSetDevice(h->device);
+    const int rc = mgp_begin(h, setup != 0, shift);         // the planes first: the fp32 coefficient copy exists once they are made
+    const MGLevel &L = h->mg[level];
+    info->level = level; info->nlevels = (int32_t)h->mg.size(); info->F = L.G.F; info->end_level = (int32_t)mg_end(h);
+    info->n[0] = L.G.nx; info->n[1] = L.G.dim >= 2 ? L.G.ny : 1; info->n[2] = L.G.dim >= 3 ? L.G.nz : 1;
+    info->sloc = L.G.sloc; info->points = L.G.nloc;
+    info->path = (int32_t)mg_path(h, L);
+    info->f32 = L.f32 ? 1 : 0;
+    const JvpSys Y = mg_sys(h, L);
+    info->coef32 = (Y.coef32 ? 2 : 0) | ((Y.coef32 && Y.cls == KC_JVP && mg_path(h, L) == JP_STRIP2D) ? 1 : 0);
+    info->can_fuse = mg_can_fuse(h, L) ? 1 : 0;
+    if (setup && !rc) {
+        info->have_setup = mgp_smoothed(h, (size_t)level) ? 1 : 0;
+        if (info->have_setup) { info->lam_max = L.lam_max; info->ratio = L.ratio; }
+        if ((size_t)level == mg_end(h) && info->have_setup) info->coarse_sweeps = mg_coarse_sweeps(h, L);
+    }
+    mgp_end(h);
+    return rc;
+}
+
+extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t variant, int32_t nu, double shift, double ratio,
+                            const double *in0, const double *in1, double *out0, double *out1)
+{
+    if (!h) return KSFD_EINVAL;
+    if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_part: this handle has no multigrid hierarchy");
+    const int nlev = (int)h->mg.size();
+    if (level < 0 || level >= nlev) return fail(h, KSFD_EINVAL, "mg_part: level %d outside 0 .. %d", (int)level, nlev - 1);
+    if (!isfinite(shift)) return fail(h, KSFD_EINVAL, "mg_part: non-finite shift");
+    MGLevel &L = h->mg[level];
+    const bool transfer = part == KSFD_MGP_RESTRICT || part == KSFD_MGP_PROLONG_ADD;
+    if (transfer && level + 1 >= nlev) return fail(h, KSFD_EINVAL, "mg_part: level %d has no coarser level", (int)level);
+    MGLevel &Lc = h->mg[transfer ? level + 1 : level];
+    const bool cf32 = transfer && mg_f32(h, (size_t)level + 1);       // the fp32 cycle keeps the coarser level in fp32 too
+    const int F = L.G.F, np = 3 + h->P.nlig;
+    bool setup = false, ok = true, need1 = false, need_o1 = false;
+    switch (part) {
+    case KSFD_MGP_COEF: ok = variant == 0; break;
+    case KSFD_MGP_RESTRICT: ok = variant == 0 || (variant == 1 && L.f32) || (variant == 2 && L.G.dim == 2 && Lc.f32); break;
+    case KSFD_MGP_PROLONG_ADD: ok = variant == 0 || (variant == 1 && L.f32); need1 = true; break;
+    case KSFD_MGP_OPERATOR: ok = variant == 1 || variant == 2 || (variant == 32 && L.f32); need1 = variant != 1; break;
+    case KSFD_MGP_DINV: ok = variant == 0; setup = true; break;
+    case KSFD_MGP_DINV_APPLY: ok = variant == 0 || (variant == 1 && L.f32); setup = true; need_o1 = true; break;
+    case KSFD_MGP_SMOOTH: ok = variant == 0; setup = true; break;
+    case KSFD_MGP_CYCLE: ok = level == 0 && (variant == 0 || variant == 1); setup = true; break;
+    default: return fail(h, KSFD_EINVAL, "mg_part: unknown part %d", (int)part);
+    }
+    if (!ok) return fail(h, KSFD_EINVAL, "mg_part %d: level %d has no variant %d", (int)part, (int)level, (int)variant);
+    if (part == KSFD_MGP_CYCLE && variant == 1 && !(h->mg_fp32 && h->mg[0].f32 && h->mg_nu == 2 && mg_can_fuse(h, h->mg[0])))
+        return fail(h, KSFD_EINVAL, "mg_part: this handle has no cycle with fp32 level vectors (2-D strip kernel on level 0, nu = 2, fused smoother, tuning bit 19 clear)");
+    if (part == KSFD_MGP_SMOOTH && (nu < 1 || nu > 5)) return fail(h, KSFD_EINVAL, "mg_part: nu = %d outside 1 .. 5", (int)nu);
+    if (part == KSFD_MGP_SMOOTH && !(ratio > 1.0)) return fail(h, KSFD_EINVAL, "mg_part: smoothing ratio %.6g not above 1", ratio);
+    if ((part != KSFD_MGP_COEF && part != KSFD_MGP_DINV && !in0) || (need1 && !in1) || !out0 || (need_o1 && !out1))
+        return fail(h, KSFD_EINVAL, "mg_part %d: missing buffer", (int)part);
+    if (setup && part != KSFD_MGP_CYCLE && (size_t)level > mg_end(h)) return fail(h, KSFD_EINVAL, "mg_part %d: level %d lies below the level the cycle ends on", (int)part, (int)level);
+    hipSetDevice(h->device);
+    int rc;
+    if ((rc = mgp_begin(h, setup, shift))) { mgp_end(h); return rc; }
+    if (setup && part != KSFD_MGP_CYCLE && !mgp_smoothed(h, (size_t)level)) { mgp_end(h); return fail(h, KSFD_EINVAL, "mg_part %d: level %d is solved exactly and has no smoother", (int)part, (int)level); }
+    double *const a = h->t1, *const b = h->t2, *const c = h->t3;     // staging in the level's ghosted layout (no larger than the handle's vectors)
+    auto run = [&]() -> int {
+        int r;
+        switch (part) {
+        case KSFD_MGP_COEF: {
+            if ((r = mgp_get(h, L, np, (const double *)L.coef, out0))) return r;
+            const float *c32 = mg_sys(h, L).coef32;
+            if (out1 && c32) return mgp_get(h, L, np, c32, out1);
+            return KSFD_OK;
+        }
+        case KSFD_MGP_RESTRICT:
+            if (variant == 0) {
+                if ((r = mgp_put(h, L, F, in0, a)) || (r = mg_halo(h, L, a, F))) return r;
+                mg_launch_restrict(h, L, Lc, F, a, b);
+                return mgp_get(h, Lc, F, (const double *)b, out0);
+            }
+            if (variant == 2) {                             // what the fp32 coefficient copy of a level is made with
+                if ((r = mgp_put(h, L, F, in0, a)) || (r = mg_halo(h, L, a, F))) return r;
+                mg_launch_restrict2d(h, L, Lc, F, (const double *)a, Lc.b32);
+                return mgp_get(h, Lc, F, (const float *)Lc.b32, out0);
+            }
+            if ((r = mgp_put(h, L, F, in0, L.r32)) || (r = mg_halo(h, L, L.r32, F))) return r;
+            if (cf32) { mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b32); return mgp_get(h, Lc, F, (const float *)Lc.b32, out0); }
+            mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b);
+            return mgp_get(h, Lc, F, (const double *)Lc.b, out0);
+        case KSFD_MGP_PROLONG_ADD:
+            if (variant == 0) {
+                if ((r = mgp_put(h, L, F, in0, a)) || (r = mgp_put(h, Lc, F, in1, b)) || (r = mg_halo(h, Lc, b, F))) return r;
+                mg_launch_prolong(h, L, Lc, F, b, a);
+                return mgp_get(h, L, F, (const double *)a, out0);
+            }
+            if ((r = mgp_put(h, L, F, in0, L.x32))) return r;
+            if (cf32) {
+                if ((r = mgp_put(h, Lc, F, in1, Lc.x32)) || (r = mg_halo(h, Lc, Lc.x32, F))) return r;
+                mg_launch_prolong2d(h, L, Lc, F, (const float *)Lc.x32, L.x32);
+            } else {
+                if ((r = mgp_put(h, Lc, F, in1, Lc.x)) || (r = mg_halo(h, Lc, Lc.x, F))) return r;
+                mg_launch_prolong2d(h, L, Lc, F, (const double *)Lc.x, L.x32);
+            }
+            return mgp_get(h, L, F, (const float *)L.x32, out0);
+        case KSFD_MGP_OPERATOR:
+            if (variant == 32) {
+                if ((r = mgp_put(h, L, F, in0, L.x32)) || (r = mgp_put(h, L, F, in1, L.b32))) return r;
+                if ((r = mg_op32(h, L, L.x32, 2, shift, L.r32, L.b32, nullptr))) return r;
+                return mgp_get(h, L, F, (const float *)L.r32, out0);
+            }
+            if ((r = mgp_put(h, L, F, in0, a)) || (variant == 2 && (r = mgp_put(h, L, F, in1, c)))) return r;
+            if ((r = mg_op(h, L, a, variant, shift, b, variant == 2 ? c : nullptr))) return r;
+            return mgp_get(h, L, F, (const double *)b, out0);
+        case KSFD_MGP_DINV: return mgp_get(h, L, F * F, (const float *)L.dinv, out0);
+        case KSFD_MGP_DINV_APPLY: {
+            const double scale = nu ? (double)nu : 1.0;        // any scale: nu stands in (0 = 1)
+            if ((r = mgp_put(h, L, F, in0, a))) return r;
+            if (variant == 0) {
+                mg_dinv_apply(h, L, 0.0, (const double *)a, 1.0 / scale, b, c, L.Ad);
+                if ((r = mgp_get(h, L, F, (const double *)b, out0)) || (r = mgp_get(h, L, F, (const double *)c, out1))) return r;
+                return mgp_get(h, L, F, (const double *)L.Ad, out1 + (int64_t)F * L.G.nloc);
+            }
+            mg_dinv_apply(h, L, 0.0, (const double *)a, 1.0 / scale, L.d32, L.x32, L.b32);
+            if ((r = mgp_get(h, L, F, (const float *)L.d32, out0)) || (r = mgp_get(h, L, F, (const float *)L.x32, out1))) return r;
+            return mgp_get(h, L, F, (const float *)L.b32, out1 + (int64_t)F * L.G.nloc);
+        }
+        case KSFD_MGP_SMOOTH:
+            if ((r = mgp_put(h, L, F, in0, a))) return r;
+            if (in1) { if ((r = mgp_put(h, L, F, in1, b))) return r; }
+            else HIPCHK(h, hipMemsetAsync(b, 0x7f, sizeof(double) * (size_t)L.vlen, h->st));      // zero guess: x is not to be read (1.4e306 if it is)
+            if ((r = mg_smooth(h, L, shift, a, b, nu, !in1, ratio))) return r;
+            return mgp_get(h, L, F, (const double *)b, out0);
+        default: {                                             // KSFD_MGP_CYCLE
+            if ((r = mgp_put(h, L, F, in0, a))) return r;
+            HIPCHK(h, hipMemsetAsync(b, 0x7f, sizeof(double) * (size_t)L.vlen, h->st));
+            const bool was = h->mg_use32;
+            h->mg_use32 = variant == 1;
+            r = mg_precond(h, shift, a, b);
+            h->mg_use32 = was;
+            if (r) return r;
+            return mgp_get(h, L, F, (const double *)b, out0);
+        }
+        }
+    };
+    rc = run();
+    if (!rc && hipGetLastError() != hipSuccess) rc = fail(h, KSFD_EHIP, "mg_part %d: launch failed", (int)part);
+    mgp_end(h);
+    return rc;
+}
 extern "C" int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, double mg_threshold)
 {
     if (!h || max_degree < 0 || max_degree > 7) return KSFD_EINVAL;

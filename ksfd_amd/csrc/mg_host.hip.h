@@ -92,6 +92,20 @@ static int mg_build(ksfd_handle *h)
     return KSFD_OK;
 }
 
+// 2-D transfer operators for any storage types of the fine and the coarse vector (the fp32 cycle and the fp32 coefficient copy)
+template <typename TF, typename TK>
+static void mg_launch_restrict2d(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TF *fine, TK *coarse)
+{
+    hipLaunchKernelGGL((k_restrict2d<TF, TK>), dim3(point_blocks(Lc.G)), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
+                       fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+}
+template <typename TK, typename TF>
+static void mg_launch_prolong2d(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TK *coarse, TF *fine)
+{
+    hipLaunchKernelGGL((k_prolong_add2d<TK, TF>), dim3(point_blocks(Lf.G)), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
+                       coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
+}
+
 // transfer operators, 2-D or 3-D by the level geometry
 static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const double *fine, double *coarse)
 {
@@ -102,9 +116,7 @@ static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np,
     else if (Lf.G.dim == 3)
         hipLaunchKernelGGL(k_restrict3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
                            fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
-    else
-        hipLaunchKernelGGL((k_restrict2d<double, double>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
-                           fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+    else mg_launch_restrict2d(h, Lf, Lc, np, fine, coarse);
 }
 static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const double *coarse, double *fine)
 {
@@ -115,9 +127,7 @@ static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, 
     else if (Lf.G.dim == 3)
         hipLaunchKernelGGL(k_prolong_add3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
                            coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
-    else
-        hipLaunchKernelGGL((k_prolong_add2d<double, double>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
-                           coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
+    else mg_launch_prolong2d(h, Lf, Lc, np, coarse, fine);
 }
 
 // ghost rows of a level vector (np field planes) from the ring neighbours.  An fp32 vector travels through the double-typed transport as
@@ -194,11 +204,9 @@ static int mg_restrict_coefs(ksfd_handle *h)
         if ((rc = mg_halo(h, Lc, Lc.coef, np))) return rc;       // fine ghosts were valid; now the coarse ones are too
         if (Lc.coef32) {
             // the fp32 cycle reads an fp32 copy (the same full weighting of the fine fp64 planes, rounded once)
-            int nb = point_blocks(Lc.G);
             {
                 Scope sc(h, KC_MG, np * (8.0 * Lf.G.nloc + 4.0 * Lc.G.nloc));
-                hipLaunchKernelGGL((k_restrict2d<double, float>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
-                                   (const double *)Lf.coef, Lf.G.plane, Lf.kv.off, Lc.coef32, Lc.G.plane, Lc.kv.off);
+                mg_launch_restrict2d(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef32);
             }
             if ((rc = mg_halo(h, Lc, Lc.coef32, np))) return rc;
         }
@@ -206,6 +214,15 @@ static int mg_restrict_coefs(ksfd_handle *h)
     HIPCHK(h, hipGetLastError());
     h->mg_coef_valid = true;
     return KSFD_OK;
+}
+
+// z = scale * Dinv r on the owned points of level L (z2, rcopy: k_dinv_apply); vectors in the level's ghosted layout, bytes = what the launch moves
+template <typename TR, typename TZ>
+static void mg_dinv_apply(ksfd_handle *h, MGLevel &L, double bytes, const TR *r, double scale, TZ *z, TZ *z2 = nullptr, TZ *rcopy = nullptr)
+{
+    const long long off = L.kv.off;     // owned rows start here inside a (ghosted) plane
+    Scope sc(h, KC_MG, bytes);
+    NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dinv_apply<NL, TR, TZ>), dim3(point_blocks(L.G)), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), r + off, scale, z + off, z2 ? z2 + off : (TZ *)nullptr, rcopy ? rcopy + off : (TZ *)nullptr));
 }
 
 // block-diagonal inverses and Chebyshev upper bounds for this shift
@@ -245,10 +262,7 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
         for (int it = 0; it < its; it++) {
             if (!(nv > 0.0) || nv != nv) break;
             if ((rc = mg_op(h, L, v, 1, shift, L.Ad, nullptr))) return rc;
-            {
-                Scope sc(h, KC_MG, 8.0 * (2 * F + 0.5 * F * F) * L.G.nloc);
-                NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dinv_apply<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + L.kv.off), (const double *)(L.Ad + L.kv.off), 1.0 / nv, w + L.kv.off));
-            }
+            mg_dinv_apply(h, L, 8.0 * (2 * F + 0.5 * F * F) * L.G.nloc, (const double *)L.Ad, 1.0 / nv, w);
             double nw;
             if ((rc = mg_norm(h, L, w, &nw))) return rc;
             if (!(nw > 0.0)) break;
@@ -290,10 +304,7 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
         KSmooth S = KSmooth{};
         S.dinv = L.dinv; S.x = x; S.c1 = rhon * rho0; S.c2 = 2.0 * rhon / delta;
         if (zero_init) {
-            {
-                Scope sc(h, KC_MG, 8.0 * (2 * F + 0.5 * F * F) * L.G.nloc);
-                NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dinv_apply<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), b + off, 1.0 / theta, L.d + off));
-            }
+            mg_dinv_apply(h, L, 8.0 * (2 * F + 0.5 * F * F) * L.G.nloc, b, 1.0 / theta, L.d);
             S.rr = b; S.x_has_d = 1;
             return mg_op(h, L, L.d, 6, shift, nullptr, nullptr, &S);
         }
@@ -307,10 +318,7 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
         if ((rc = mg_op(h, L, x, 2, shift, L.r, b))) return rc;        // r = b - A x
         res = L.r;
     }
-    {
-        Scope sc(h, KC_MG, 8.0 * ((zero_init ? 3 : 2) * F + 0.5 * F * F) * L.G.nloc);
-        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dinv_apply<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), res + off, 1.0 / theta, L.d + off, zero_init ? x + off : (double *)nullptr));
-    }
+    mg_dinv_apply(h, L, 8.0 * ((zero_init ? 3 : 2) * F + 0.5 * F * F) * L.G.nloc, res, 1.0 / theta, L.d, zero_init ? x : (double *)nullptr);
     bool x_has_d = zero_init;          // x == d_0 already
     double rho = 1.0 / sig1;
     for (int k = 1; k < nu; k++) {
@@ -345,6 +353,13 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
 }
 
 static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const double *b, double *x);
+
+// Chebyshev sweeps of the coarse solve on the level the cycle ends on: over the whole spectrum, enough for the reduction mg_coarse_tol
+static int mg_coarse_sweeps(const ksfd_handle *h, const MGLevel &L)
+{
+    const int sweeps = (int)ceil(0.5 * sqrt(L.ratio) * log(2.0 / h->mg_coarse_tol));
+    return std::min(std::max(sweeps, 4), h->mg_ncoarse);
+}
 
 // coarse-grid correction of level l: restrict L.r, recurse, prolong-add into x
 static int mg_coarse_correction(ksfd_handle *h, size_t l, double shift, double *x)
@@ -407,10 +422,7 @@ static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const double *b, do
     MGLevel &L = h->mg[l];
     if (l == mg_end(h)) {
         if (h->mgc.kind == 1 && h->mgc.ready) return mgc_apply(h, L, b, x);
-        // coarsest grid: Chebyshev over the whole spectrum, enough sweeps for a ~1e-2 reduction
-        int sweeps = (int)ceil(0.5 * sqrt(L.ratio) * log(2.0 / h->mg_coarse_tol));
-        sweeps = std::min(std::max(sweeps, 4), h->mg_ncoarse);
-        return mg_smooth(h, L, shift, b, x, sweeps, true, L.ratio);
+        return mg_smooth(h, L, shift, b, x, mg_coarse_sweeps(h, L), true, L.ratio);
     }
     if ((rc = mg_smooth(h, L, shift, b, x, h->mg_nu, true, h->mg_ratio))) return rc;
     if ((rc = mg_op(h, L, x, 2, shift, L.r, b))) return rc;
@@ -453,14 +465,12 @@ static int mg_coarse_correction32(ksfd_handle *h, size_t l, double shift)
     int rc;
     MGLevel &L = h->mg[l], &Lc = h->mg[l + 1];
     const int F = L.G.F;
-    const int nbr = point_blocks(Lc.G);
-    const int nbp = point_blocks(L.G);
     const bool c32 = mg_f32(h, l + 1);
     if ((rc = mg_halo(h, L, L.r32, F))) return rc;                    // restriction reads fine rows -1 and sloc
     {
         Scope sc(h, KC_MG, F * (4.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
-        if (c32) hipLaunchKernelGGL((k_restrict2d<float, float>), dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)L.r32, L.G.plane, L.kv.off, Lc.b32, Lc.G.plane, Lc.kv.off);
-        else hipLaunchKernelGGL((k_restrict2d<float, double>), dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)L.r32, L.G.plane, L.kv.off, Lc.b, Lc.G.plane, Lc.kv.off);
+        if (c32) mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b32);
+        else mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b);
     }
     if (c32) rc = mg_vcycle32(h, l + 1, shift, nullptr, nullptr);
     else rc = mg_vcycle(h, l + 1, shift, Lc.b, Lc.x);
@@ -468,8 +478,8 @@ static int mg_coarse_correction32(ksfd_handle *h, size_t l, double shift)
     if ((rc = c32 ? mg_halo(h, Lc, Lc.x32, F) : mg_halo(h, Lc, Lc.x, F))) return rc;      // prolongation reads coarse row sloc_c
     {
         Scope sc(h, KC_MG, F * (8.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
-        if (c32) hipLaunchKernelGGL((k_prolong_add2d<float, float>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const float *)Lc.x32, Lc.G.plane, Lc.kv.off, L.x32, L.G.plane, L.kv.off);
-        else hipLaunchKernelGGL((k_prolong_add2d<double, float>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, F, L.G.nx, L.G.sloc, L.G.wrap_slow, (const double *)Lc.x, Lc.G.plane, Lc.kv.off, L.x32, L.G.plane, L.kv.off);
+        if (c32) mg_launch_prolong2d(h, L, Lc, F, (const float *)Lc.x32, L.x32);
+        else mg_launch_prolong2d(h, L, Lc, F, (const double *)Lc.x, L.x32);
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
@@ -481,21 +491,16 @@ static int mg_vcycle32(ksfd_handle *h, size_t l, double shift, const double *b64
     int rc;
     MGLevel &L = h->mg[l];
     const int F = L.G.F;
-    const int nb = point_blocks(L.G);
     const double lmax = L.lam_max, lmin = lmax / h->mg_ratio;
     const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
     const double rho0 = 1.0 / sig1, rhon = 1.0 / (2.0 * sig1 - rho0);
-    const long long off = L.kv.off;
     KSmoothT<float> S = KSmoothT<float>{};
     S.dinv = L.dinv; S.x = L.x32; S.c1 = rhon * rho0; S.c2 = 2.0 * rhon / delta;
     // pre-smoothing from a zero guess: d0 = Dinv b / theta (+ the fp32 copy of b on level 0); then x = d0 + d1 in the epilogue of A d0
     {
-        Scope sc(h, KC_MG, ((b64 ? 8.0 + 4.0 : 4.0) * F + 4.0 * F + 4.0 * F * F) * (double)L.G.nloc);
-        if (b64) {
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dinv_apply<NL, double, float>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), b64 + off, 1.0 / theta, L.d32 + off, (float *)nullptr, L.b32 + off));
-        } else {
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dinv_apply<NL, float, float>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), (const float *)(L.b32 + off), 1.0 / theta, L.d32 + off));
-        }
+        const double by = ((b64 ? 8.0 + 4.0 : 4.0) * F + 4.0 * F + 4.0 * F * F) * (double)L.G.nloc;
+        if (b64) mg_dinv_apply(h, L, by, b64, 1.0 / theta, L.d32, (float *)nullptr, L.b32);
+        else mg_dinv_apply(h, L, by, (const float *)L.b32, 1.0 / theta, L.d32);
     }
     S.rr = L.b32; S.x_has_d = 1;
     if ((rc = mg_op32(h, L, L.d32, 6, shift, nullptr, nullptr, &S))) return rc;

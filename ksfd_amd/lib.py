@@ -79,6 +79,17 @@ class MGCoarseInfo(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class MGLevelInfo(C.Structure):
+    _fields_ = [('level', C.c_int32), ('nlevels', C.c_int32), ('end_level', C.c_int32), ('F', C.c_int32), ('n', C.c_int64 * 3),
+                ('sloc', C.c_int64), ('points', C.c_int64), ('path', C.c_int32), ('f32', C.c_int32), ('coef32', C.c_int32),
+                ('can_fuse', C.c_int32), ('have_setup', C.c_int32), ('coarse_sweeps', C.c_int32), ('lam_max', C.c_double),
+                ('ratio', C.c_double)]
+
+
+# parts of ksfd_mg_part (KSFD_MGP_*) and the kernel paths ksfd_mg_level_info reports
+MGP_COEF, MGP_RESTRICT, MGP_PROLONG_ADD, MGP_OPERATOR, MGP_DINV, MGP_DINV_APPLY, MGP_SMOOTH, MGP_CYCLE = range(8)
+MG_PATH_STRIP2D, MG_PATH_STRIP3D, MG_PATH_GENERIC = 0, 2, 3
+
 ROT_MAXIN, ROT_MAXOUT = 121, 18     # KSFD_ROT_MAXIN / KSFD_ROT_MAXOUT: limits of the basis rotation kernel
 BENCH_ROTATE, BENCH_ROTATE_COMPOSED = 100, 101      # ksfd_bench_kernel: one-pass rotation 31 -> 11 vectors / 11 basis combinations
 # operations of ksfd_krylov_op (KSFD_KOP_*), and the longest cycle of the pipelined solver (KSFD_ASYNC_MAXK)
@@ -99,7 +110,7 @@ ABI_SYMBOLS = [
     'ksfd_get_profile', 'ksfd_synchronize', 'ksfd_bench_kernel', 'ksfd_set_tuning', 'ksfd_set_mg_params', 'ksfd_set_poly_params',
     'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply', 'ksfd_banded_apply',
     'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity', 'ksfd_krylov_op',
-    'ksfd_set_mg_coarse', 'ksfd_get_mg_coarse_info', 'ksfd_mg_coarse_apply',
+    'ksfd_set_mg_coarse', 'ksfd_get_mg_coarse_info', 'ksfd_mg_coarse_apply', 'ksfd_mg_level_info', 'ksfd_mg_part',
 ]
 
 
@@ -173,6 +184,8 @@ def load():
     L.ksfd_set_mg_coarse.argtypes = [vp, C.c_int32, C.c_int32]
     L.ksfd_get_mg_coarse_info.argtypes = [vp, C.POINTER(MGCoarseInfo)]
     L.ksfd_mg_coarse_apply.argtypes = [vp, C.c_double, C.c_int32, dp, dp]
+    L.ksfd_mg_level_info.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.POINTER(MGLevelInfo)]
+    L.ksfd_mg_part.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp]
     _lib = L
     return L
 
@@ -443,6 +456,46 @@ class KSFDHip:
         out = np.empty(n)
         self._chk(self.L.ksfd_mg_coarse_apply(self.h, float(shift), int(op), _dp(v), _dp(out)))
         return out
+
+    def mg_level_info(self, level, shift=None):
+        """geometry and kernel choice of one level of the V cycle (test entry, ksfd_mg_level_info): dict(level, nlevels, end_level, F, n,
+        sloc, points, path, f32, coef32, can_fuse); with a shift, after a cold set-up at it, also have_setup, lam_max, ratio and
+        coarse_sweeps.  Afterwards the hierarchy counts as not set up."""
+        s = MGLevelInfo()
+        self._chk(self.L.ksfd_mg_level_info(self.h, int(level), int(shift is not None), float(shift or 0.0), C.byref(s)))
+        return dict(level=s.level, nlevels=s.nlevels, end_level=s.end_level, F=s.F, n=tuple(int(x) for x in s.n), sloc=int(s.sloc),
+                    points=int(s.points), path=s.path, f32=bool(s.f32), coef32=s.coef32, can_fuse=bool(s.can_fuse),
+                    have_setup=bool(s.have_setup), coarse_sweeps=s.coarse_sweeps, lam_max=s.lam_max, ratio=s.ratio)
+
+    def mg_part(self, part, level, in0=None, in1=None, variant=0, nu=0, shift=0.0, ratio=0.0):
+        """one part of the V cycle on host vectors through the wrappers the cycle calls (test entry, ksfd_mg_part; include/ksfd_hip.h has
+        the parts and their variants).  Vectors: (planes, owned points of the level) or flat.  Returns out0 as (planes, points); COEF
+        returns (planes, fp32 copy or None), DINV_APPLY (z, z2, rcopy)."""
+        fine = self.mg_level_info(level)                   # refuses a handle without a hierarchy and a level out of range
+        F, nlig = fine['F'], fine['F'] - 1
+        coarse = self.mg_level_info(level + 1) if part in (MGP_RESTRICT, MGP_PROLONG_ADD) and level + 1 < fine['nlevels'] else fine
+        n_in0, n_in1 = F * fine['points'], F * (coarse['points'] if part == MGP_PROLONG_ADD else fine['points'])
+        planes, pts = {MGP_COEF: (3 + nlig, fine['points']), MGP_RESTRICT: (F, coarse['points']),
+                       MGP_DINV: (F * F, fine['points'])}.get(part, (F, fine['points']))
+
+        def vec(a, n):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            if a.size != n:
+                raise ValueError('mg_part: vector of %d entries, expected %d' % (a.size, n))
+            return a
+        a0, a1 = vec(in0, n_in0), vec(in1, n_in1)
+        out0 = np.full((planes, pts), np.nan)
+        out1 = np.full((2 * F if part == MGP_DINV_APPLY else planes, pts), np.nan) if part in (MGP_COEF, MGP_DINV_APPLY) else None
+        p = lambda a: None if a is None else _dp(a)
+        self._chk(self.L.ksfd_mg_part(self.h, int(part), int(level), int(variant), int(nu), float(shift), float(ratio),
+                                      p(a0), p(a1), p(out0), p(out1)))
+        if part == MGP_COEF:
+            return out0, (out1 if fine['coef32'] & 2 else None)
+        if part == MGP_DINV_APPLY:
+            return out0, out1[:F], out1[F:]
+        return out0
 
     def set_deflation(self, keep, carry_stages=False):
         """GMRES with deflated restarting for the stage solves: keep harmonic Ritz vectors (0 = off, at most 16) survive a restart;
