@@ -287,8 +287,8 @@ int ksfd_get_mg_coarse_info(ksfd_handle *h, ksfd_mg_coarse_info *info);
  * calls (KSFD_ELINEAR on a zero or non-finite pivot).  State and step memory untouched. */
 int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double *v_host, double *out_host);
 /* Parity/test entry of the PARTS of the V cycle, the twin of ksfd_mg_coarse_apply and ksfd_krylov_op: one part of the cycle runs on
- * host vectors through the wrappers the cycle itself calls (mg_restrict_coefs, mg_setup_shift, mg_launch_restrict / _prolong and their
- * 2-D storage-type forms, mg_halo, mg_op, mg_op32, mg_dinv_apply, mg_smooth, mg_precond), never through a kernel launch of its own, so a
+ * host vectors through the wrappers the cycle itself calls (mg_restrict_coefs, mg_setup_shift, mg_launch_restrict / _prolong in
+ * every storage-type pair, mg_halo, mg_op in both storage types, mg_dinv_apply, mg_smooth, mg_precond), never through a kernel launch of its own, so a
  * wrong launch argument shows.  Host vectors are SoA of the level (x fastest, field slowest), OWNED points only: F * points doubles,
  * points = ksfd_mg_level_info_t.points.  fp32 operands are rounded to float on the host before upload and come back as doubles.
  * Handles with a halo transport: every call is collective, each rank passes its slab of the level (sloc slow units).
@@ -314,7 +314,7 @@ int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double 
  *                launch that makes the fp32 coefficient copy)
  *   PROLONG_ADD  out0 = in0 (level) + P in1 (level + 1).  variant 0: fp64 (mg_launch_prolong); 1 (f32 levels): fine fp32, coarse as above
  *   OPERATOR     variant 1: out0 = (shift*I - J_l) in0; 2: out0 = in1 - (shift*I - J_l) in0 (mg_op modes 1, 2); 32 (f32 levels): mode 2 of
- *                mg_op32 on fp32 vectors
+ *                mg_op on fp32 vectors
  *   DINV         out0 = the F*F planes k_blockdiag_inv leaves after mg_setup_shift(shift) (row-major blocks, fp32 values)
  *   DINV_APPLY   k_dinv_apply with scale 1/nu (nu = 0: 1): out0 = z, out1 = [z2 | rcopy] (2 F points).  variant 0: fp64 in and out;
  *                1 (f32 levels): fp64 in, fp32 out (entry of the fp32 cycle)

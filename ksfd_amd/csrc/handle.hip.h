@@ -13,6 +13,10 @@ static thread_local std::string g_create_error;
 
 struct EvPair { hipEvent_t a, b; int cls; };
 
+// level vectors of the V cycle in the storage type T: solution, right-hand side, residual, Chebyshev direction
+template <typename T>
+struct MGVecs { T *x = nullptr, *b = nullptr, *r = nullptr, *d = nullptr; };
+
 // one grid of the multigrid hierarchy (level 0 = the solver's own grid; see mg.hip.h)
 struct MGLevel {
     KGeom G;
@@ -22,8 +26,10 @@ struct MGLevel {
     int nblk = 1;
     double *coef = nullptr;    // [rho, G, G_rho, G_U..] planes (level 0 aliases the handle's)
     float *dinv = nullptr;     // F*F planes (fp32)
-    double *x = nullptr, *b = nullptr, *r = nullptr, *d = nullptr, *Ad = nullptr, *dG = nullptr;
-    float *x32 = nullptr, *b32 = nullptr, *r32 = nullptr, *d32 = nullptr;   // level vectors of the fp32 V cycle (f32 levels only)
+    MGVecs<double> v64;        // level 0 has no x and b: they are the caller's vectors
+    MGVecs<float> v32;         // f32 levels only
+    template <typename T> MGVecs<T> &vecs() { if constexpr (std::is_same<T, float>::value) return v32; else return v64; }
+    double *Ad = nullptr, *dG = nullptr;
     float *coef32 = nullptr;   // fp32 copy of the coefficient planes of a coarse f32 level (level 0 uses the handle's)
     bool f32 = false;          // this level can run the fp32 cycle (2-D strip kernel, not the coarsest level)
     double *pv = nullptr;      // power-iteration vector of Dinv*A, kept from one set-up to the next (warm start)
@@ -230,7 +236,7 @@ struct ksfd_handle {
     // multigrid preconditioner
     std::vector<MGLevel> mg;
     bool sf_auto = true;         // online search for memo.mg_shift_floor (shift_floor_update); KSFD_PC_SIGMA fixes the floor instead
-    bool mg_fp32 = true;         // V cycle with fp32 level vectors when the solve tolerance allows (KSFD_TUNE bit 19 clears); see mg_vcycle32
+    bool mg_fp32 = true;         // V cycle with fp32 level vectors when the solve tolerance allows (KSFD_TUNE bit 19 clears); see mg_vcycle
     bool mg_use32 = false;       // ... decided per step by ksfd_step (ksp_rtol >= 1e-7)
     bool mg_graph_f32 = false;   // precision the captured coarse cycle was recorded in
     bool mg_warm_power = true;   // power iteration of a level starts from the vector of the previous set-up (KSFD_TUNE bit 18 clears)

@@ -819,22 +819,23 @@ extern "C" int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, co
     int rc;
     if ((rc = ensure_coef(h))) return rc;
     if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
-    MGLevel &L = h->mg[mg_end(h)];                        // never level 0: L.b and L.x are the level's own
+    MGLevel &L = h->mg[mg_end(h)];                        // never level 0: b and x are the level's own
+    double *const lb = L.v64.b, *const lx = L.v64.x;
     const size_t nb = sizeof(double) * (size_t)L.G.nloc;
     for (int f = 0; f < L.G.F; f++)
-        HIPCHK(h, hipMemcpyAsync(L.b + (int64_t)f * L.G.plane + L.kv.off, vh + (int64_t)f * L.G.nloc, nb, hipMemcpyHostToDevice, h->st));
-    if (op == 0) rc = mg_op(h, L, L.b, 1, shift, L.x, nullptr);
+        HIPCHK(h, hipMemcpyAsync(lb + (int64_t)f * L.G.plane + L.kv.off, vh + (int64_t)f * L.G.nloc, nb, hipMemcpyHostToDevice, h->st));
+    if (op == 0) rc = mg_op<double>(h, L, lb, 1, shift, lx, nullptr);
     else {
         bool ok = false;
         h->mg_shift = -1.0;                              // the coarse factors now belong to this shift: the next cycle sets up again
         if ((rc = mgc_setup(h, L, shift, &ok))) return rc;
         if (!ok) return fail(h, KSFD_ELINEAR, "coarse solve: zero or non-finite pivot in column %d of shift*I - J_c (shift %.6g, %lld unknowns)", h->mgc.info_h - 1, shift, (long long)h->mgc.lu.n);
-        rc = mgc_apply(h, L, L.b, L.x);
+        rc = mgc_apply(h, L, lb, lx);
         h->mgc.ready = false;
     }
     if (rc) return rc;
     for (int f = 0; f < L.G.F; f++)
-        HIPCHK(h, hipMemcpyAsync(outh + (int64_t)f * L.G.nloc, L.x + (int64_t)f * L.G.plane + L.kv.off, nb, hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipMemcpyAsync(outh + (int64_t)f * L.G.nloc, lx + (int64_t)f * L.G.plane + L.kv.off, nb, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
     return KSFD_OK;
 }
@@ -942,7 +943,7 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
     default: return fail(h, KSFD_EINVAL, "mg_part: unknown part %d", (int)part);
     }
     if (!ok) return fail(h, KSFD_EINVAL, "mg_part %d: level %d has no variant %d", (int)part, (int)level, (int)variant);
-    if (part == KSFD_MGP_CYCLE && variant == 1 && !(h->mg_fp32 && h->mg[0].f32 && h->mg_nu == 2 && mg_can_fuse(h, h->mg[0])))
+    if (part == KSFD_MGP_CYCLE && variant == 1 && !mg_cycle32_ok(h))
         return fail(h, KSFD_EINVAL, "mg_part: this handle has no cycle with fp32 level vectors (2-D strip kernel on level 0, nu = 2, fused smoother, tuning bit 19 clear)");
     if (part == KSFD_MGP_SMOOTH && (nu < 1 || nu > 5)) return fail(h, KSFD_EINVAL, "mg_part: nu = %d outside 1 .. 5", (int)nu);
     if (part == KSFD_MGP_SMOOTH && !(ratio > 1.0)) return fail(h, KSFD_EINVAL, "mg_part: smoothing ratio %.6g not above 1", ratio);
@@ -963,57 +964,43 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
             if (out1 && c32) return mgp_get(h, L, np, c32, out1);
             return KSFD_OK;
         }
-        case KSFD_MGP_RESTRICT:
-            if (variant == 0) {
-                if ((r = mgp_put(h, L, F, in0, a)) || (r = mg_halo(h, L, a, F))) return r;
-                mg_launch_restrict(h, L, Lc, F, a, b);
-                return mgp_get(h, Lc, F, (const double *)b, out0);
-            }
-            if (variant == 2) {                             // what the fp32 coefficient copy of a level is made with
-                if ((r = mgp_put(h, L, F, in0, a)) || (r = mg_halo(h, L, a, F))) return r;
-                mg_launch_restrict2d(h, L, Lc, F, (const double *)a, Lc.b32);
-                return mgp_get(h, Lc, F, (const float *)Lc.b32, out0);
-            }
-            if ((r = mgp_put(h, L, F, in0, L.r32)) || (r = mg_halo(h, L, L.r32, F))) return r;
-            if (cf32) { mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b32); return mgp_get(h, Lc, F, (const float *)Lc.b32, out0); }
-            mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b);
-            return mgp_get(h, Lc, F, (const double *)Lc.b, out0);
-        case KSFD_MGP_PROLONG_ADD:
-            if (variant == 0) {
-                if ((r = mgp_put(h, L, F, in0, a)) || (r = mgp_put(h, Lc, F, in1, b)) || (r = mg_halo(h, Lc, b, F))) return r;
-                mg_launch_prolong(h, L, Lc, F, b, a);
-                return mgp_get(h, L, F, (const double *)a, out0);
-            }
-            if ((r = mgp_put(h, L, F, in0, L.x32))) return r;
-            if (cf32) {
-                if ((r = mgp_put(h, Lc, F, in1, Lc.x32)) || (r = mg_halo(h, Lc, Lc.x32, F))) return r;
-                mg_launch_prolong2d(h, L, Lc, F, (const float *)Lc.x32, L.x32);
-            } else {
-                if ((r = mgp_put(h, Lc, F, in1, Lc.x)) || (r = mg_halo(h, Lc, Lc.x, F))) return r;
-                mg_launch_prolong2d(h, L, Lc, F, (const double *)Lc.x, L.x32);
-            }
-            return mgp_get(h, L, F, (const float *)L.x32, out0);
-        case KSFD_MGP_OPERATOR:
-            if (variant == 32) {
-                if ((r = mgp_put(h, L, F, in0, L.x32)) || (r = mgp_put(h, L, F, in1, L.b32))) return r;
-                if ((r = mg_op32(h, L, L.x32, 2, shift, L.r32, L.b32, nullptr))) return r;
-                return mgp_get(h, L, F, (const float *)L.r32, out0);
-            }
-            if ((r = mgp_put(h, L, F, in0, a)) || (variant == 2 && (r = mgp_put(h, L, F, in1, c)))) return r;
-            if ((r = mg_op(h, L, a, variant, shift, b, variant == 2 ? c : nullptr))) return r;
-            return mgp_get(h, L, F, (const double *)b, out0);
+        case KSFD_MGP_RESTRICT: {
+            auto go = [&](auto *fine, auto *coarse) -> int {
+                if ((r = mgp_put(h, L, F, in0, fine)) || (r = mg_halo(h, L, fine, F))) return r;
+                mg_launch_restrict(h, L, Lc, F, fine, coarse);
+                return mgp_get(h, Lc, F, coarse, out0);
+            };
+            if (variant == 0) return go(a, b);
+            if (variant == 2) return go(a, Lc.v32.b);       // what the fp32 coefficient copy of a level is made with
+            return cf32 ? go(L.v32.r, Lc.v32.b) : go(L.v32.r, Lc.v64.b);
+        }
+        case KSFD_MGP_PROLONG_ADD: {
+            auto go = [&](auto *fine, auto *coarse) -> int {
+                if ((r = mgp_put(h, L, F, in0, fine)) || (r = mgp_put(h, Lc, F, in1, coarse)) || (r = mg_halo(h, Lc, coarse, F))) return r;
+                mg_launch_prolong(h, L, Lc, F, coarse, fine);
+                return mgp_get(h, L, F, fine, out0);
+            };
+            if (variant == 0) return go(a, b);
+            return cf32 ? go(L.v32.x, Lc.v32.x) : go(L.v32.x, Lc.v64.x);
+        }
+        case KSFD_MGP_OPERATOR: {
+            auto go = [&](auto *v, auto *out, auto *y, int mode) -> int {
+                if ((r = mgp_put(h, L, F, in0, v)) || (mode == 2 && (r = mgp_put(h, L, F, in1, y)))) return r;
+                if ((r = mg_op(h, L, v, mode, shift, out, mode == 2 ? y : nullptr))) return r;
+                return mgp_get(h, L, F, out, out0);
+            };
+            return variant == 32 ? go(L.v32.x, L.v32.r, L.v32.b, 2) : go(a, b, c, variant);
+        }
         case KSFD_MGP_DINV: return mgp_get(h, L, F * F, (const float *)L.dinv, out0);
         case KSFD_MGP_DINV_APPLY: {
             const double scale = nu ? (double)nu : 1.0;        // any scale: nu stands in (0 = 1)
-            if ((r = mgp_put(h, L, F, in0, a))) return r;
-            if (variant == 0) {
-                mg_dinv_apply(h, L, 0.0, (const double *)a, 1.0 / scale, b, c, L.Ad);
-                if ((r = mgp_get(h, L, F, (const double *)b, out0)) || (r = mgp_get(h, L, F, (const double *)c, out1))) return r;
-                return mgp_get(h, L, F, (const double *)L.Ad, out1 + (int64_t)F * L.G.nloc);
-            }
-            mg_dinv_apply(h, L, 0.0, (const double *)a, 1.0 / scale, L.d32, L.x32, L.b32);
-            if ((r = mgp_get(h, L, F, (const float *)L.d32, out0)) || (r = mgp_get(h, L, F, (const float *)L.x32, out1))) return r;
-            return mgp_get(h, L, F, (const float *)L.b32, out1 + (int64_t)F * L.G.nloc);
+            auto go = [&](auto *z, auto *z2, auto *rcopy) -> int {
+                if ((r = mgp_put(h, L, F, in0, a))) return r;
+                mg_dinv_apply(h, L, 0.0, (const double *)a, 1.0 / scale, z, z2, rcopy);
+                if ((r = mgp_get(h, L, F, z, out0)) || (r = mgp_get(h, L, F, z2, out1))) return r;
+                return mgp_get(h, L, F, rcopy, out1 + (int64_t)F * L.G.nloc);
+            };
+            return variant == 0 ? go(b, c, L.Ad) : go(L.v32.d, L.v32.x, L.v32.b);
         }
         case KSFD_MGP_SMOOTH:
             if ((r = mgp_put(h, L, F, in0, a))) return r;
@@ -1285,7 +1272,7 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         case KSFD_BENCH_BAND_FACTOR: r = banded_factor(h, h->band.shift); break;
         case KSFD_BENCH_BAND_SOLVE: r = banded_solve(h, h->Y, h->t3); break;
         case KSFD_BENCH_MGC_SETUP: { bool ok = false; MGLevel &L = h->mg[mg_end(h)]; r = mgc_setup(h, L, 1.0, &ok); if (!r && !ok) r = fail(h, KSFD_ELINEAR, "bench_kernel: the coarse factorization is flagged"); } break;
-        case KSFD_BENCH_MGC_APPLY: { MGLevel &L = h->mg[mg_end(h)]; r = mgc_apply(h, L, L.b, L.x); } break;
+        case KSFD_BENCH_MGC_APPLY: { MGLevel &L = h->mg[mg_end(h)]; r = mgc_apply(h, L, L.v64.b, L.v64.x); } break;
         case KSFD_BENCH_MGC_FACTOR_COLUMNS: {
             MGLevel &L = h->mg[mg_end(h)];
             const LUSys Y{ &L.G, &L.P, L.coef, (long long)L.G.sloc, 0, KC_MG };

@@ -8,7 +8,8 @@ static int mgc_apply(ksfd_handle *h, MGLevel &L, const double *b, double *x);
 
 // level the V cycle ends on: the coarsest one unless ksfd_set_mg_coarse chose a finer one for the exact solve
 static inline size_t mg_end(const ksfd_handle *h) { return h->mgc.kind == 1 ? (size_t)h->mgc.level : h->mg.size() - 1; }
-// level l runs the fp32 cycle (the level of an exact coarse solve stays in fp64, like the coarsest level of the Chebyshev cycle)
+// level l keeps fp32 vectors in the cycle with fp32 level vectors (the level of an exact coarse solve stays in fp64, like the coarsest
+// level of the Chebyshev cycle)
 static inline bool mg_f32(const ksfd_handle *h, size_t l) { return h->mg[l].f32 && !(h->mgc.kind == 1 && l == (size_t)h->mgc.level); }
 
 // The frozen Jacobian action on level L (ops.hip.h: JvpSys, jvp_path).  Level 0 is the handle's grid: booked as its Jacobian actions are,
@@ -27,11 +28,8 @@ static void mg_free(ksfd_handle *h)
     if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
     for (size_t l = 0; l < h->mg.size(); l++) {
         MGLevel &L = h->mg[l];
-        if (L.dinv) hipFree(L.dinv);
-        double *bufs[] = { l ? L.coef : nullptr, l ? L.x : nullptr, l ? L.b : nullptr, L.r, L.d, L.Ad, L.dG, L.pv };
-        for (double *b : bufs) if (b) hipFree(b);
-        float *fb[] = { L.x32, L.b32, L.r32, L.d32, L.coef32 };
-        for (float *b : fb) if (b) hipFree(b);
+        void *bufs[] = { L.dinv, l ? L.coef : nullptr, L.coef32, L.Ad, L.dG, L.pv, L.v64.x, L.v64.b, L.v64.r, L.v64.d, L.v32.x, L.v32.b, L.v32.r, L.v32.d };
+        for (void *b : bufs) if (b) hipFree(b);
     }
     h->mg.clear();
     h->mg_ok = false;
@@ -57,10 +55,10 @@ static int mg_build(ksfd_handle *h)
         L.vlen = (int64_t)F * L.G.plane;
         L.nblk = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 2048);
         if (l == 0) L.coef = h->coef;
-        else if (alloc_d(h, &L.coef, (int64_t)(3 + nl) * L.G.plane) || alloc_d(h, &L.x, L.vlen) || alloc_d(h, &L.b, L.vlen)) return KSFD_ENOMEM;
-        if (hipMalloc((void **)&L.dinv, sizeof(float) * (size_t)F * F * L.G.plane) != hipSuccess || alloc_d(h, &L.r, L.vlen) || alloc_d(h, &L.d, L.vlen) ||
+        else if (alloc_d(h, &L.coef, (int64_t)(3 + nl) * L.G.plane) || alloc_d(h, &L.v64.x, L.vlen) || alloc_d(h, &L.v64.b, L.vlen)) return KSFD_ENOMEM;
+        if (hipMalloc((void **)&L.dinv, sizeof(float) * (size_t)F * F * L.G.plane) != hipSuccess || alloc_d(h, &L.v64.r, L.vlen) || alloc_d(h, &L.v64.d, L.vlen) ||
             alloc_d(h, &L.Ad, L.vlen) || alloc_d(h, &L.dG, L.G.plane) || alloc_d(h, &L.pv, L.vlen)) return KSFD_ENOMEM;
-        double *zero[] = { l ? L.x : nullptr, l ? L.b : nullptr, L.r, L.d, L.Ad, L.pv };
+        double *zero[] = { L.v64.x, L.v64.b, L.v64.r, L.v64.d, L.Ad, L.pv };
         for (double *z : zero) if (z) hipMemsetAsync(z, 0, sizeof(double) * (size_t)L.vlen, h->st);
         h->mg.push_back(L);
         // next level: every rank keeps >= 4 slow units (ghost width 2 + the 4th-order star), global grid >= 8 per axis
@@ -74,17 +72,17 @@ static int mg_build(ksfd_handle *h)
     h->mg_ok = h->mg.size() >= 2;
     h->mgc.level = (int)h->mg.size() - 1;
     if (h->ring) h->mg_use_graph = false;           // collectives inside the cycle: keep eager launches
-    // fp32 level vectors (mg_vcycle32): 2-D, levels the strip kernel serves, never the coarsest one (its many Chebyshev sweeps
+    // fp32 level vectors (mg_vcycle<float>): 2-D, levels the strip kernel serves, never the coarsest one (its many Chebyshev sweeps
     // stay in fp64 with the kernels they have)
     if (h->mg_ok) {
         for (size_t l = 0; l + 1 < h->mg.size(); l++) {
             MGLevel &L = h->mg[l];
             if (mg_path(h, L) != JP_STRIP2D) break;
             const size_t nb = sizeof(float) * (size_t)L.vlen;
-            if (hipMalloc((void **)&L.x32, nb) != hipSuccess || hipMalloc((void **)&L.b32, nb) != hipSuccess ||
-                hipMalloc((void **)&L.r32, nb) != hipSuccess || hipMalloc((void **)&L.d32, nb) != hipSuccess) { (void)hipGetLastError(); break; }
-            float *zero[] = { L.x32, L.b32, L.r32, L.d32 };
-            for (float *z : zero) hipMemsetAsync(z, 0, nb, h->st);
+            MGVecs<float> &V = L.v32;
+            if (hipMalloc((void **)&V.x, nb) != hipSuccess || hipMalloc((void **)&V.b, nb) != hipSuccess ||
+                hipMalloc((void **)&V.r, nb) != hipSuccess || hipMalloc((void **)&V.d, nb) != hipSuccess) { (void)hipGetLastError(); break; }
+            for (float *z : { V.x, V.b, V.r, V.d }) hipMemsetAsync(z, 0, nb, h->st);
             if (l > 0 && hipMalloc((void **)&L.coef32, sizeof(float) * (size_t)(3 + nl) * L.G.plane) != hipSuccess) { (void)hipGetLastError(); L.coef32 = nullptr; }
             L.f32 = true;
         }
@@ -92,42 +90,41 @@ static int mg_build(ksfd_handle *h)
     return KSFD_OK;
 }
 
-// 2-D transfer operators for any storage types of the fine and the coarse vector (the fp32 cycle and the fp32 coefficient copy)
+// transfer operators for the storage types of the fine and the coarse vector.  fp64 on both sides: 1-D, 2-D or 3-D by the level geometry;
+// any other pair exists in 2-D only (levels with fp32 vectors, the fp32 coefficient copy)
 template <typename TF, typename TK>
-static void mg_launch_restrict2d(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TF *fine, TK *coarse)
+static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TF *fine, TK *coarse)
 {
-    hipLaunchKernelGGL((k_restrict2d<TF, TK>), dim3(point_blocks(Lc.G)), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
-                       fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+    constexpr bool f64 = std::is_same<TF, double>::value && std::is_same<TK, double>::value;
+    const int nb = point_blocks(Lc.G), dim = f64 ? Lf.G.dim : 2;
+    if constexpr (f64) {
+        if (dim == 1)
+            hipLaunchKernelGGL(k_restrict1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
+                               fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+        if (dim == 3)
+            hipLaunchKernelGGL(k_restrict3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
+                               fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+    }
+    if (dim == 2)
+        hipLaunchKernelGGL((k_restrict2d<TF, TK>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
+                           fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
 }
 template <typename TK, typename TF>
-static void mg_launch_prolong2d(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TK *coarse, TF *fine)
+static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TK *coarse, TF *fine)
 {
-    hipLaunchKernelGGL((k_prolong_add2d<TK, TF>), dim3(point_blocks(Lf.G)), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
-                       coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
-}
-
-// transfer operators, 2-D or 3-D by the level geometry
-static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const double *fine, double *coarse)
-{
-    int nb = point_blocks(Lc.G);
-    if (Lf.G.dim == 1)
-        hipLaunchKernelGGL(k_restrict1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
-                           fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
-    else if (Lf.G.dim == 3)
-        hipLaunchKernelGGL(k_restrict3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
-                           fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
-    else mg_launch_restrict2d(h, Lf, Lc, np, fine, coarse);
-}
-static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const double *coarse, double *fine)
-{
-    int nb = point_blocks(Lf.G);
-    if (Lf.G.dim == 1)
-        hipLaunchKernelGGL(k_prolong_add1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
+    constexpr bool f64 = std::is_same<TF, double>::value && std::is_same<TK, double>::value;
+    const int nb = point_blocks(Lf.G), dim = f64 ? Lf.G.dim : 2;
+    if constexpr (f64) {
+        if (dim == 1)
+            hipLaunchKernelGGL(k_prolong_add1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
+                               coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
+        if (dim == 3)
+            hipLaunchKernelGGL(k_prolong_add3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
+                               coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
+    }
+    if (dim == 2)
+        hipLaunchKernelGGL((k_prolong_add2d<TK, TF>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
                            coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
-    else if (Lf.G.dim == 3)
-        hipLaunchKernelGGL(k_prolong_add3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
-                           coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
-    else mg_launch_prolong2d(h, Lf, Lc, np, coarse, fine);
 }
 
 // ghost rows of a level vector (np field planes) from the ring neighbours.  An fp32 vector travels through the double-typed transport as
@@ -145,30 +142,39 @@ static int mg_halo(ksfd_handle *h, MGLevel &L, T *v, int np)
 // smoother algebra in the epilogue of the Jacobian action: the 2-D strip kernel and the generic kernel have it
 static bool mg_can_fuse(const ksfd_handle *h, const MGLevel &L) { return h->mg_fuse && mg_path(h, L) != JP_STRIP3D; }
 
-// out = J v | shift v - J v | yadd - (shift v - J v) on level L
+// Which coefficient planes the strip kernel reads on the level of Y when the level vectors are stored in T.  fp64 vectors: the fp32 copy
+// on level 0 only (the V cycle is a preconditioner: see poly_apply; the coarse levels keep their fp64 planes).  fp32 vectors: the fp32
+// copy on every level that has one.  NULL: the fp64 planes
+template <typename T>
+static const float *mg_strip_coef32(const JvpSys &Y) { return (std::is_same<T, float>::value || Y.cls == KC_JVP) ? Y.coef32 : nullptr; }
+
+// out = J v | shift v - J v | yadd - (shift v - J v) on level L, vectors stored in T (float: levels of the 2-D strip kernel only)
 // sm != NULL: modes 5 / 6, smoother algebra in the epilogue (2-D strip kernel and generic kernel only: see mg_can_fuse)
-static int mg_op(ksfd_handle *h, MGLevel &L, const double *v, int mode, double shift, double *out, const double *yadd,
-                 const KSmooth *sm = nullptr)
+template <typename T>
+static int mg_op(ksfd_handle *h, MGLevel &L, const T *v, int mode, double shift, T *out, const T *yadd, const KSmoothT<T> *sm = nullptr)
 {
     const KGeom &G = L.G;
-    if (h->ring) { int rch = mg_halo(h, L, const_cast<double *>(v), G.F); if (rch) return rch; }
+    if (h->ring) { int rch = mg_halo(h, L, const_cast<T *>(v), G.F); if (rch) return rch; }
     const JvpSys Y = mg_sys(h, L);
-    const JvpPath path = mg_path(h, L);
-    // planes moved: coefficients + v, plus per mode: 1/2: out (+ yadd); 5: yadd, Dinv, r, d; 6: Dinv, rr, x in and out
-    const double by = 8.0 * ((3 + h->P.nlig) + G.F + (mode == 5 ? 3.0 * G.F + 0.5 * G.F * G.F : mode == 6 ? 3.0 * G.F + 0.5 * G.F * G.F : G.F + (mode == 2 ? G.F : 0))) * (double)G.nloc;
-    const KSmooth S = sm ? *sm : KSmooth{};
+    // path: fp32 vectors exist only where mg_build found the 2-D strip kernel, the one kernel that takes them; the 3-D strip kernel and
+    // the generic kernel are reached with fp64 vectors alone
+    const JvpPath path = std::is_same<T, float>::value ? JP_STRIP2D : mg_path(h, L);
+    const float *c32 = path == JP_STRIP2D ? mg_strip_coef32<T>(Y) : nullptr;
+    // bytes per point: coefficient planes, v and per mode 1: out; 2: yadd, out; 5: yadd, r, d; 6: rr, x in and out; Dinv in modes 5 and 6;
+    // a mode 6 that writes the fp64 result (x64) stores 8 bytes in place of sizeof(T)
+    const double s = sizeof(T);
+    const double by = ((c32 ? 4.0 : 8.0) * (3 + h->P.nlig) + s * G.F * (1 + (mode == 1 ? 1 : mode == 2 ? 2 : 3)) + (mode >= 5 ? 4.0 * G.F * G.F : 0.0) +
+                       ((mode == 6 && sm && sm->x64) ? (8.0 - s) * G.F : 0.0)) * (double)G.nloc;
     if (path == JP_STRIP2D) {
         const KStrips K = strips_for(G, h->yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
-        // fp64 level vectors: level 0 alone reads an fp32 copy of the coefficient planes (the V cycle is a preconditioner: see poly_apply)
-        const float *c32 = Y.cls == KC_JVP ? Y.coef32 : nullptr;
-        Scope sc(h, Y.cls, by - (c32 ? 4.0 * (3 + h->P.nlig) * (double)G.nloc : 0.0));
-        auto launch = [&](auto *C) { sm ? jvp2d_launch<true>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, S, nullptr) : jvp2d_launch<false>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, S, nullptr); };
+        Scope sc(h, Y.cls, by);
+        auto launch = [&](auto *C) { sm ? jvp2d_launch<true>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, *sm, nullptr) : jvp2d_launch<false>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, KSmooth{}, nullptr); };
         if (c32) launch(c32); else launch(Y.coef);
-    } else {
+    } else if constexpr (std::is_same<T, double>::value) {
         Scope sc(h, Y.cls, by + 8.0 * G.plane);
         dg_pass(h, Y, v, -1);
         if (path == JP_STRIP3D) jvp3d_launch<double>(h, Y, k3d_for(G, 4, 0, h->zseg, 1024), v, mode, shift, out, yadd, 0.0, 0.0, nullptr);
-        else jvpgen_launch(h, Y, plane_blocks(G), v, mode, shift, out, yadd, 0.0, 0.0, S);
+        else jvpgen_launch(h, Y, plane_blocks(G), v, mode, shift, out, yadd, 0.0, 0.0, sm ? *sm : KSmooth{});
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
@@ -199,14 +205,14 @@ static int mg_restrict_coefs(ksfd_handle *h)
         MGLevel &Lf = h->mg[l], &Lc = h->mg[l + 1];
         {
             Scope sc(h, KC_MG, 8.0 * np * (Lf.G.nloc + Lc.G.nloc));
-            mg_launch_restrict(h, Lf, Lc, np, Lf.coef, Lc.coef);
+            mg_launch_restrict(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef);
         }
         if ((rc = mg_halo(h, Lc, Lc.coef, np))) return rc;       // fine ghosts were valid; now the coarse ones are too
         if (Lc.coef32) {
             // the fp32 cycle reads an fp32 copy (the same full weighting of the fine fp64 planes, rounded once)
             {
                 Scope sc(h, KC_MG, np * (8.0 * Lf.G.nloc + 4.0 * Lc.G.nloc));
-                mg_launch_restrict2d(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef32);
+                mg_launch_restrict(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef32);
             }
             if ((rc = mg_halo(h, Lc, Lc.coef32, np))) return rc;
         }
@@ -247,11 +253,11 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
             NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_blockdiag_inv<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G, L.P, (const double *)L.coef, shift, L.dinv));
         }
         HIPCHK(h, hipGetLastError());
-        // power iteration on Dinv*A: v and w = Dinv A v / |v| alternate between L.pv and L.r, A v in L.Ad.  The vector is kept
+        // power iteration on Dinv*A: v and w = Dinv A v / |v| alternate between L.pv and L.v64.r, A v in L.Ad.  The vector is kept
         // from one set-up to the next (L.pv): the shift and the frozen state move a little from step to step and the dominant
         // vector with them, so a warm start needs 2-3 iterations where the cold one from a hash fill takes mg_power_its
         // (4096^2 x 3 fields: 9.4 -> 2.9 ms of set-up per step).
-        double *v = L.pv, *w = L.r;
+        double *v = L.pv, *w = L.v64.r;
         double nv = L.pv_norm, lam = 2.0, lam_prev = 0.0;
         const bool warm = nv > 0.0 && h->mg_warm_power;
         if (!warm) {
@@ -261,7 +267,7 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
         const int its = warm ? std::min(h->mg_power_its, 3) : h->mg_power_its;
         for (int it = 0; it < its; it++) {
             if (!(nv > 0.0) || nv != nv) break;
-            if ((rc = mg_op(h, L, v, 1, shift, L.Ad, nullptr))) return rc;
+            if ((rc = mg_op<double>(h, L, v, 1, shift, L.Ad, nullptr))) return rc;
             mg_dinv_apply(h, L, 8.0 * (2 * F + 0.5 * F * F) * L.G.nloc, (const double *)L.Ad, 1.0 / nv, w);
             double nw;
             if ((rc = mg_norm(h, L, w, &nw))) return rc;
@@ -285,64 +291,81 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
     return KSFD_OK;
 }
 
+// The V(2,2) smoother pair with the algebra in the Jacobian-action epilogues (modes 5 and 6, KSmoothT), level vectors stored in T: 2 launches
+// instead of 3 (zero guess) or 4 (correction), and the residual / A d round trips through memory disappear.
+//   zero guess:  d0 = Dinv b / theta, then x = d0 + d1 in the epilogue of A d0 (mode 6)
+//   correction:  r = b - A x and d0 = Dinv r / theta in one launch (mode 5), x += d0 + d1 in the next (mode 6)
+// Level 0 of the fp32 cycle works on the caller's fp64 vectors: b64 (zero guess) is the right-hand side, read once, k_dinv_apply leaves its
+// copy of type T in b; x64: the last kernel writes the result there in fp64 instead of back to x
+template <typename T>
+static int mg_smooth_fused(ksfd_handle *h, MGLevel &L, double shift, const T *b, T *x, bool zero_init, double ratio, const double *b64 = nullptr, double *x64 = nullptr)
+{
+    int rc;
+    const int F = L.G.F;
+    MGVecs<T> &V = L.vecs<T>();
+    const double lmax = L.lam_max, lmin = lmax / ratio;
+    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
+    const double rho0 = 1.0 / sig1, rhon = 1.0 / (2.0 * sig1 - rho0);
+    KSmoothT<T> S = KSmoothT<T>{};
+    S.dinv = L.dinv; S.x = x; S.c1 = rhon * rho0; S.c2 = 2.0 * rhon / delta;
+    if (zero_init) {
+        const double by = ((b64 ? 8.0 + sizeof(T) : sizeof(T)) * F + sizeof(T) * F + 4.0 * F * F) * (double)L.G.nloc;
+        if (b64) mg_dinv_apply(h, L, by, b64, 1.0 / theta, V.d, (T *)nullptr, const_cast<T *>(b));
+        else mg_dinv_apply(h, L, by, b, 1.0 / theta, V.d);
+        S.rr = b; S.x_has_d = 1;
+    } else {
+        S.out2 = V.d; S.scale = 1.0 / theta;
+        if ((rc = mg_op<T>(h, L, x, 5, shift, V.r, b, &S))) return rc;
+        S.rr = V.r; S.x_has_d = 0;
+    }
+    S.x64 = x64;
+    return mg_op<T>(h, L, V.d, 6, shift, nullptr, nullptr, &S);
+}
+
 // Chebyshev smoothing of A x = b on level L with Dinv; nu sweeps; eigen-interval [lmax/ratio, lmax]
 static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, double *x, int nu, bool zero_init, double ratio)
 {
     // Chebyshev iteration in the "direction" form:  d_0 = Dinv r_0 / theta ; x += d_k ; r -= A d_k ;
     // d_{k+1} = c1 d_k + c2 Dinv r.   nu sweeps = nu updates of x = nu-1 operator applications (+1 for a nonzero guess).
     // Fusions: a zero guess writes x = d_0 directly; the last sweep folds "x += d_old + d_new" into one kernel.
+    if (nu == 2 && mg_can_fuse(h, L)) return mg_smooth_fused(h, L, shift, b, x, zero_init, ratio);    // the default V(2,2) sweeps
     int rc;
     const int F = L.G.F;
     const int nb = point_blocks(L.G);
     const double lmax = L.lam_max, lmin = lmax / ratio;
     const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
     const long long off = L.kv.off;     // owned rows start here inside a (ghosted) plane
-    if (nu == 2 && mg_can_fuse(h, L)) {
-        // the default V(2,2) sweeps with the smoother algebra in the Jacobian-action epilogues: 2 launches instead of 3 (zero guess)
-        // or 4 (correction), and the residual / A d round trips through memory disappear (modes 5 and 6, KSmooth)
-        const double rho0 = 1.0 / sig1, rhon = 1.0 / (2.0 * sig1 - rho0);
-        KSmooth S = KSmooth{};
-        S.dinv = L.dinv; S.x = x; S.c1 = rhon * rho0; S.c2 = 2.0 * rhon / delta;
-        if (zero_init) {
-            mg_dinv_apply(h, L, 8.0 * (2 * F + 0.5 * F * F) * L.G.nloc, b, 1.0 / theta, L.d);
-            S.rr = b; S.x_has_d = 1;
-            return mg_op(h, L, L.d, 6, shift, nullptr, nullptr, &S);
-        }
-        S.out2 = L.d; S.scale = 1.0 / theta;
-        if ((rc = mg_op(h, L, x, 5, shift, L.r, b, &S))) return rc;
-        S.rr = L.r; S.x_has_d = 0;
-        return mg_op(h, L, L.d, 6, shift, nullptr, nullptr, &S);
-    }
+    double *const r = L.v64.r, *const d = L.v64.d;
     const double *res = b;
     if (!zero_init) {
-        if ((rc = mg_op(h, L, x, 2, shift, L.r, b))) return rc;        // r = b - A x
-        res = L.r;
+        if ((rc = mg_op(h, L, x, 2, shift, r, b))) return rc;        // r = b - A x
+        res = r;
     }
-    mg_dinv_apply(h, L, 8.0 * ((zero_init ? 3 : 2) * F + 0.5 * F * F) * L.G.nloc, res, 1.0 / theta, L.d, zero_init ? x : (double *)nullptr);
+    mg_dinv_apply(h, L, 8.0 * ((zero_init ? 3 : 2) * F + 0.5 * F * F) * L.G.nloc, res, 1.0 / theta, d, zero_init ? x : (double *)nullptr);
     bool x_has_d = zero_init;          // x == d_0 already
     double rho = 1.0 / sig1;
     for (int k = 1; k < nu; k++) {
-        if ((rc = mg_op(h, L, L.d, 1, shift, L.Ad, nullptr))) return rc;
+        if ((rc = mg_op<double>(h, L, d, 1, shift, L.Ad, nullptr))) return rc;
         const double rhon = 1.0 / (2.0 * sig1 - rho);
-        const double *rsrc = (zero_init && k == 1) ? b : L.r;             // first sweep from a zero guess: r_0 = b, never copied
+        const double *rsrc = (zero_init && k == 1) ? b : r;             // first sweep from a zero guess: r_0 = b, never copied
         if (k == nu - 1) {
             Scope sc(h, KC_MG, 8.0 * (5 * F + 0.5 * F * F) * L.G.nloc);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_last<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, rsrc + off, (const double *)(L.d + off), (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / delta, x_has_d ? 1 : 0));
+            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_last<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, rsrc + off, (const double *)(d + off), (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / delta, x_has_d ? 1 : 0));
             x_has_d = true;
         } else {
-            if (rsrc != L.r) HIPCHK(h, hipMemcpyAsync(L.r, b, sizeof(double) * (size_t)L.vlen, hipMemcpyDeviceToDevice, h->st));
+            if (rsrc != r) HIPCHK(h, hipMemcpyAsync(r, b, sizeof(double) * (size_t)L.vlen, hipMemcpyDeviceToDevice, h->st));
             if (x_has_d && k == 1) { /* x already holds d_0: the step kernel adds d to x, so undo by starting x at 0 */
                 HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)L.vlen, h->st));
             }
             Scope sc(h, KC_MG, 8.0 * (7 * F + 0.5 * F * F) * L.G.nloc);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_step<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, L.r + off, L.d + off, (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / delta));
+            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_step<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, r + off, d + off, (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / delta));
             x_has_d = false;
         }
         rho = rhon;
     }
     if (!x_has_d) {
         // x += d (only reached when nu == 1 with a nonzero guess, or after k_cheb_step sweeps)
-        const double *xs[2] = { x, L.d };
+        const double *xs[2] = { x, d };
         KLin LL;
         for (int t = 0; t < 6; t++) { LL.x[t] = t < 2 ? xs[t] : nullptr; LL.a[t] = t < 2 ? 1.0 : 0.0; }
         Scope sc(h, KC_MG, 24.0 * L.vlen);
@@ -352,7 +375,8 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
     return KSFD_OK;
 }
 
-static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const double *b, double *x);
+template <typename T>
+static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const T *b, T *x, const double *b64 = nullptr, double *x64 = nullptr);
 
 // Chebyshev sweeps of the coarse solve on the level the cycle ends on: over the whole spectrum, enough for the reduction mg_coarse_tol
 static int mg_coarse_sweeps(const ksfd_handle *h, const MGLevel &L)
@@ -361,24 +385,37 @@ static int mg_coarse_sweeps(const ksfd_handle *h, const MGLevel &L)
     return std::min(std::max(sweeps, 4), h->mg_ncoarse);
 }
 
-// coarse-grid correction of level l: restrict L.r, recurse, prolong-add into x
-static int mg_coarse_correction(ksfd_handle *h, size_t l, double shift, double *x)
+// coarse-grid correction of level l, vectors stored in T and those of level l + 1 in TC: restrict r, recurse, prolong-add into x
+template <typename T, typename TC>
+static int mg_coarse_correction_in(ksfd_handle *h, size_t l, double shift, T *x)
 {
     int rc;
     MGLevel &L = h->mg[l], &Lc = h->mg[l + 1];
-    if ((rc = mg_halo(h, L, L.r, L.G.F))) return rc;                 // restriction reads fine rows -1 and sloc
+    MGVecs<T> &V = L.vecs<T>();
+    MGVecs<TC> &Vc = Lc.vecs<TC>();
+    const int F = L.G.F;
+    const double sf = sizeof(T), sk = sizeof(TC);
+    if ((rc = mg_halo(h, L, V.r, F))) return rc;                      // restriction reads fine rows -1 and sloc
     {
-        Scope sc(h, KC_MG, 8.0 * L.G.F * (L.G.nloc + Lc.G.nloc));
-        mg_launch_restrict(h, L, Lc, L.G.F, L.r, Lc.b);
+        Scope sc(h, KC_MG, F * (sf * L.G.nloc + sk * Lc.G.nloc));
+        mg_launch_restrict(h, L, Lc, F, (const T *)V.r, Vc.b);
     }
-    if ((rc = mg_vcycle(h, l + 1, shift, Lc.b, Lc.x))) return rc;
-    if ((rc = mg_halo(h, Lc, Lc.x, L.G.F))) return rc;               // prolongation reads coarse row sloc_c
+    if ((rc = mg_vcycle<TC>(h, l + 1, shift, Vc.b, Vc.x))) return rc;
+    if ((rc = mg_halo(h, Lc, Vc.x, F))) return rc;                    // prolongation reads coarse row sloc_c
     {
-        Scope sc(h, KC_MG, 8.0 * L.G.F * (2 * L.G.nloc + Lc.G.nloc));
-        mg_launch_prolong(h, L, Lc, L.G.F, Lc.x, x);
+        Scope sc(h, KC_MG, F * (2.0 * sf * L.G.nloc + sk * Lc.G.nloc));
+        mg_launch_prolong(h, L, Lc, F, (const TC *)Vc.x, x);
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;
+}
+// ... in the storage type of the next level: below fp32 vectors it keeps fp32 ones where it can (mg_f32) and the transfer kernels convert
+// at the border to fp64; below fp64 vectors everything is fp64
+template <typename T>
+static int mg_coarse_correction(ksfd_handle *h, size_t l, double shift, T *x)
+{
+    if constexpr (std::is_same<T, float>::value) if (mg_f32(h, l + 1)) return mg_coarse_correction_in<T, float>(h, l, shift, x);
+    return mg_coarse_correction_in<T, double>(h, l, shift, x);
 }
 
 // everything below level 0 touches only fixed buffers: capture it once per shift into a hipGraph and replay it (a V cycle has ~15
@@ -416,104 +453,44 @@ static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool 
     return KSFD_OK;
 }
 
-static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const double *b, double *x)
+// ------------------------------------------------------------------------------------------------
+// Level l of the V cycle, level vectors (x, b, r, d) stored in T; the arithmetic inside the kernels is fp64 either way.
+// Why fp32 LEVEL VECTORS are legitimate: a V cycle is a preconditioner: GMRES sees the true fp64 residual of the real system whatever
+// the cycle returns, and the cycle is bandwidth-bound -- at 4096^2 x 3 fields an iteration moves ~82 planes of 134 MB through level 0
+// alone, two thirds of them level vectors.  Used when the step's ksp_rtol >= 1e-7 (ksfd_step; the parity tests at 1e-11 keep the fp64
+// cycle), 2-D, one rank or slab ranks (a float plane travels through the double-typed transport as half as many doubles), V(2,2) with
+// the fused smoother (mg_cycle32_ok).  The fp64 right-hand side is read once (k_dinv_apply leaves its fp32 copy), the last smoothing
+// kernel writes the result in fp64 (KSmoothT::x64); levels below the last f32 one run with T = double, the transfer kernels convert
+// at that border.
+// b -> x are the level's own vectors of type T, except on level 0: T = double: the caller's vectors; T = float: the level's, with the
+// caller's fp64 right-hand side in b64 and the result going to x64.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const T *b, T *x, const double *b64, double *x64)
 {
     int rc;
+    constexpr bool f32 = std::is_same<T, float>::value;
     MGLevel &L = h->mg[l];
-    if (l == mg_end(h)) {
+    // the level the cycle ends on has fp64 vectors (mg_f32): the exact solve, or Chebyshev sweeps over the whole spectrum
+    if constexpr (!f32) if (l == mg_end(h)) {
         if (h->mgc.kind == 1 && h->mgc.ready) return mgc_apply(h, L, b, x);
         return mg_smooth(h, L, shift, b, x, mg_coarse_sweeps(h, L), true, L.ratio);
     }
-    if ((rc = mg_smooth(h, L, shift, b, x, h->mg_nu, true, h->mg_ratio))) return rc;
-    if ((rc = mg_op(h, L, x, 2, shift, L.r, b))) return rc;
+    // nu sweeps before and after the correction; fp32 vectors have the fused V(2,2) pair only
+    auto smooth = [&](bool zero_init) {
+        if constexpr (f32) return mg_smooth_fused(h, L, shift, b, x, zero_init, h->mg_ratio, zero_init ? b64 : nullptr, zero_init ? nullptr : x64);
+        else return mg_smooth(h, L, shift, b, x, h->mg_nu, zero_init, h->mg_ratio);
+    };
+    if ((rc = smooth(true))) return rc;
+    if ((rc = mg_op<T>(h, L, x, 2, shift, L.vecs<T>().r, b))) return rc;
     if (l == 0 && h->mg_use_graph && !h->capturing) {
-        if ((rc = mg_coarse_graph(h, shift, x, false, [&]() { return mg_coarse_correction(h, 0, shift, x); }))) return rc;
+        if ((rc = mg_coarse_graph(h, shift, x, f32, [&]() { return mg_coarse_correction(h, 0, shift, x); }))) return rc;
     } else if ((rc = mg_coarse_correction(h, l, shift, x))) return rc;
-    return mg_smooth(h, L, shift, b, x, h->mg_nu, false, h->mg_ratio);
+    return smooth(false);
 }
 
-// ------------------------------------------------------------------------------------------------
-// The same V(2,2) cycle with fp32 LEVEL VECTORS (x, b, r, d of every f32 level; the arithmetic inside the kernels stays fp64).
-// A V cycle is a preconditioner: GMRES sees the true fp64 residual of the real system whatever the cycle returns, and the cycle is
-// bandwidth-bound -- at 4096^2 x 3 fields an iteration moves ~82 planes of 134 MB through level 0 alone, two thirds of them level
-// vectors.  Used when the step's ksp_rtol >= 1e-7 (ksfd_step; the parity tests at 1e-11 keep the fp64 cycle), 2-D, one rank or slab
-// ranks (a float plane travels through the double-typed transport as half as many doubles), V(2,2) with the fused smoother.  The fp64 right-hand side is read once (k_dinv_apply leaves its fp32 copy), the last smoothing
-// kernel writes the result in fp64 (KSmoothT::x64); levels below the last f32 one run the fp64 code above, the transfer kernels
-// convert at that border.
-// ------------------------------------------------------------------------------------------------
-static int mg_op32(ksfd_handle *h, MGLevel &L, const float *v, int mode, double shift, float *out, const float *yadd, const KSmoothT<float> *sm)
-{
-    const KGeom &G = L.G;
-    if (h->ring) { int rch = mg_halo(h, L, const_cast<float *>(v), G.F); if (rch) return rch; }
-    const JvpSys Y = mg_sys(h, L);
-    const float *c32 = Y.coef32;                                  // fp32 level vectors: every level reads its fp32 copy where it has one
-    // planes moved (in units of 8 B per point): coefficients, v, per mode: 2: yadd + out; 5: yadd, Dinv, r, d; 6: Dinv, rr, x in and out
-    const double by = ((c32 ? 4.0 : 8.0) * (3 + h->P.nlig) + 4.0 * G.F + (mode == 2 ? 8.0 * G.F : 12.0 * G.F + 4.0 * G.F * G.F + ((sm && sm->x64) ? 4.0 * G.F : 0.0))) * (double)G.nloc;
-    const KStrips K = strips_for(G, h->yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
-    Scope sc(h, Y.cls, by);
-    auto launch = [&](auto *C) { sm ? jvp2d_launch<true>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, *sm, nullptr) : jvp2d_launch<false>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, KSmooth{}, nullptr); };
-    if (c32) launch(c32); else launch(Y.coef);
-    HIPCHK(h, hipGetLastError());
-    return KSFD_OK;
-}
-
-static int mg_vcycle32(ksfd_handle *h, size_t l, double shift, const double *b64, double *x64);
-
-// coarse-grid correction of an f32 level: restrict r32, recurse in the precision of the next level, prolong-add into x32
-static int mg_coarse_correction32(ksfd_handle *h, size_t l, double shift)
-{
-    int rc;
-    MGLevel &L = h->mg[l], &Lc = h->mg[l + 1];
-    const int F = L.G.F;
-    const bool c32 = mg_f32(h, l + 1);
-    if ((rc = mg_halo(h, L, L.r32, F))) return rc;                    // restriction reads fine rows -1 and sloc
-    {
-        Scope sc(h, KC_MG, F * (4.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
-        if (c32) mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b32);
-        else mg_launch_restrict2d(h, L, Lc, F, (const float *)L.r32, Lc.b);
-    }
-    if (c32) rc = mg_vcycle32(h, l + 1, shift, nullptr, nullptr);
-    else rc = mg_vcycle(h, l + 1, shift, Lc.b, Lc.x);
-    if (rc) return rc;
-    if ((rc = c32 ? mg_halo(h, Lc, Lc.x32, F) : mg_halo(h, Lc, Lc.x, F))) return rc;      // prolongation reads coarse row sloc_c
-    {
-        Scope sc(h, KC_MG, F * (8.0 * L.G.nloc + (c32 ? 4.0 : 8.0) * Lc.G.nloc));
-        if (c32) mg_launch_prolong2d(h, L, Lc, F, (const float *)Lc.x32, L.x32);
-        else mg_launch_prolong2d(h, L, Lc, F, (const double *)Lc.x, L.x32);
-    }
-    HIPCHK(h, hipGetLastError());
-    return KSFD_OK;
-}
-
-// level l of the fp32 cycle.  l = 0: right-hand side b64 and result x64 in fp64 (the caller's vectors); l > 0: L.b32 -> L.x32.
-static int mg_vcycle32(ksfd_handle *h, size_t l, double shift, const double *b64, double *x64)
-{
-    int rc;
-    MGLevel &L = h->mg[l];
-    const int F = L.G.F;
-    const double lmax = L.lam_max, lmin = lmax / h->mg_ratio;
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
-    const double rho0 = 1.0 / sig1, rhon = 1.0 / (2.0 * sig1 - rho0);
-    KSmoothT<float> S = KSmoothT<float>{};
-    S.dinv = L.dinv; S.x = L.x32; S.c1 = rhon * rho0; S.c2 = 2.0 * rhon / delta;
-    // pre-smoothing from a zero guess: d0 = Dinv b / theta (+ the fp32 copy of b on level 0); then x = d0 + d1 in the epilogue of A d0
-    {
-        const double by = ((b64 ? 8.0 + 4.0 : 4.0) * F + 4.0 * F + 4.0 * F * F) * (double)L.G.nloc;
-        if (b64) mg_dinv_apply(h, L, by, b64, 1.0 / theta, L.d32, (float *)nullptr, L.b32);
-        else mg_dinv_apply(h, L, by, (const float *)L.b32, 1.0 / theta, L.d32);
-    }
-    S.rr = L.b32; S.x_has_d = 1;
-    if ((rc = mg_op32(h, L, L.d32, 6, shift, nullptr, nullptr, &S))) return rc;
-    if ((rc = mg_op32(h, L, L.x32, 2, shift, L.r32, L.b32, nullptr))) return rc;
-    if (l == 0 && h->mg_use_graph && !h->capturing) {
-        if ((rc = mg_coarse_graph(h, shift, L.x32, true, [&]() { return mg_coarse_correction32(h, 0, shift); }))) return rc;
-    } else if ((rc = mg_coarse_correction32(h, l, shift))) return rc;
-    // post-smoothing: r = b - A x and d0 = Dinv r / theta in one launch, x += d0 + d1 in the next (level 0: into the caller's fp64 vector)
-    S.out2 = L.d32; S.scale = 1.0 / theta;
-    if ((rc = mg_op32(h, L, L.x32, 5, shift, L.r32, L.b32, &S))) return rc;
-    S.rr = L.r32; S.x_has_d = 0; S.x64 = x64;
-    return mg_op32(h, L, L.d32, 6, shift, nullptr, nullptr, &S);
-}
+// this handle has a cycle with fp32 level vectors: they exist on level 0, and the V(2,2) pair with the fused smoother is what runs on them
+static bool mg_cycle32_ok(const ksfd_handle *h) { return h->mg_fp32 && h->mg[0].f32 && h->mg_nu == 2 && mg_can_fuse(h, h->mg[0]); }
 
 // out = M^-1 in  (one V cycle)
 static int mg_precond(ksfd_handle *h, double shift, const double *in, double *out)
@@ -521,6 +498,7 @@ static int mg_precond(ksfd_handle *h, double shift, const double *in, double *ou
     int rc;
     if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
     if (h->mg_shift != shift && (rc = mg_setup_shift(h, shift))) return rc;
-    if (h->mg_use32 && h->mg_fp32 && h->mg[0].f32 && h->mg_nu == 2 && mg_can_fuse(h, h->mg[0])) return mg_vcycle32(h, 0, shift, in, out);
-    return mg_vcycle(h, 0, shift, in, out);
+    MGVecs<float> &V = h->mg[0].v32;
+    if (h->mg_use32 && mg_cycle32_ok(h)) return mg_vcycle<float>(h, 0, shift, V.b, V.x, in, out);
+    return mg_vcycle<double>(h, 0, shift, in, out);
 }

@@ -98,7 +98,7 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
         p.use_poly = h->poly_deg >= 1 && h->poly_max_deg >= 1;
     }
     p.use_async = ksfd_ctl::pipelined_allowed(in, r, p.use_poly);
-    h->mg_use32 = opts->ksp_rtol >= 1e-7;          // fp32 level vectors inside the V cycle (mg_vcycle32); tight tolerances keep fp64
+    h->mg_use32 = opts->ksp_rtol >= 1e-7;          // fp32 level vectors inside the V cycle (mg_vcycle<float>); tight tolerances keep fp64
     p.fuse_stage = (fused_ok(h) || (strip3d_ok(h) && h->rhs3d_strip)) && h->P.nlig <= 4 && h->fuse_stage;
     // Initial guesses for the spectral stage solves from the earlier stages of the step (A Y_j = b_j is known): the right-hand
     // sides of a step are nearly dependent -- b_1 = c b_0 to ~1e-3, later ones to a few per cent (CPU experiment with the oracle)

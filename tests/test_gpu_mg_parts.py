@@ -109,7 +109,7 @@ class Case:
 
     def levels(self, shift, tune=0, dtype=np.float64, copies=0):
         """reference levels from the downloaded planes, blocks and bounds.  copies: levels 0 .. copies - 1 on their fp32 coefficient copy,
-        the planes the cycle with fp32 level vectors reads there (mg_op32)"""
+        the planes the cycle with fp32 level vectors reads there (mg_op<float>)"""
         out = []
         for l, (inf, D) in enumerate(self.setup(shift, tune)):
             C = self.coef(l, tune)[1] if (l < copies and self.coef(l, tune)[1] is not None) else self.planes(l, tune)
@@ -393,7 +393,7 @@ def test_level_operator_fp32(name):
     for l in range(c.nlev):
         if not c.info[l]['f32']:
             continue
-        C = c.coef(l)[1].astype(LD)                          # mg_op32 reads the fp32 copy on every level that has one
+        C = c.coef(l)[1].astype(LD)                          # mg_op<float> reads the fp32 copy on every level that has one
         y = np.random.default_rng(101 + l).standard_normal((c.F,) + c.grid(l))
         v = c.inputs(l, 105 + l)[0][1]
         ref = y.astype(LD) - mr.op_apply(C, v.astype(LD), c.h(l), c.lig, S_CYCLE)
