@@ -277,6 +277,24 @@ int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_max, int32_t 
  * KSFD_EINVAL, nothing changed: kind 1 on a handle with a halo transport, without a hierarchy, when the chosen level has more than
  * KSFD_MG_DIRECT_MAX unknowns or no level qualifies, max_unknowns > KSFD_MG_DIRECT_MAX. */
 int ksfd_set_mg_coarse(ksfd_handle *h, int32_t kind, int32_t max_unknowns);
+/* Coarse-level agglomeration of the multigrid hierarchy on slab ranks (handles with a halo transport, 2-D and 3-D).  Without it the
+ * hierarchy ends where a rank would keep fewer than 4 slow units (4096^2 on 8 ranks: 32^2 instead of 8^2), and the Chebyshev solve on
+ * that level needs many sweeps, each with a halo exchange.  With it the coarse levels are REPLICATED: every rank holds the whole level
+ * and computes it redundantly with the wrap-index kernels of a single rank -- no ghost units, no halo exchange, no all-reduce in its
+ * norms -- and coarsening goes on by the single-rank rule (even extents, >= 8 points per axis after halving).
+ * max_points = 0: off (default): level list and every bit are those of a handle that never made the call.
+ * max_points > 0: every level below level 0 whose GLOBAL point count is <= max_points is replicated, and, whatever max_points says,
+ * the level the 4-units rule refuses is replicated instead of ending the hierarchy (1 = "replicate only where the slab rule forces it").
+ * Across the border the restriction is a launch into this rank's slice of a zeroed whole-level vector and one all-reduce (sum) of that
+ * vector -- the same bits on every rank; the prolongation reads the whole coarse vector with wrapped global indices, without
+ * communication; the coefficient planes cross the same way, one all-reduce of 3 + nlig planes per set-up.  Replicated levels keep fp64
+ * vectors and planes.  Launches stay eager, nothing joins the checkpoint.  What the all-reduce costs between devices against the halo
+ * exchanges and sweeps it saves has NOT been measured: no timing claim is made.
+ * The call is collective, every rank passes the same value.  It frees and rebuilds the hierarchy, so the hierarchy counts as not set up
+ * afterwards (as after ksfd_mg_part).  On a handle without a halo transport: KSFD_OK, nothing changes.
+ * KSFD_EINVAL, nothing changed: a negative value, a 1-D handle with a transport, a handle without a hierarchy.
+ * ksfd_set_mg_coarse kind 1 stays refused on handles with a transport. */
+int ksfd_set_mg_agglomerate(ksfd_handle *h, int64_t max_points);
 typedef struct ksfd_mg_coarse_info { int32_t kind, level, nlevels, F; int64_t n[3]; int64_t unknowns;
                                      int32_t factorizations, solves, fallbacks, reserved; } ksfd_mg_coarse_info;
 /* valid with kind 0 too: describes the level the cycle ends on; the counters run over the life of the handle */
@@ -291,7 +309,10 @@ int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double 
  * every storage-type pair, mg_halo, mg_op in both storage types, mg_dinv_apply, mg_smooth, mg_precond), never through a kernel launch of its own, so a
  * wrong launch argument shows.  Host vectors are SoA of the level (x fastest, field slowest), OWNED points only: F * points doubles,
  * points = ksfd_mg_level_info_t.points.  fp32 operands are rounded to float on the host before upload and come back as doubles.
- * Handles with a halo transport: every call is collective, each rank passes its slab of the level (sloc slow units).
+ * Handles with a halo transport: every call is collective, each rank passes its slab of the level (sloc slow units).  A REPLICATED level
+ * (ksfd_set_mg_agglomerate) is taken and returned WHOLE on every rank: ksfd_mg_level_info reports sloc = the global slow extent and
+ * points = the whole level there, nlevels / end_level count the replicated levels, and RESTRICT / PROLONG_ADD across the border run
+ * slab <-> whole level (RESTRICT returns the gathered coarse vector, the same bits on every rank).
  * Both calls work at the resident state (its coefficient planes are made and restricted if they are not current) and leave the state and
  * what the stepper remembers from step to step untouched.  After either call the hierarchy counts as NOT set up: shift forgotten, captured
  * graph dropped, power-iteration vectors forgotten -- so the next real set-up starts its power iteration cold, as on a fresh handle, and so

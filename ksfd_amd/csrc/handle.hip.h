@@ -32,6 +32,8 @@ struct MGLevel {
     double *Ad = nullptr, *dG = nullptr;
     float *coef32 = nullptr;   // fp32 copy of the coefficient planes of a coarse f32 level (level 0 uses the handle's)
     bool f32 = false;          // this level can run the fp32 cycle (2-D strip kernel, not the coarsest level)
+    bool rep = false;          // slab ranks: every rank holds this WHOLE level and computes it redundantly (ksfd_set_mg_agglomerate): no ghost
+                               // units, no halo exchange, the slow axis wraps in the kernels, norms are local
     double *pv = nullptr;      // power-iteration vector of Dinv*A, kept from one set-up to the next (warm start)
     double pv_norm = 0.0;      // its norm; 0 = no vector yet
     double lam_max = 2.3;
@@ -244,6 +246,7 @@ struct ksfd_handle {
     bool mg_ok = false;          // hierarchy exists (2-D, single rank, >= 2 levels)
     double mg_shift = -1.0;      // shift the block diagonals / eigen-bounds were built for
     bool mg_coef_valid = false;  // coarse coefficient planes match the current frozen state
+    int64_t mg_agg = 0;          // slab ranks: 0 = every level distributed; > 0: coarse levels replicated (mg_agglomerate_plan.h)
     hipGraphExec_t mg_graph = nullptr;   // captured coarse part of the V cycle (levels >= 1) for mg_graph_shift/x
     double mg_graph_shift = -1.0, mg_graph_bytes = 0.0;
     const void *mg_graph_x = nullptr;

@@ -22,6 +22,7 @@
 #include "transport.h"
 #include "step_control.h"
 #include "mg_coarse_plan.h"
+#include "mg_agglomerate_plan.h"
 
 #include "handle.hip.h"
 #include "ops.hip.h"
@@ -794,6 +795,48 @@ extern "C" int ksfd_set_mg_coarse(ksfd_handle *h, int32_t kind, int32_t max_unkn
     if (h->mg_graph) { HIPCHK(h, hipStreamSynchronize(h->st)); hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
     return KSFD_OK;
 }
+extern "C" int ksfd_set_mg_agglomerate(ksfd_handle *h, int64_t max_points)
+{
+    if (!h) return KSFD_EINVAL;
+    if (max_points < 0) return fail(h, KSFD_EINVAL, "mg_agglomerate: max_points = %lld is negative", (long long)max_points);
+    if (!h->ring) return KSFD_OK;                        // one rank without a transport: every level is whole already
+    if (h->G.dim == 1) return fail(h, KSFD_EINVAL, "mg_agglomerate: 2-D and 3-D slabs only (this handle is 1-D)");
+    if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_agglomerate: this handle has no multigrid hierarchy");
+    hipSetDevice(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    // free and rebuild; every rank must come out with the same hierarchy (an allocation that failed on one rank only would leave the
+    // others waiting in a collective), so the ranks agree on the outcome and fall back to the previous setting together
+    const int64_t before = h->mg_agg;
+    int own_rc = KSFD_OK;
+    std::string own_err;
+    bool failed = false;
+    auto rebuild = [&](int64_t agg) -> int {
+        mg_free(h);
+        h->mg_agg = agg;
+        h->mg_coef_valid = false; h->mg_shift = -1.0; h->mg_graph_shift = -1.0;
+        h->dr.valid = false;                             // the recycled subspace belongs to the preconditioner that is gone
+        own_rc = mg_build(h);
+        own_err = h->err;
+        if (!own_rc && !h->mg_ok) own_rc = fail(h, KSFD_EINVAL, "mg_agglomerate: the rebuilt hierarchy has fewer than two levels"), own_err = h->err;
+        double bad = own_rc ? 1.0 : 0.0;
+        if (hipMemcpyAsync(h->dres, &bad, sizeof bad, hipMemcpyHostToDevice, h->st) != hipSuccess || h->tr->allreduce(h->dres, 1, 1, h->st))
+            return fail(h, KSFD_ECOMM, "mg_agglomerate: agreeing on the hierarchy failed: %s", h->tr->error().c_str());
+        if (h->tr->result_on_host()) bad = h->tr->host_result()[0];
+        else if (hipMemcpyAsync(&bad, h->dres, sizeof bad, hipMemcpyDeviceToHost, h->st) != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess)
+            return fail(h, KSFD_EHIP, "mg_agglomerate: reading the agreed outcome failed");
+        HIPCHK(h, hipStreamSynchronize(h->st));
+        failed = bad > 0.5;
+        return KSFD_OK;
+    };
+    int rc = rebuild(max_points);
+    if (rc || !failed) return rc;
+    // this rank's own reason where it has one; a rank whose build went through learns that another's did not
+    const int why_rc = own_rc;
+    const std::string why = own_err;
+    if (rebuild(before) != KSFD_OK || failed) { mg_free(h); h->mg_agg = 0; }
+    if (why_rc) { h->err = why; return why_rc; }
+    return fail(h, KSFD_ENOMEM, "mg_agglomerate: another rank could not build the hierarchy with max_points = %lld", (long long)max_points);
+}
 extern "C" int ksfd_get_mg_coarse_info(ksfd_handle *h, ksfd_mg_coarse_info *info)
 {
     if (!h || !info) return KSFD_EINVAL;
@@ -954,7 +997,9 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
     int rc;
     if ((rc = mgp_begin(h, setup, shift))) { mgp_end(h); return rc; }
     if (setup && part != KSFD_MGP_CYCLE && !mgp_smoothed(h, (size_t)level)) { mgp_end(h); return fail(h, KSFD_EINVAL, "mg_part %d: level %d is solved exactly and has no smoother", (int)part, (int)level); }
-    double *const a = h->t1, *const b = h->t2, *const c = h->t3;     // staging in the level's ghosted layout (no larger than the handle's vectors)
+    // staging in the level's ghosted layout (no larger than the handle's vectors); a replicated level, which may be larger than this
+    // rank's slab, lends its own vectors
+    double *const a = L.rep ? L.v64.b : h->t1, *const b = L.rep ? L.v64.x : h->t2, *const c = L.rep ? L.v64.d : h->t3;
     auto run = [&]() -> int {
         int r;
         switch (part) {
@@ -967,20 +1012,20 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
         case KSFD_MGP_RESTRICT: {
             auto go = [&](auto *fine, auto *coarse) -> int {
                 if ((r = mgp_put(h, L, F, in0, fine)) || (r = mg_halo(h, L, fine, F))) return r;
-                mg_launch_restrict(h, L, Lc, F, fine, coarse);
+                if ((r = mg_launch_restrict(h, L, Lc, F, fine, coarse)) || (r = mg_border_reduce(h, L, Lc, F, coarse))) return r;
                 return mgp_get(h, Lc, F, coarse, out0);
             };
-            if (variant == 0) return go(a, b);
+            if (variant == 0) return Lc.rep ? go(a, Lc.v64.b) : go(a, b);
             if (variant == 2) return go(a, Lc.v32.b);       // what the fp32 coefficient copy of a level is made with
             return cf32 ? go(L.v32.r, Lc.v32.b) : go(L.v32.r, Lc.v64.b);
         }
         case KSFD_MGP_PROLONG_ADD: {
             auto go = [&](auto *fine, auto *coarse) -> int {
                 if ((r = mgp_put(h, L, F, in0, fine)) || (r = mgp_put(h, Lc, F, in1, coarse)) || (r = mg_halo(h, Lc, coarse, F))) return r;
-                mg_launch_prolong(h, L, Lc, F, coarse, fine);
+                if ((r = mg_launch_prolong(h, L, Lc, F, coarse, fine))) return r;
                 return mgp_get(h, L, F, fine, out0);
             };
-            if (variant == 0) return go(a, b);
+            if (variant == 0) return Lc.rep ? go(a, Lc.v64.x) : go(a, b);
             return cf32 ? go(L.v32.x, Lc.v32.x) : go(L.v32.x, Lc.v64.x);
         }
         case KSFD_MGP_OPERATOR: {

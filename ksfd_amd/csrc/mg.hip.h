@@ -8,6 +8,10 @@
 // coarsening on the periodic box, full-weighting restriction, bilinear prolongation, V(nu,nu) cycle, fixed
 // polynomial smoothing on the coarsest grid -- every piece is a fixed linear operator, so plain
 // right-preconditioned GMRES applies.  1-D, 2-D and 3-D, single rank or slab ranks.
+// Slab ranks: every level is distributed like level 0 (ghost units, halo exchange) down to the last level on which a rank keeps >= 4
+// slow units; ksfd_set_mg_agglomerate (opt-in, 2-D and 3-D) continues below it with REPLICATED levels that every rank holds whole and
+// computes redundantly with wrapped indices -- the *_border kernels below carry vectors and coefficient planes across.  What the one
+// all-reduce per cycle costs between devices against the halo exchanges it saves has not been measured.
 #pragma once
 #include "stencil.hip.h"
 
@@ -133,6 +137,106 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add3d(int nplanes, long 
         const long long K1 = (k & 1) ? (wrap ? (K + 1) % nzc : K + 1) : K;
         for (int c = 0; c < nplanes; c++) {
             const double *q = coarse + (long long)c * cplane + coff;
+            const double v = 0.125 * (q[I + nxc * (J + nyc * K)] + q[I1 + nxc * (J + nyc * K)] + q[I + nxc * (J1 + nyc * K)] +
+                                      q[I1 + nxc * (J1 + nyc * K)] + q[I + nxc * (J + nyc * K1)] + q[I1 + nxc * (J + nyc * K1)] +
+                                      q[I + nxc * (J1 + nyc * K1)] + q[I1 + nxc * (J1 + nyc * K1)]);
+            fine[(long long)c * fplane + foff + p] += v;
+        }
+    }
+}
+
+// Transfers across the border between the last distributed level (fine: this rank's slab with its ghost units) and the first replicated
+// level (coarse: the WHOLE level on every rank, no ghost units; ksfd_set_mg_agglomerate).  Same weights as above.
+// Restriction: the rank full-weights its own rows into its slice [row0c, row0c + nyf/2) of the whole coarse vector and writes zeros
+// everywhere else, so that the sum over the ranks (the transport's all-reduce; adding zeros is exact) is the gathered coarse vector,
+// the same bits on every rank.  The fine ghost rows must be current and the slab starts on an even global row.  nycg: global coarse rows.
+template <typename TF = double>
+__global__ void __launch_bounds__(KSFD_BLOCK) k_restrict2d_border(int nplanes, long long nxf, long long nyf, long long row0c, long long nycg,
+                                                                  const TF *__restrict__ fine, long long fplane, long long foff,
+                                                                  double *__restrict__ coarse, long long cplane)
+{
+    const long long nxc = nxf >> 1, nyc = nyf >> 1, nc = nxc * nycg;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nc; p += stride) {
+        const long long I = p % nxc, J = p / nxc - row0c;
+        const bool own = J >= 0 && J < nyc;
+        const long long i0 = 2 * I, j0 = 2 * J;
+        const long long im = (i0 + nxf - 1) % nxf, ip = (i0 + 1) % nxf, jm = j0 - 1, jp = j0 + 1;
+        for (int c = 0; c < nplanes; c++) {
+            double s = 0.0;
+            if (own) {
+                const TF *f = fine + (long long)c * fplane + foff;
+                s = 0.25 * (double)f[i0 + nxf * j0] +
+                    0.125 * ((double)f[im + nxf * j0] + (double)f[ip + nxf * j0] + (double)f[i0 + nxf * jm] + (double)f[i0 + nxf * jp]) +
+                    0.0625 * ((double)f[im + nxf * jm] + (double)f[ip + nxf * jm] + (double)f[im + nxf * jp] + (double)f[ip + nxf * jp]);
+            }
+            coarse[(long long)c * cplane + p] = s;
+        }
+    }
+}
+// Prolongation: the rank interpolates its own fine rows [row0f, row0f + nyf) from the whole coarse vector with wrapped global indices
+template <typename TF = double>
+__global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add2d_border(int nplanes, long long nxf, long long nyf, long long row0f, long long nycg,
+                                                                     const double *__restrict__ coarse, long long cplane,
+                                                                     TF *__restrict__ fine, long long fplane, long long foff)
+{
+    const long long nxc = nxf >> 1, nf = nxf * nyf;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nf; p += stride) {
+        const long long i = p % nxf, j = row0f + p / nxf;
+        const long long I = i >> 1, J = j >> 1;
+        const long long I1 = (i & 1) ? (I + 1) % nxc : I;
+        const long long J1 = (j & 1) ? (J + 1) % nycg : J;
+        for (int c = 0; c < nplanes; c++) {
+            const double *q = coarse + (long long)c * cplane;
+            const double v = 0.25 * (q[I + nxc * J] + q[I1 + nxc * J] + q[I + nxc * J1] + q[I1 + nxc * J1]);
+            fine[(long long)c * fplane + foff + p] = (TF)((double)fine[(long long)c * fplane + foff + p] + v);
+        }
+    }
+}
+// ... in 3-D (slab axis z): planes [pl0c, pl0c + nzf/2) of nzcg coarse planes; fine planes [pl0f, pl0f + nzf)
+__global__ void __launch_bounds__(KSFD_BLOCK) k_restrict3d_border(int nplanes, long long nxf, long long nyf, long long nzf, long long pl0c, long long nzcg,
+                                                                  const double *__restrict__ fine, long long fplane, long long foff,
+                                                                  double *__restrict__ coarse, long long cplane)
+{
+    const long long nxc = nxf >> 1, nyc = nyf >> 1, nzc = nzf >> 1, nc = nxc * nyc * nzcg;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nc; p += stride) {
+        const long long I = p % nxc, J = (p / nxc) % nyc, K = p / (nxc * nyc) - pl0c;
+        const bool own = K >= 0 && K < nzc;
+        long long xi[3], yj[3], zk[3];
+        xi[1] = 2 * I; xi[0] = (xi[1] + nxf - 1) % nxf; xi[2] = (xi[1] + 1) % nxf;
+        yj[1] = 2 * J; yj[0] = (yj[1] + nyf - 1) % nyf; yj[2] = (yj[1] + 1) % nyf;
+        zk[1] = 2 * K; zk[0] = zk[1] - 1; zk[2] = zk[1] + 1;
+        const double w[3] = { 0.25, 0.5, 0.25 };
+        for (int c = 0; c < nplanes; c++) {
+            double s = 0.0;
+            if (own) {
+                const double *f = fine + (long long)c * fplane + foff;
+#pragma unroll
+                for (int a = 0; a < 3; a++)
+#pragma unroll
+                    for (int b = 0; b < 3; b++)
+#pragma unroll
+                        for (int d = 0; d < 3; d++) s += w[a] * w[b] * w[d] * f[xi[d] + nxf * (yj[b] + nyf * zk[a])];
+            }
+            coarse[(long long)c * cplane + p] = s;
+        }
+    }
+}
+__global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add3d_border(int nplanes, long long nxf, long long nyf, long long nzf, long long pl0f, long long nzcg,
+                                                                     const double *__restrict__ coarse, long long cplane,
+                                                                     double *__restrict__ fine, long long fplane, long long foff)
+{
+    const long long nxc = nxf >> 1, nyc = nyf >> 1, nf = nxf * nyf * nzf;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nf; p += stride) {
+        const long long i = p % nxf, j = (p / nxf) % nyf, k = pl0f + p / (nxf * nyf);
+        const long long I = i >> 1, J = j >> 1, K = k >> 1;
+        const long long I1 = (i & 1) ? (I + 1) % nxc : I, J1 = (j & 1) ? (J + 1) % nyc : J;
+        const long long K1 = (k & 1) ? (K + 1) % nzcg : K;
+        for (int c = 0; c < nplanes; c++) {
+            const double *q = coarse + (long long)c * cplane;
             const double v = 0.125 * (q[I + nxc * (J + nyc * K)] + q[I1 + nxc * (J + nyc * K)] + q[I + nxc * (J1 + nyc * K)] +
                                       q[I1 + nxc * (J1 + nyc * K)] + q[I + nxc * (J + nyc * K1)] + q[I1 + nxc * (J + nyc * K1)] +
                                       q[I + nxc * (J1 + nyc * K1)] + q[I1 + nxc * (J1 + nyc * K1)]);

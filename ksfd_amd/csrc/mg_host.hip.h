@@ -35,39 +35,72 @@ static void mg_free(ksfd_handle *h)
     h->mg_ok = false;
 }
 
+// one level of `rows` slow units by nx (by ny in 3-D) with the physics P: geometry, buffers, and onto the list.  rep: the whole level
+// on every slab rank (rows = the global slow extent): no ghost units, the slow axis wraps in the kernels
+static int mg_push_level(ksfd_handle *h, long long nx, long long ny, long long rows, const KPhys &P, bool rep)
+{
+    const int dim = h->G.dim, nl = h->P.nlig, F = h->G.F;
+    const bool l0 = h->mg.empty();
+    MGLevel L;
+    L.G = h->G; L.G.nx = nx;
+    L.rep = rep;
+    if (rep) { L.G.ng = 0; L.G.wrap_slow = 1; }
+    if (dim == 1) { L.G.nx = rows; L.G.inner = 1; }                      // 1-D: the slab axis is x itself
+    else if (dim == 2) { L.G.ny = rows; L.G.inner = nx; } else { L.G.ny = ny; L.G.nz = rows; L.G.inner = nx * ny; }
+    L.G.sloc = rows;
+    L.G.plane = (rows + 2 * L.G.ng) * L.G.inner; L.G.nloc = rows * L.G.inner;
+    L.P = P;
+    L.kv.plane = L.G.plane; L.kv.off = (long long)L.G.ng * L.G.inner; L.kv.nloc = L.G.nloc; L.kv.nf = F;
+    L.vlen = (int64_t)F * L.G.plane;
+    L.nblk = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 2048);
+    h->mg.push_back(L);                                                  // first: mg_free releases whatever the allocations below leave
+    MGLevel &M = h->mg.back();
+    if (l0) M.coef = h->coef;
+    else if (alloc_d(h, &M.coef, (int64_t)(3 + nl) * M.G.plane) || alloc_d(h, &M.v64.x, M.vlen) || alloc_d(h, &M.v64.b, M.vlen)) return KSFD_ENOMEM;
+    if (hipMalloc((void **)&M.dinv, sizeof(float) * (size_t)F * F * M.G.plane) != hipSuccess || alloc_d(h, &M.v64.r, M.vlen) || alloc_d(h, &M.v64.d, M.vlen) ||
+        alloc_d(h, &M.Ad, M.vlen) || alloc_d(h, &M.dG, M.G.plane) || alloc_d(h, &M.pv, M.vlen)) return KSFD_ENOMEM;
+    double *zero[] = { M.v64.x, M.v64.b, M.v64.r, M.v64.d, M.Ad, M.pv };
+    for (double *z : zero) if (z) hipMemsetAsync(z, 0, sizeof(double) * (size_t)M.vlen, h->st);
+    return KSFD_OK;
+}
+
 static int mg_build(ksfd_handle *h)
 {
-    const int dim = h->G.dim;
-    int nl = h->P.nlig, F = h->G.F;
+    const int dim = h->G.dim, nl = h->P.nlig;
     long long nx = h->G.nx, ny = dim == 3 ? h->G.ny : 1, rows = h->G.sloc;   // rows = local slow units (y rows in 2-D, z planes in 3-D)
     // NOTE: every decision below must be identical on all ranks (the levels exchange halos): use sloc, never slow0.
     // Slab r starts at unit r*sloc; it stays on the coarse grid of level l as long as sloc is divisible by 2^l.
+    // Coarse-level agglomeration (h->mg_agg > 0): the plan says how many levels stay distributed and which replicated ones follow
+    ksfd_ctl::MGPlanLevel plan[64];
+    int nplan = 0, ndist = 0;
+    if (h->mg_agg > 0) {
+        const long long nglob[3] = { dim == 1 ? rows * h->size : nx, dim == 2 ? rows * h->size : ny, dim == 3 ? rows * h->size : 1 };
+        nplan = ksfd_ctl::mg_agglomerate_plan(dim, nglob, h->size, h->ring ? 1 : 0, h->mg_agg, plan, 64);
+        while (ndist < nplan && !plan[ndist].rep) ndist++;
+    }
     KPhys P = h->P;
+    auto coarser = [&]() {
+        nx /= 2; rows /= 2;
+        if (dim == 3) ny /= 2;
+        for (int a = 0; a < 3; a++) { P.inv_h[a] *= 0.5; P.inv_h2[a] *= 0.25; }
+    };
     for (int l = 0;; l++) {
-        MGLevel L;
-        L.G = h->G; L.G.nx = nx;
-        if (dim == 1) { L.G.nx = rows; L.G.inner = 1; }                      // 1-D: the slab axis is x itself
-        else if (dim == 2) { L.G.ny = rows; L.G.inner = nx; } else { L.G.ny = ny; L.G.nz = rows; L.G.inner = nx * ny; }
-        L.G.sloc = rows;
-        L.G.plane = (rows + 2 * L.G.ng) * L.G.inner; L.G.nloc = rows * L.G.inner;
-        L.P = P;
-        L.kv.plane = L.G.plane; L.kv.off = (long long)L.G.ng * L.G.inner; L.kv.nloc = L.G.nloc; L.kv.nf = F;
-        L.vlen = (int64_t)F * L.G.plane;
-        L.nblk = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 2048);
-        if (l == 0) L.coef = h->coef;
-        else if (alloc_d(h, &L.coef, (int64_t)(3 + nl) * L.G.plane) || alloc_d(h, &L.v64.x, L.vlen) || alloc_d(h, &L.v64.b, L.vlen)) return KSFD_ENOMEM;
-        if (hipMalloc((void **)&L.dinv, sizeof(float) * (size_t)F * F * L.G.plane) != hipSuccess || alloc_d(h, &L.v64.r, L.vlen) || alloc_d(h, &L.v64.d, L.vlen) ||
-            alloc_d(h, &L.Ad, L.vlen) || alloc_d(h, &L.dG, L.G.plane) || alloc_d(h, &L.pv, L.vlen)) return KSFD_ENOMEM;
-        double *zero[] = { L.v64.x, L.v64.b, L.v64.r, L.v64.d, L.Ad, L.pv };
-        for (double *z : zero) if (z) hipMemsetAsync(z, 0, sizeof(double) * (size_t)L.vlen, h->st);
-        h->mg.push_back(L);
+        int rc = mg_push_level(h, nx, ny, rows, P, false);
+        if (rc) return rc;
+        if (nplan > 0 && l + 1 == ndist) break;                               // the plan replicates the next level
         // next level: every rank keeps >= 4 slow units (ghost width 2 + the 4th-order star), global grid >= 8 per axis
         const long long rows_glob = rows * h->size;
         if ((dim > 1 && ((nx % 2) || nx / 2 < 8)) || (rows % 2) || rows_glob / 2 < 8 || (h->ring && rows / 2 < 4)) break;
         if (dim == 3 && ((ny % 2) || ny / 2 < 8)) break;
-        nx /= 2; rows /= 2;
-        if (dim == 3) ny /= 2;
-        for (int a = 0; a < 3; a++) { P.inv_h[a] *= 0.5; P.inv_h2[a] *= 0.25; }
+        coarser();
+    }
+    // replicated levels: the global slow extent from here on (the plan's distributed prefix is the list of the loop above)
+    if (nplan > 0 && (int)h->mg.size() != ndist) return fail(h, KSFD_EINVAL, "multigrid: the agglomeration plan and the slab rule disagree on the distributed levels");
+    for (int l = ndist; l < nplan; l++) {
+        coarser();
+        if (l == ndist) rows *= h->size;
+        int rc = mg_push_level(h, nx, ny, rows, P, true);
+        if (rc) return rc;
     }
     h->mg_ok = h->mg.size() >= 2;
     h->mgc.level = (int)h->mg.size() - 1;
@@ -77,7 +110,7 @@ static int mg_build(ksfd_handle *h)
     if (h->mg_ok) {
         for (size_t l = 0; l + 1 < h->mg.size(); l++) {
             MGLevel &L = h->mg[l];
-            if (mg_path(h, L) != JP_STRIP2D) break;
+            if (L.rep || mg_path(h, L) != JP_STRIP2D) break;                 // replicated levels keep fp64 vectors and planes
             const size_t nb = sizeof(float) * (size_t)L.vlen;
             MGVecs<float> &V = L.v32;
             if (hipMalloc((void **)&V.x, nb) != hipSuccess || hipMalloc((void **)&V.b, nb) != hipSuccess ||
@@ -92,11 +125,42 @@ static int mg_build(ksfd_handle *h)
 
 // transfer operators for the storage types of the fine and the coarse vector.  fp64 on both sides: 1-D, 2-D or 3-D by the level geometry;
 // any other pair exists in 2-D only (levels with fp32 vectors, the fp32 coefficient copy)
+// Across the border from the last distributed level Lf to the first replicated one Lc (mg.hip.h: k_restrict2d_border) the restriction
+// is a launch (here) and one all-reduce of the whole coarse vector (mg_border_reduce, which the caller runs behind the launch and
+// outside the launch's Scope: the all-reduce is booked as communication, once), the prolongation a launch; the coarse side is fp64
+static inline bool mg_border(const MGLevel &Lf, const MGLevel &Lc) { return Lc.rep && !Lf.rep; }
+// sum over the ranks of the slices the border restriction left in `coarse` (np planes of Lc); a no-op anywhere but at the border
+static int mg_border_reduce(ksfd_handle *h, const MGLevel &Lf, const MGLevel &Lc, int np, double *coarse)
+{
+    if (!mg_border(Lf, Lc)) return KSFD_OK;
+    Scope sc(h, KC_HALO, 8.0 * np * (double)Lc.G.plane);
+    if (h->tr->allreduce_vec(coarse, (long long)np * Lc.G.plane, h->st)) return fail(h, KSFD_ECOMM, "allreduce failed: %s", h->tr->error().c_str());
+    return KSFD_OK;
+}
+template <typename T> static int mg_border_reduce(ksfd_handle *h, const MGLevel &Lf, const MGLevel &Lc, int, T *)
+{
+    return mg_border(Lf, Lc) ? fail(h, KSFD_EINVAL, "multigrid: a replicated level has fp64 vectors") : KSFD_OK;
+}
 template <typename TF, typename TK>
-static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TF *fine, TK *coarse)
+static int mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TF *fine, TK *coarse)
 {
     constexpr bool f64 = std::is_same<TF, double>::value && std::is_same<TK, double>::value;
     const int nb = point_blocks(Lc.G), dim = f64 ? Lf.G.dim : 2;
+    if (mg_border(Lf, Lc)) {
+        if constexpr (std::is_same<TK, double>::value) {
+            const long long u0c = (long long)h->rank * (Lf.G.sloc / 2);       // first coarse slow unit of this rank's slice
+            if (Lf.G.dim == 2)
+                hipLaunchKernelGGL((k_restrict2d_border<TF>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, u0c, Lc.G.sloc,
+                                   fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane);
+            else if constexpr (f64) {
+                if (Lf.G.dim != 3) return fail(h, KSFD_EINVAL, "multigrid: no replicated levels on a 1-D grid");
+                hipLaunchKernelGGL(k_restrict3d_border, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, u0c, Lc.G.sloc,
+                                   fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane);
+            } else return fail(h, KSFD_EINVAL, "multigrid: fp32 level vectors exist in 2-D only");
+            HIPCHK(h, hipGetLastError());
+            return KSFD_OK;
+        } else return fail(h, KSFD_EINVAL, "multigrid: a replicated level has fp64 vectors");
+    }
     if constexpr (f64) {
         if (dim == 1)
             hipLaunchKernelGGL(k_restrict1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
@@ -108,12 +172,27 @@ static void mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np,
     if (dim == 2)
         hipLaunchKernelGGL((k_restrict2d<TF, TK>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
                            fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+    return KSFD_OK;
 }
 template <typename TK, typename TF>
-static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TK *coarse, TF *fine)
+static int mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TK *coarse, TF *fine)
 {
     constexpr bool f64 = std::is_same<TF, double>::value && std::is_same<TK, double>::value;
     const int nb = point_blocks(Lf.G), dim = f64 ? Lf.G.dim : 2;
+    if (mg_border(Lf, Lc)) {
+        if constexpr (std::is_same<TK, double>::value) {
+            const long long u0f = (long long)h->rank * Lf.G.sloc;             // first fine slow unit of this rank's slab
+            if (Lf.G.dim == 2)
+                hipLaunchKernelGGL((k_prolong_add2d_border<TF>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, u0f, Lc.G.sloc,
+                                   coarse, Lc.G.plane, fine, Lf.G.plane, Lf.kv.off);
+            else if constexpr (f64) {
+                if (Lf.G.dim != 3) return fail(h, KSFD_EINVAL, "multigrid: no replicated levels on a 1-D grid");
+                hipLaunchKernelGGL(k_prolong_add3d_border, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, u0f, Lc.G.sloc,
+                                   coarse, Lc.G.plane, fine, Lf.G.plane, Lf.kv.off);
+            } else return fail(h, KSFD_EINVAL, "multigrid: fp32 level vectors exist in 2-D only");
+            return KSFD_OK;
+        } else return fail(h, KSFD_EINVAL, "multigrid: a replicated level has fp64 vectors");
+    }
     if constexpr (f64) {
         if (dim == 1)
             hipLaunchKernelGGL(k_prolong_add1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
@@ -125,14 +204,15 @@ static void mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, 
     if (dim == 2)
         hipLaunchKernelGGL((k_prolong_add2d<TK, TF>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
                            coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
+    return KSFD_OK;
 }
 
 // ghost rows of a level vector (np field planes) from the ring neighbours.  An fp32 vector travels through the double-typed transport as
-// half as many doubles (nx is even on the levels that have one)
+// half as many doubles (nx is even on the levels that have one).  A replicated level has no ghost rows
 template <typename T>
 static int mg_halo(ksfd_handle *h, MGLevel &L, T *v, int np)
 {
-    if (!h->ring) return KSFD_OK;
+    if (!h->ring || L.rep) return KSFD_OK;
     const long long scale = sizeof(double) / sizeof(T);
     Scope sc(h, KC_HALO, 4.0 * sizeof(T) * np * (double)L.G.inner * 2.0);
     if (h->tr->exchange(reinterpret_cast<double *>(v), np, L.G.plane / scale, L.G.inner / scale, L.G.sloc, L.G.ng, h->st)) return fail(h, KSFD_ECOMM, "halo exchange failed: %s", h->tr->error().c_str());
@@ -190,7 +270,7 @@ static int mg_norm(ksfd_handle *h, MGLevel &L, const double *v, double *nrm)
         else hipLaunchKernelGGL((k_multidot<4, 1>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.kv, v, v, L.vlen, 0, h->part);
     }
     HIPCHK(h, hipGetLastError());
-    int rc = reduce_rows(h, 1, nb, 0);
+    int rc = reduce_rows(h, 1, nb, 0, L.rep);                 // a replicated level: the local sum is the whole one
     if (rc) return rc;
     *nrm = sqrt(h->hres[0]);
     return KSFD_OK;
@@ -205,14 +285,15 @@ static int mg_restrict_coefs(ksfd_handle *h)
         MGLevel &Lf = h->mg[l], &Lc = h->mg[l + 1];
         {
             Scope sc(h, KC_MG, 8.0 * np * (Lf.G.nloc + Lc.G.nloc));
-            mg_launch_restrict(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef);
+            if ((rc = mg_launch_restrict(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef))) return rc;
         }
+        if ((rc = mg_border_reduce(h, Lf, Lc, np, Lc.coef))) return rc;
         if ((rc = mg_halo(h, Lc, Lc.coef, np))) return rc;       // fine ghosts were valid; now the coarse ones are too
         if (Lc.coef32) {
             // the fp32 cycle reads an fp32 copy (the same full weighting of the fine fp64 planes, rounded once)
             {
                 Scope sc(h, KC_MG, np * (8.0 * Lf.G.nloc + 4.0 * Lc.G.nloc));
-                mg_launch_restrict(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef32);
+                if ((rc = mg_launch_restrict(h, Lf, Lc, np, (const double *)Lf.coef, Lc.coef32))) return rc;
             }
             if ((rc = mg_halo(h, Lc, Lc.coef32, np))) return rc;
         }
@@ -282,7 +363,7 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
         if (l == end) {
             int nbr = (int)std::min<long long>((L.G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 256);
             hipLaunchKernelGGL(k_ratio_est, dim3(nbr), dim3(KSFD_BLOCK), 0, h->st, (long long)L.G.nloc, (const float *)(L.dinv + L.kv.off), shift, h->part);
-            if ((rc = reduce_rows(h, 1, nbr, 1))) return rc;
+            if ((rc = reduce_rows(h, 1, nbr, 1, L.rep))) return rc;
             L.ratio = std::max(30.0, 1.5 * L.lam_max * h->hres[0]);
         }
     }
@@ -398,13 +479,14 @@ static int mg_coarse_correction_in(ksfd_handle *h, size_t l, double shift, T *x)
     if ((rc = mg_halo(h, L, V.r, F))) return rc;                      // restriction reads fine rows -1 and sloc
     {
         Scope sc(h, KC_MG, F * (sf * L.G.nloc + sk * Lc.G.nloc));
-        mg_launch_restrict(h, L, Lc, F, (const T *)V.r, Vc.b);
+        if ((rc = mg_launch_restrict(h, L, Lc, F, (const T *)V.r, Vc.b))) return rc;
     }
+    if ((rc = mg_border_reduce(h, L, Lc, F, Vc.b))) return rc;
     if ((rc = mg_vcycle<TC>(h, l + 1, shift, Vc.b, Vc.x))) return rc;
     if ((rc = mg_halo(h, Lc, Vc.x, F))) return rc;                    // prolongation reads coarse row sloc_c
     {
         Scope sc(h, KC_MG, F * (2.0 * sf * L.G.nloc + sk * Lc.G.nloc));
-        mg_launch_prolong(h, L, Lc, F, (const TC *)Vc.x, x);
+        if ((rc = mg_launch_prolong(h, L, Lc, F, (const TC *)Vc.x, x))) return rc;
     }
     HIPCHK(h, hipGetLastError());
     return KSFD_OK;

@@ -29,12 +29,13 @@ static int spin_for(ksfd_handle *h, unsigned long long seq)
     }
 }
 
-// part holds `rows` rows of `nblk` partials; result lands in h->hres[0..rows)
-static int reduce_rows(ksfd_handle *h, int rows, int nblk, int op)
+// part holds `rows` rows of `nblk` partials; result lands in h->hres[0..rows).  local: the partials already cover the whole quantity on
+// every rank (a replicated multigrid level), so slab ranks skip the all-reduce
+static int reduce_rows(ksfd_handle *h, int rows, int nblk, int op, bool local = false)
 {
     // several ranks with a device-side all-reduce (RCCL): a one-block k_publish behind the all-reduce hands the result over
     // the same way; ksfd_amd.dist.open_handle checks that path end to end on a new handle and clears zero_copy if it fails
-    const bool zc = h->zero_copy && !h->capturing && rows <= 128 && (!h->ring || h->tr->device_allreduce());
+    const bool zc = h->zero_copy && !h->capturing && rows <= 128 && (!h->ring || (h->tr->device_allreduce() && !local));
     const bool zc_here = zc && !h->ring;
     h->n_host_sync++;
     const unsigned long long seq = zc ? ++h->pub_seq : 0;
@@ -44,7 +45,7 @@ static int reduce_rows(ksfd_handle *h, int rows, int nblk, int op)
         else hipLaunchKernelGGL(k_reduce_rows, dim3(rows), dim3(KSFD_BLOCK), 0, h->st, h->part, nblk, op, h->dres);
     }
     if (zc_here) { HIPCHK(h, hipGetLastError()); return spin_for(h, seq); }
-    if (h->ring) {
+    if (h->ring && !local) {
         int rc = h->tr->allreduce(h->dres, rows, op, h->st);
         if (rc) return fail(h, KSFD_ECOMM, "allreduce failed: %s", h->tr->error().c_str());
         if (h->tr->result_on_host()) { memcpy(h->hres, h->tr->host_result(), sizeof(double) * rows); return KSFD_OK; }

@@ -28,6 +28,9 @@ struct Transport {
     // fill the 2*ng ghost units of every field plane of vec from the ring neighbours
     virtual int exchange(double *vec, int F, long long plane, long long inner, long long sloc, int ng, hipStream_t st) = 0;
     virtual int allreduce(double *dev, int n, int op, hipStream_t st) = 0;   // op 0 sum, 1 max; in place
+    // in-place sum of a whole device vector over the ranks, result on the device and the same bits on every rank (the multigrid
+    // levels that every rank holds whole: mg_host.hip.h); any length, a transport with a limit moves it in pieces
+    virtual int allreduce_vec(double *dev, long long n, hipStream_t st) = 0;
     virtual bool result_on_host() const { return false; }
     virtual bool device_allreduce() const { return true; }   // allreduce is stream-ordered and leaves the result on the device
     virtual const double *host_result() const { return nullptr; }
@@ -103,6 +106,10 @@ struct RcclTransport : Transport {
     {
         return chk(api.AllReduce(dev, dev, (size_t)n, ncclDouble, op ? ncclMax : ncclSum, comm, st), "ncclAllReduce");
     }
+    int allreduce_vec(double *dev, long long n, hipStream_t st) override
+    {
+        return chk(api.AllReduce(dev, dev, (size_t)n, ncclDouble, ncclSum, comm, st), "ncclAllReduce");
+    }
     bool has_alltoall() const override { return true; }
     int alltoall(const std::vector<A2APiece> &sends, const std::vector<A2APiece> &recvs, hipStream_t st) override
     {
@@ -134,17 +141,21 @@ struct CallbackTransport : Transport {
     size_t a2a_cap = 0;
     double *stage = nullptr;      // pinned: [send_lo | send_hi | recv_lo | recv_hi], each F*ng*inner
     double *hred = nullptr;       // pinned, 128 doubles (as the handle's result buffers)
+    double *vred = nullptr;       // pinned staging of allreduce_vec, grown on demand up to vred_max doubles
+    size_t vred_cap = 0;
+    size_t vred_max = (size_t)1 << 20;       // doubles per piece of allreduce_vec (KSFD_VRED_MAX: experiments and the test of the piece loop)
     size_t chunk = 0;
     bool init(const ksfd_dist *d, int F, long long inner)
     {
         ex = d->exchange; ar = d->allreduce; a2a = d->alltoall; ctx = d->ctx; nranks = d->size;
+        if (getenv("KSFD_VRED_MAX")) vred_max = (size_t)std::max(1LL, atoll(getenv("KSFD_VRED_MAX")));
         if (!ex || !ar) { err = "transport 2 needs exchange and allreduce callbacks"; return false; }
         chunk = (size_t)(F + 2) * 2 * inner;                  // F fields (+2: the 3+n coefficient planes of a coarse level fit too)
         if (hipHostMalloc((void **)&stage, sizeof(double) * chunk * 4, hipHostMallocDefault) != hipSuccess ||
             hipHostMalloc((void **)&hred, sizeof(double) * 128, hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return false; }
         return true;
     }
-    ~CallbackTransport() override { if (stage) hipHostFree(stage); if (hred) hipHostFree(hred); if (a2a_send) hipHostFree(a2a_send); if (a2a_recv) hipHostFree(a2a_recv); }
+    ~CallbackTransport() override { if (stage) hipHostFree(stage); if (hred) hipHostFree(hred); if (vred) hipHostFree(vred); if (a2a_send) hipHostFree(a2a_send); if (a2a_recv) hipHostFree(a2a_recv); }
     bool has_alltoall() const override { return a2a != nullptr; }
     int alltoall(const std::vector<A2APiece> &sends, const std::vector<A2APiece> &recvs, hipStream_t st) override
     {
@@ -199,6 +210,27 @@ struct CallbackTransport : Transport {
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) { err = std::string("allreduce D2H: ") + hipGetErrorString(e); return 1; }
         if (ar(ctx, hred, n, op)) { err = "allreduce callback reported failure"; return 1; }
+        return 0;
+    }
+    int allreduce_vec(double *dev, long long n, hipStream_t st) override
+    {
+        const size_t want = std::min<size_t>((size_t)n, vred_max);
+        if (want > vred_cap) {
+            if (vred) hipHostFree(vred);
+            vred = nullptr; vred_cap = 0;
+            if (hipHostMalloc((void **)&vred, sizeof(double) * want, hipHostMallocDefault) != hipSuccess) { err = "allreduce_vec: hipHostMalloc failed"; return 1; }
+            vred_cap = want;
+        }
+        // pieces of at most vred_max doubles; the copy back of one piece and the copy out of the next are ordered by the stream
+        for (long long o = 0; o < n; o += (long long)vred_cap) {
+            const size_t cnt = (size_t)std::min<long long>(n - o, (long long)vred_cap);
+            hipError_t e = hipMemcpyAsync(vred, dev + o, sizeof(double) * cnt, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) { err = std::string("allreduce_vec D2H: ") + hipGetErrorString(e); return 1; }
+            if (ar(ctx, vred, (int32_t)cnt, 0)) { err = "allreduce callback reported failure"; return 1; }
+            e = hipMemcpyAsync(dev + o, vred, sizeof(double) * cnt, hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) { err = std::string("allreduce_vec H2D: ") + hipGetErrorString(e); return 1; }
+        }
         return 0;
     }
     bool result_on_host() const override { return true; }

@@ -110,7 +110,7 @@ ABI_SYMBOLS = [
     'ksfd_get_profile', 'ksfd_synchronize', 'ksfd_bench_kernel', 'ksfd_set_tuning', 'ksfd_set_mg_params', 'ksfd_set_poly_params',
     'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply', 'ksfd_banded_apply',
     'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity', 'ksfd_krylov_op',
-    'ksfd_set_mg_coarse', 'ksfd_get_mg_coarse_info', 'ksfd_mg_coarse_apply', 'ksfd_mg_level_info', 'ksfd_mg_part',
+    'ksfd_set_mg_agglomerate', 'ksfd_set_mg_coarse', 'ksfd_get_mg_coarse_info', 'ksfd_mg_coarse_apply', 'ksfd_mg_level_info', 'ksfd_mg_part',
 ]
 
 
@@ -182,6 +182,7 @@ def load():
     L.ksfd_basis_rotate.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32]
     L.ksfd_krylov_op.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, C.c_double, C.c_double, dp, dp, dp, C.c_int32]
     L.ksfd_set_mg_coarse.argtypes = [vp, C.c_int32, C.c_int32]
+    L.ksfd_set_mg_agglomerate.argtypes = [vp, C.c_int64]
     L.ksfd_get_mg_coarse_info.argtypes = [vp, C.POINTER(MGCoarseInfo)]
     L.ksfd_mg_coarse_apply.argtypes = [vp, C.c_double, C.c_int32, dp, dp]
     L.ksfd_mg_level_info.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.POINTER(MGLevelInfo)]
@@ -437,6 +438,13 @@ class KSFDHip:
         exact solve (dense LU + explicit inverse, rebuilt per set-up).  max_unknowns > 0: the cycle ends on the finest level below level 0
         with at most that many unknowns (<= MG_DIRECT_MAX), else on the coarsest.  KSFDError(EINVAL) leaves the handle as it was."""
         self._chk(self.L.ksfd_set_mg_coarse(self.h, int(kind), int(max_unknowns)))
+
+    def set_mg_agglomerate(self, max_points):
+        """Coarse-level agglomeration of the multigrid hierarchy on slab ranks (collective: every rank passes the same value).  0: off, the
+        default.  > 0: levels below level 0 with at most that many GLOBAL points, and the level the 4-rows-per-rank rule would refuse,
+        are replicated on every rank and coarsening goes on by the single-rank rule.  The hierarchy is rebuilt.  No effect on a handle
+        without a halo transport; KSFDError(EINVAL) leaves the handle as it was."""
+        self._chk(self.L.ksfd_set_mg_agglomerate(self.h, int(max_points)))
 
     def mg_coarse_info(self):
         """the level the V cycle ends on and the counters of the exact coarse solve over the life of the handle:

@@ -409,6 +409,23 @@ def mg_coarse_from(petsc_args):
     return (0 if kind is None else kind, 0 if nmax is None else nmax)
 
 
+def mg_agglomerate_from(petsc_args):
+    """max_points for KSFDHip.set_mg_agglomerate from -ksfd_mg_agglomerate <points> (0 = off, 1 = replicate only the level the
+    4-rows-per-rank rule of the slab hierarchy would refuse), or None when the list does not name the flag (the handle is left alone)."""
+    a = list(petsc_args)
+    pts = None
+    for i, k in enumerate(a):
+        if k == '-ksfd_mg_agglomerate':
+            nxt = a[i + 1] if i + 1 < len(a) else None
+            try:
+                pts = int(nxt)
+            except (TypeError, ValueError):
+                pts = -1
+            if not 0 <= pts < 2 ** 63:
+                raise ValueError('-ksfd_mg_agglomerate must be a non-negative integer number of points, got %s' % nxt)
+    return pts
+
+
 def _isnum(s):
     try:
         float(s.split(',')[0])

@@ -188,7 +188,7 @@ class KSFDTS:
     default_hmin = 1e-20
 
     def __init__(self, derivs, t0=0.0, dt=0.001, tmax=20, maxsteps=100, rtol=1e-5, atol=1e-5, restart=True,
-                 hmin=None, comm=None, opts=None, rng=None, deflation=None, mg_coarse=None):
+                 hmin=None, comm=None, opts=None, rng=None, deflation=None, mg_coarse=None, mg_agglomerate=None):
         self.derivs = derivs
         self.ks = derivs.ks
         self.comm = comm if comm is not None else derivs.grid.comm
@@ -200,6 +200,8 @@ class KSFDTS:
         self.opts.rtol, self.opts.atol = self.rtol, self.atol
         if deflation is not None:                   # (keep, carry_stages) of -ksfd_ksp_type dgmres: ksfd_amd.options.deflation_from
             self.ks.set_deflation(*deflation)
+        if mg_agglomerate is not None:              # max_points of -ksfd_mg_agglomerate (collective on slab ranks): ksfd_amd.options.mg_agglomerate_from
+            self.ks.set_mg_agglomerate(mg_agglomerate)
         if mg_coarse is not None:                   # (kind, max_unknowns) of -ksfd_mg_coarse: ksfd_amd.options.mg_coarse_from
             self.ks.set_mg_coarse(*mg_coarse)
         self.history = []
