@@ -1,6 +1,7 @@
 // libksfd_hip.so -- the handle: device buffers, solver state, error reporting, HIP-event profiling scopes, tableau and physics tables
 // (part of the single translation unit ksfd_hip.hip, first of its host-side headers: the include list there gives the order)
 #pragma once
+#include "spectral_plan.h"
 // ------------------------------------------------------------------------------------------------
 // kernel classes for the profile
 enum { KC_RHS = 0, KC_JVP, KC_MULTIDOT, KC_GSUPDATE, KC_LINCOMB, KC_BASISAXPY, KC_FINISH, KC_REDUCE,
@@ -40,28 +41,27 @@ struct MGLevel {
     double ratio = 60.0;       // lambda_max/lambda_min estimate (used on the coarsest grid)
 };
 
-// spectral preconditioner (spectral.hip.h / spectral_host.hip.h)
+// spectral preconditioner (spectral.hip.h / spectral_plan.h / spectral_host.hip.h): what spec_build makes of the planner's shape
 struct SpecState {
-    bool ok = false, means_valid = false, tile_major = false;
-    int cols_split = 0;                      // k_spec_cols_split in two phases (spectral.hip.h): 1 = the 2*npair columns of a pair block exceed the LDS (one field pair per block),
-                                             // 2 = the two columns of one pair do too (columns of more than 8192 points: one column per block)
-    KFFTPlan px, py, pz;
-    int dim = 2, lg_cz = 0, pb = 1, nent = 0, lg_rb3 = 0;          // 3-D: z per block of the y kernels, column pairs per block / entries of the z kernel
-    size_t lds_y3 = 0, lds_z3 = 0;
-    int *posz = nullptr, *kzofpos = nullptr;
-    float *lz = nullptr;
-    int rb = 0, npair = 0, nyp = 0;
-    int nch = 1;                             // slab ranks with 3 * 2^j rows (3-D: z planes): 3 chunks of 2^j (spectral_plan.h); else 1
-    size_t lds_rows = 0, lds_cols = 0;
-    kcf *W = nullptr, *W2 = nullptr, *twx = nullptr, *twy = nullptr, *twz = nullptr;     // W: [pair][pos_x][y_local]; W2: after the all-to-all, [rank][pair][own pos][y_local] (nch = 3: [chunk] in front of [pair] in both)
-    int *posy = nullptr, *kyofpos = nullptr;
-    int2 *ytab = nullptr;                    // per y position: (position of -ky, bits of ly[ky]) -- symbol stage of k_spec_cols
-    int lgw = -1;                            // layout of the forward work array (kspec_wt_index)
-    int4 *pairtab = nullptr;          // per block of the column kernel
-    int nxl = 0, nblk_cols = 0, lg_pl = 0;   // owned positions, column-kernel blocks, log2(rows (3-D: planes) per rank and chunk)
-    std::vector<A2APiece> a2a_fwd_s, a2a_fwd_r, a2a_bwd_s, a2a_bwd_r;
-    float *lx = nullptr, *ly = nullptr;
-    double a_rr = 0.0, a_rU[KSFD_MAXL] = { 0 };
+    bool ok = false, means_valid = false;
+    SpecShape shape;
+    // work arrays W: [pair][pos_x][y_local]; W2: after the all-to-all, [rank][pair][own pos][y_local] (nch = 3: [chunk] in front of [pair] in both)
+    kcf *W = nullptr, *W2 = nullptr, *twx = nullptr, *twy = nullptr, *twz = nullptr;
+    int *spos = nullptr, *skof = nullptr;    // slow axis (2-D: y, 3-D: z): position of a wavenumber, wavenumber at a position
+    int2 *ytab = nullptr;                    // per position of the slow axis: (position of -k, bits of its symbol) -- symbol stage of k_spec_cols / k_spec3_z
+    int4 *pairtab = nullptr;                 // SpecTables.pairtab
+    float *lx = nullptr, *ly = nullptr, *lz = nullptr;
+    // the kernel instances this handle launches, chosen once (spec_build raises the dynamic-LDS limit of exactly these)
+    decltype(&k_spec_rows_fwd<double>) k_rows_fwd64 = nullptr;
+    decltype(&k_spec_rows_fwd<float>) k_rows_fwd32 = nullptr;
+    decltype(&k_spec_rows_inv) k_rows_inv = nullptr;
+    decltype(&k_spec_cols<0>) k_cols = nullptr;
+    decltype(&k_spec_cols_split<false>) k_cols_split = nullptr;
+    decltype(&k_spec3_y_fwd<false>) k_y_fwd = nullptr;
+    decltype(&k_spec3_y_inv<false>) k_y_inv = nullptr;
+    decltype(&k_spec3_z<0, false>) k_z = nullptr;
+    std::vector<A2APiece> a2a_fwd_s, a2a_fwd_r, a2a_back_s, a2a_back_r;
+    double a_rr = 0.0, a_rU[KSFD_MAXL] = { 0 };       // means of rho*G_rho, rho*G_Ul (spec_means)
     bool user_off = false;                   // ksfd_set_spectral_params(enable = 0): off until enabled again; a checkpoint restore does not bring it back
 };
 

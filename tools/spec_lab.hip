@@ -44,24 +44,21 @@ struct Lab {
 static void lab_init(Lab &L, int n)
 {
     L.n = n; L.plane = (long long)n * n;
-    if (!spec_plan(n, L.px) || !spec_plan(n, L.py)) { fprintf(stderr, "no plan for %d\n", n); exit(2); }
-    const size_t row_bytes = sizeof(kcf) * spec_sstride(L.px);
-    int rb = (int)std::min<size_t>((160 * 1024 - 1024) / row_bytes, 16);
-    while (rb & (rb - 1)) rb &= rb - 1;
-    while (rb > 1 && (n % rb)) rb >>= 1;
-    while (rb > 2 && n / rb < 512) rb >>= 1;
-    L.rb = rb; L.ntiles = n / rb; L.lg_rb = 0; while ((1 << L.lg_rb) < rb) L.lg_rb++;
-    L.lds_rows = row_bytes * rb;
-    L.lds_cols = sizeof(kcf) * spec_sstride(L.py) * 2 * L.npair;
-    L.thr_rows = (int)std::min<long long>(1024, std::max<long long>(256, (long long)rb * n / 16));
-    L.thr_cols = (int)std::min<long long>(512, std::max<long long>(128, (long long)2 * L.npair * n / 16));
+    // the launch shape of a one-rank handle with F fields on n x n, from the library's own planner
+    SpecShape Z;
+    SpecTables T;
+    if (!spec_shape(SpecGrid{ 2, { n, n, 1 }, L.F, 1, 0, false, n, 0 }, SpecKnobs(), Z, T) || Z.cols_split) { fprintf(stderr, "no plain 2-D shape for %d\n", n); exit(2); }
+    L.px = Z.px; L.py = Z.py;
+    L.rb = Z.rb; L.ntiles = Z.ntiles; L.lg_rb = Z.lg_rb; L.lg_pl = Z.lg_pl;  // column stride of W = 2^lg_pl (padded for 3 * 2^k rows)
+    L.lds_rows = Z.lds_rows; L.lds_cols = Z.lds_cols;
+    L.thr_rows = Z.thr_rows; L.thr_cols = Z.thr_cols;
+    L.nblk_cols = Z.nblk_cols;
     std::vector<float> hr((size_t)L.F * L.plane);
     std::vector<double> hx((size_t)L.F * L.plane);
     srand(7);
     for (auto &v : hr) v = (float)(rand() / (double)RAND_MAX - 0.5);
     for (auto &v : hx) v = rand() / (double)RAND_MAX - 0.5;
     L.r32 = up(hr); L.x = up(hx); L.x0 = up(hx);
-    L.lg_pl = 0; while ((1 << L.lg_pl) < n) L.lg_pl++;              // column stride of W = 2^lg_pl (as spec_build: padded for 3 * 2^k rows)
     CK(hipMalloc((void **)&L.W, sizeof(kcf) * L.npair * (size_t)n * ((size_t)1 << L.lg_pl)));
     CK(hipMalloc((void **)&L.W2, sizeof(kcf) * L.npair * L.plane));
     L.twx = up(spec_twiddles(L.px)); L.twy = up(spec_twiddles(L.py));
@@ -69,16 +66,7 @@ static void lab_init(Lab &L, int n)
     const double h = 4.0 / 1536, ih2 = 1.0 / (h * h);
     L.lx = up(spec_symbol_table(n, ih2)); L.ly = up(spec_symbol_table(n, ih2));
     L.ytab = up(spec_partner_table(L.py, spec_symbol_table(n, ih2)));
-    const std::vector<int> posx = spec_positions(L.px);
-    std::vector<int4> pairs;
-    for (int kx = 0; kx <= n / 2; kx++) {
-        const int kxm = (n - kx) % n, j = posx[kx], jm = posx[kxm];
-        if (kx == 0) pairs.push_back(make_int4(posx[0], posx[n / 2], 0, n / 2 + 1));
-        else if (kx != n / 2) pairs.push_back(make_int4(j, jm, kx, 0));
-    }
-    std::sort(pairs.begin(), pairs.end(), [](const int4 &a, const int4 &b) { return a.x < b.x; });
-    L.nblk_cols = (int)pairs.size();
-    L.pairtab = up(pairs);
+    L.pairtab = up(T.pairtab);
     memset(&L.Y, 0, sizeof L.Y);
     L.Y.nlig = 1; L.Y.shift = 11.6f; L.Y.a_rr = 2.8e-4f; L.Y.scale = (float)(1.0 / ((double)n * n)); L.Y.den_floor = 0.02f * 11.6f;
     L.Y.a_rU[0] = -3.1e-3f; L.Y.s[0] = 0.01f; L.Y.gam[0] = 0.01f; L.Y.D[0] = 1e-6f;
