@@ -39,32 +39,11 @@ static int est_lambda_max(ksfd_handle *h, double shift, int nits)
     return KSFD_OK;
 }
 
-// coefficients of p for this shift; degree 0 = "do not precondition"
+// coefficients of p for this shift (ksfd_krylov::cheb_setup); degree 0 = "do not precondition"
 static void poly_setup(ksfd_handle *h, double shift)
 {
-    const double a = 0.97, b = 1.0 + 1.15 * h->memo.lamJ / shift;      // spectrum of A/shift (power iteration converges from below: +15 %)
     h->poly_shift = shift;
-    h->poly_deg = 0;
-    const double kappa = b / a;
-    if (kappa < 1.3) return;                                       // GMRES alone needs <= 3 iterations
-    const double rc_ = (sqrt(kappa) - 1.0) / (sqrt(kappa) + 1.0);
-    int d = (int)ceil(log(h->poly_target) / log(rc_)) - 1;         // residual polynomial of degree d+1: ~2 rc^(d+1) <= 2*target
-    d = std::min(std::max(d, 1), std::max(h->poly_max_deg, 1));
-    // r(l) = T_{d+1}(mu(l)) / T_{d+1}(mu(0)), mu(l) = m0 + m1 l;  p(l) = (1 - r(l)) / l
-    const int n = d + 1;
-    double m0 = (b + a) / (b - a), m1 = -2.0 / (b - a);
-    double Tp[10] = { 1.0 }, Tc[10] = { m0, m1 }, Tn[10];
-    int degc = 1;
-    for (int k = 1; k < n; k++) {
-        for (int i = 0; i < 10; i++) Tn[i] = 0.0;
-        for (int i = 0; i <= degc; i++) { Tn[i] += 2.0 * m0 * Tc[i]; Tn[i + 1] += 2.0 * m1 * Tc[i]; }
-        for (int i = 0; i <= degc - 1; i++) Tn[i] -= Tp[i];
-        for (int i = 0; i < 10; i++) { Tp[i] = Tc[i]; Tc[i] = Tn[i]; }
-        degc++;
-    }
-    const double t0 = Tc[0];                                       // T_n(mu(0))
-    for (int i = 0; i <= d; i++) h->poly_alpha[i] = -(Tc[i + 1] / t0) / shift;   // p_i = -r_{i+1}; the 1/shift turns p(A/shift) into ~A^-1
-    h->poly_deg = d;
+    h->poly_deg = ksfd_krylov::cheb_setup(h->memo.lamJ, shift, h->poly_target, h->poly_max_deg, h->poly_alpha);
 }
 
 // z = sum_i alpha_i (A/shift)^i v  by Horner, one fused Jacobian action per degree
@@ -108,7 +87,7 @@ static int poly_apply(ksfd_handle *h, double shift, double *v, double *z)
 // matrix-free GMRES(m) for (shift I - J(u)) x = b, x0 = 0  -- replaces -ksp_type preonly -pc_type lu
 // (options84:58-60).  Classical Gram-Schmidt applied twice (CGS2), one fused multi-dot + one fused
 // update kernel per pass; the new vector's norm comes from the second pass by Pythagoras.
-// The small host algebra (Hessenberg QR, algebraic second projection, recycling rules) is in krylov_small.h.
+// The small host algebra (Hessenberg QR, algebraic second projection, recycling and cycle-length rules) is in krylov_small.h.
 // ------------------------------------------------------------------------------------------------
 struct LinStats { int its; double rel; };
 
@@ -349,12 +328,9 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
     if (rcy.reset) rec_reset(h);
     R.rec_on = rcy.rec_on; R.rec_full = rcy.rec_full;
     R.vb = R.rec_on ? h->rec_vtop : 0; R.zb = R.rec_on ? h->rec_ztop : 0;
-    // Restart length.  The first cycle runs with ksp_restart (30: PETSc's default); a cycle that ends without convergence is followed by
-    // one of twice the length, up to what ksfd_create could allocate (restart_alloc, <= 120).  Restarted GMRES loses most on exactly the
-    // systems where it needs many iterations -- shift*I - J indefinite late in a run, 30-50 iterations per stage system -- and a longer
-    // basis costs little next to the V cycle and Jacobian actions of an iteration there.  Host arrays are sized for the longest cycle.
-    const int m = h->restart_alloc - R.vb;
-    int m_cur = (R.rec_full && R.rec_on) ? m : std::min(m_opt, m);          // rec_full: no restart inside the space that is going to be kept
+    // restart length: ksfd_krylov::cycle_first / cycle_next.  Host arrays are sized for the longest cycle.
+    const int m = ksfd_krylov::cycle_room(h->restart_alloc, R.vb);
+    int m_cur = ksfd_krylov::cycle_first(m_opt, m, R.rec_on, R.rec_full);
     double *const V = R.V = h->V + (int64_t)R.vb * vs;
     R.Zq = R.use_poly ? h->Zb + (int64_t)R.zb * vs : nullptr;
     R.xcoef.assign((size_t)std::max(h->restart_alloc + 2, KSFD_MAXDOT), 0.0);
@@ -400,7 +376,7 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
             if ((rc = apply_AMinv(h, ustate, shift, R.shift_pc, pcmode, vj, z, w))) return rc;
             const int k = j + 1;
             double hn;
-            if ((o->reserved & 1) || k > 30) {       // (the fused multi-dot + Gram-row kernel returns 2k + 1 numbers, sized for the 30 vectors of the default restart: longer cycles finish classically)
+            if (ksfd_krylov::gs_classic(o->reserved, k)) {
                 if ((rc = op_multidot(h, w, V, k))) return rc;
                 if (!(h->hres[k] == h->hres[k])) return fail(h, KSFD_ENAN, "GMRES: Krylov vector is not finite");
                 if ((rc = cgs2_classic(h, w, V, k, hcol.data(), d.data(), &hn))) return rc;
@@ -417,11 +393,11 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
         first = false;
         if (done || total >= maxit) break;
         restarted = true;
-        if (h->restart_grow) m_cur = std::min(2 * m_cur, m);
+        m_cur = ksfd_krylov::cycle_next(m_cur, m, h->restart_grow);
     }
     if (!R.x_set) HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
     ls->its = total;
-    ls->rel = rn / ((tol_abs > 0.0 && o->ksp_rtol > 0.0) ? tol_abs / o->ksp_rtol : bn);      // correction equation: relative to the original right-hand side
+    ls->rel = ksfd_krylov::rel_of(rn, bn, tol_abs, o->ksp_rtol);
     if (rn > tol) return fail(h, KSFD_ELINEAR, "GMRES did not converge: %d iterations, relative residual %.3e (tol %.3e)", total, rn / bn, tol / bn);
     return KSFD_OK;
 }
@@ -438,6 +414,17 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
 // flexible GMRES with the same preconditioner, and if that fails too the caller falls back to the V cycle.
 // bnorm2 >= 0: ||b||^2 if the caller already has it (RHS kernel epilogue), else it is computed here.
 // ------------------------------------------------------------------------------------------------
+// residual of the iterate a spectral application left in x: r32 (fp32, fused: the strip kernel whose store epilogue also leaves the norm)
+// or r (fp64); ||r||^2 -> hres[0]
+static int spec_residual(ksfd_handle *h, bool fused, double *x, double shift, const double *b, double *r, float *r32)
+{
+    int rc;
+    // the spectral application wrote owned rows only; the 2-D fused residual exchanges the ghost rows itself, behind its interior rows
+    if (h->ring && !(fused && h->G.dim == 2) && (rc = halo(h, x))) return rc;
+    if (fused) return op_residual32(h, x, shift, b, r32);
+    return (rc = op_jvp_frozen(h, x, 2, shift, r, b)) ? rc : op_multidot(h, r, r, 0);
+}
+
 // guess != NULL: the first sweep starts from x0 = sum_j c_j Y_j (earlier stage solutions of the same step, A Y_j = b_j):
 //   x = x0 + M^-1 (b - sum_j c_j b_j)   -- no extra Jacobian action, the vectors ride in the row kernels of the application
 static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, const ksfd_step_opts *o, LinStats *ls, double bnorm2, int gmres_cap,
@@ -454,82 +441,66 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
     bool empty;
     if ((rc = rhs_empty(h, bn, x, "spectral solve: right-hand side is not finite", &empty)) || empty) return rc;
     const double tol = std::max(o->ksp_rtol * bn, o->ksp_atol);
-    const int maxit = std::min(o->ksp_max_it > 0 ? o->ksp_max_it : 2000, 24);
+    const int maxit = std::min(o->ksp_max_it > 0 ? o->ksp_max_it : 2000, ksfd_ctl::SPEC_SWEEP_CAP);
     double *r = h->Z;                              // residual (the fused-stage path leaves Z unused)
     float *r32 = reinterpret_cast<float *>(h->Z);  // ... kept in fp32 while only the preconditioner reads it
     double rn = bn, rprev = bn;
     // fp32 residual with the norm from the store epilogue: the 2-D strip kernel, or the 3-D one when its wave count fits the partial buffer
     const bool fused = fused_ok(h) || (strip3d_ok(h) && k3d_waves(h) <= part_capacity());
-    bool slow = false;
     // Predicted last sweep.  Every sweep multiplies the residual by (I - A M^-1); the four stage systems of a step share that
     // operator, so its contraction has been MEASURED by the time a solve is about to finish: rho_hat = the largest ratio
-    // ||r_k+1|| / ||r_k|| of any sweep (but the first one from zero, see below) of this step and the previous one.  When SAFETY * rho_hat * ||r_k|| <= tol the update
-    // x += M^-1 r_k is applied and the solve returns WITHOUT evaluating the residual of the result (a Jacobian action, 40 % of a
-    // sweep, whose only purpose would be to confirm a number 1-2 decades below the tolerance).  Every other residual is the true
-    // fp64 one, as before.  Off for tight tolerances (ksp_rtol < 1e-8: the parity tests verify every solve), with opts.reserved
-    // bit 3, and with KSFD_SPEC_VERIFY=1, which also evaluates and reports the residual the prediction stood in for.
+    // ||r_k+1|| / ||r_k|| of any sweep (but the first one from zero, see ksfd_ctl::spec_sweep) of this step and the previous one.  When
+    // SAFETY * rho_hat * ||r_k|| <= tol the update x += M^-1 r_k is applied and the solve returns WITHOUT evaluating the residual of the
+    // result (a Jacobian action, 40 % of a sweep, whose only purpose would be to confirm a number 1-2 decades below the tolerance).  Every
+    // other residual is the true fp64 one, as before.  Off for tight tolerances (ksp_rtol < 1e-8: the parity tests verify every solve),
+    // with opts.reserved bit 3, and with KSFD_SPEC_VERIFY=1, which also evaluates and reports the residual the prediction stood in for.
     static const int verify_env = getenv("KSFD_SPEC_VERIFY") ? atoi(getenv("KSFD_SPEC_VERIFY")) : 0;
-    const bool predict = h->spec_predict && !(o->reserved & 8) && o->ksp_rtol >= 1e-8 && verify_env != 2;
-    const double PRED_SAFETY = 4.0;
-    bool final_pending = false;
-    for (int k = 0; k < maxit; k++) {
+    const bool predict = ksfd_ctl::spec_predict_on(h->spec_predict, o->reserved, o->ksp_rtol, verify_env);
+    bool final_sweep = false, slow = false;
+    for (int k = 0; k < maxit && !slow; k++) {
         if (k == 0) rc = spec_apply(h, shift, b, x, nullptr, nullptr, guess);
         else rc = fused ? spec_apply(h, shift, nullptr, x, x, r32) : spec_apply(h, shift, r, x, x);
         if (rc) return rc;
         ls->its++;
-        if (final_pending) {
-            const double rho_hat = std::max(h->memo.spec_rho_step, h->memo.spec_rho_prev);
-            ls->rel = PRED_SAFETY * rho_hat * rn / bn;                            // the bound the decision was made on
+        if (final_sweep) {
+            ls->rel = ksfd_ctl::spec_pred_bound(h->memo, rn, bn);                  // the bound the decision was made on
             h->n_predicted++;
             if (verify_env == 1) {
-                if (h->ring && !(fused && h->G.dim == 2) && (rc = halo(h, x))) return rc;
-                if (fused) { if ((rc = op_residual32(h, x, shift, b, r32))) return rc; }
-                else if ((rc = op_jvp_frozen(h, x, 2, shift, r, b)) || (rc = op_multidot(h, r, r, 0))) return rc;
+                if ((rc = spec_residual(h, fused, x, shift, b, r, r32))) return rc;
                 const double rv = sqrt(h->hres[0]);
                 fprintf(stderr, "[spec] predicted final sweep %d: bound %.3e true %.3e tol %.3e%s\n", k, ls->rel, rv / bn, tol / bn, rv <= tol ? "" : "  <-- ABOVE TOLERANCE");
                 if (!(rv <= tol)) return fail(h, KSFD_ELINEAR, "predicted final sweep missed the tolerance: true %.3e, bound %.3e, tol %.3e", rv / bn, ls->rel, tol / bn);
             }
             return KSFD_OK;
         }
-        // the spectral application wrote owned rows only; the 2-D fused residual exchanges the ghost rows itself, behind its interior rows
-        if (h->ring && !(fused && h->G.dim == 2) && (rc = halo(h, x))) return rc;
-        if (fused) {
-            if ((rc = op_residual32(h, x, shift, b, r32))) return rc;                          // r = b - A x (fp32 copy), ||r||^2 -> hres[0]
-        } else {
-            if ((rc = op_jvp_frozen(h, x, 2, shift, r, b)) || (rc = op_multidot(h, r, r, 0))) return rc;
-        }
+        if ((rc = spec_residual(h, fused, x, shift, b, r, r32))) return rc;
         h->n_residual++;
         rn = sqrt(h->hres[0]);
         {
             static const bool trace = getenv("KSFD_SPEC_TRACE") != nullptr;        // residual history of the defect correction (diagnostics)
             if (trace) fprintf(stderr, "[spec] sweep %d rel %.3e%s\n", k, rn / bn, (k == 0 && guess) ? " (guess)" : "");
         }
-        if (!(rn == rn)) return fail(h, KSFD_ENAN, "spectral solve: residual is not finite");
-        if (rn <= tol) { ls->rel = rn / bn; return KSFD_OK; }
-        if (rn > 0.25 * rprev) { slow = true; break; }
-        // A contraction ratio of the sweep operator, taken between residuals of iterates that have been through a sweep or come from an
-        // initial guess.  The first sweep from zero is a class of its own and is neither recorded nor predicted from: b = f(u) is
-        // smooth, (I - A M^-1) b = dJ M^-1 b is several times larger relative to b (3-6 % on the bench window) than the same operator
-        // makes of the rough residuals that follow (0.6-1 %), and after one sweep a residual never is that smooth again.
-        if (k >= 1) h->memo.spec_rho_step = std::max(h->memo.spec_rho_step, rn / rprev);
-        rprev = rn;
-        const double rho_hat = std::max(h->memo.spec_rho_step, h->memo.spec_rho_prev);
-        if (predict && rho_hat > 0.0 && (k >= 1 || guess) && k + 1 < maxit && PRED_SAFETY * rho_hat * rn <= tol) final_pending = true;
+        switch (ksfd_ctl::spec_sweep(k, maxit, rn, rprev, tol, guess != nullptr, predict, h->memo)) {
+        case ksfd_ctl::SPEC_NOT_FINITE: return fail(h, KSFD_ENAN, "spectral solve: residual is not finite");
+        case ksfd_ctl::SPEC_CONVERGED: ls->rel = rn / bn; return KSFD_OK;
+        case ksfd_ctl::SPEC_SLOW: slow = true; break;
+        case ksfd_ctl::SPEC_CONTINUE_FINAL: final_sweep = true; rprev = rn; break;
+        case ksfd_ctl::SPEC_CONTINUE: rprev = rn; break;
+        }
     }
     if (fused && (rc = op_jvp_frozen(h, x, 2, shift, r, b))) return rc;       // the correction solve below wants the residual in fp64
-    if (!slow && rn > tol) slow = true;
-    // hand the correction equation A d = r to flexible GMRES with the same preconditioner (absolute tolerance = ours)
+    // slow, or out of sweeps: hand the correction equation A d = r to flexible GMRES with the same preconditioner (absolute tolerance = ours)
     ksfd_step_opts go = *o;
     go.ksp_rtol = 1e-30; go.ksp_atol = tol;
     if (gmres_cap > 0) go.ksp_max_it = gmres_cap;
-    const bool restart_from_zero = !(rn < bn);       // the sweeps made it worse: forget x
+    const bool restart_from_zero = ksfd_ctl::spec_handover(rn, bn);       // the sweeps made it worse: forget x
     LinStats g2;
     rc = gmres(h, h->u, shift, restart_from_zero ? b : r, h->t3, &go, &g2, 3);
     ls->its += g2.its;
     if (rc) { ls->rel = rn / bn; return rc; }
     if (restart_from_zero) { if ((rc = op_copy(h, x, h->t3))) return rc; }
     else { const double *xs[2] = { x, h->t3 }; double a2[2] = { 1.0, 1.0 }; if ((rc = op_lincomb(h, 2, xs, a2, x))) return rc; }
-    ls->rel = g2.rel * (restart_from_zero ? 1.0 : rn / bn);
+    ls->rel = ksfd_ctl::spec_handover_rel(g2.rel, restart_from_zero, rn, bn);
     return KSFD_OK;
 }
 
@@ -570,7 +541,7 @@ static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x,
     // Cycle length: what the kernels of an iteration hold, whatever the basis has room for.  k_multidot_gram / k_gs_update_dev stop at the
     // top of the KB ladder (32 vectors), k_gmres_coef keeps its coefficients in KSFD_MAXDOT slots: a longer ksp_restart runs as cycles of
     // KSFD_ASYNC_MAXK (gmres() goes on classically and in chunks beyond that length; there is no such path here).
-    const int m = std::min(std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc), KSFD_ASYNC_MAXK);
+    const int m = ksfd_krylov::async_cycle(o->ksp_restart, h->restart_alloc, KSFD_ASYNC_MAXK);
     const int maxit = o->ksp_max_it > 0 ? o->ksp_max_it : 2000;
     const int64_t vs = h->vlen;
     const int ld = h->restart_alloc + 1;

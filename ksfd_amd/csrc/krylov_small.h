@@ -7,6 +7,9 @@
 //   cgs2_algebraic   second Gram-Schmidt projection and the norm of the result from the Gram row
 //   recycle_uses     which earlier stages' spaces a stage projects on
 //   recycle_decide   whether a solve recycles at all
+//   cycle_room, cycle_first, cycle_next, gs_classic, async_cycle, rel_of   length of a GMRES cycle, which Gram-Schmidt it runs, what it reports
+//   restart_fit, restart_cap   how many basis vectors ksfd_create allocates from the free device memory
+//   cheb_setup       degree and monomial coefficients of the Chebyshev polynomial preconditioner
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -140,6 +143,74 @@ static inline RecycleChoice recycle_decide(int pcmode, int stage, int rec_mode, 
     c.reset = !c.rec_on || stage == 0 || restart_alloc - rec_vtop < (c.rec_full ? 16 : 6);
     if (c.reset && stage != 0) c.rec_on = false;
     return c;
+}
+
+// ---- cycle length ----
+// Restart length.  The first cycle runs with ksp_restart (30: PETSc's default); a cycle that ends without convergence is followed by
+// one of twice the length, up to what ksfd_create could allocate (restart_alloc, <= 120).  Restarted GMRES loses most on exactly the
+// systems where it needs many iterations -- shift*I - J indefinite late in a run, 30-50 iterations per stage system -- and a longer
+// basis costs little next to the V cycle and Jacobian actions of an iteration there.
+// room: basis slots behind the kept spaces (vb: first slot of this solve's own vectors)
+static inline int cycle_room(int restart_alloc, int vb) { return restart_alloc - vb; }
+// m_opt: min(ksp_restart, restart_alloc).  rec_full: no restart inside the space that is going to be kept
+static inline int cycle_first(int m_opt, int room, bool rec_on, bool rec_full) { return (rec_full && rec_on) ? room : std::min(m_opt, room); }
+static inline int cycle_next(int m_cur, int room, bool restart_grow) { return restart_grow ? std::min(2 * m_cur, room) : m_cur; }
+// Column k (= j + 1 vectors to project on) by classical CGS2 instead of the Gram-row variant: on request (opts.reserved bit 0), and beyond 30
+// (the fused multi-dot + Gram-row kernel returns 2k + 1 numbers, sized for the 30 vectors of the default restart: longer cycles finish classically)
+static inline bool gs_classic(int reserved, int k) { return (reserved & 1) || k > 30; }
+// Pipelined solver: what the kernels of an iteration hold (maxk), whatever the basis has room for
+static inline int async_cycle(int ksp_restart, int restart_alloc, int maxk) { return std::min(std::min(ksp_restart > 0 ? ksp_restart : 30, restart_alloc), maxk); }
+// Relative residual a solve reports.  tol_abs > 0: a correction equation A d = b - A x0 solved to the absolute tolerance of the original
+// system -- relative to the original right-hand side, whose norm is tol_abs / ksp_rtol
+static inline double rel_of(double rn, double bn, double tol_abs, double ksp_rtol) { return rn / ((tol_abs > 0.0 && ksp_rtol > 0.0) ? tol_abs / ksp_rtol : bn); }
+
+// ---- basis size ----
+const int RESTART_DEFAULT = 30, RESTART_MAX = 120, RESTART_MIN = 8;     // below RESTART_MIN the grid does not fit the device
+// KSFD_RESTART_MAX as the caller's environment gives it -> the cap on the basis
+static inline int restart_cap(int env_value) { return std::max(RESTART_MIN, std::min(env_value, RESTART_MAX)); }
+// Krylov storage is what scales with the restart length: V (m+1 vectors) + Zb (m).  Sized to the free device memory mfree (bytes):
+// ~30 other full-size vectors of vecbytes (state, stage vectors, temporaries, coefficient planes, multigrid level 0 + coarse levels)
+// must fit first.  Where memory is plentiful the basis may be longer than the first cycle's 30 vectors (cycle_next), up to cap and to
+// 40 % of the free memory for V + Zb; where it is short, whatever fits (the caller refuses below RESTART_MIN).
+static inline int restart_fit(double mfree, double vecbytes, int cap)
+{
+    const double room = 0.92 * mfree / vecbytes - 30.0;
+    const int fit_room = (int)floor(std::min((room - 1.0) / 2.0, 1.0e6));
+    const int fit_40 = (int)floor(std::min(0.4 * mfree / vecbytes / 2.0, 1.0e6));
+    return std::max(std::min(std::min(cap, fit_room), fit_40), std::min(RESTART_DEFAULT, fit_room));
+}
+
+// ---- Chebyshev polynomial preconditioner ----
+const int CHEB_MAX_DEG = 7;                     // largest degree ksfd_set_poly_params admits: alpha[0 .. CHEB_MAX_DEG]
+const int CHEB_NCOEF = CHEB_MAX_DEG + 2;        // monomial coefficients of T_n(mu(l)), n = degree + 1 <= CHEB_MAX_DEG + 1
+static_assert(CHEB_MAX_DEG + 1 == 8, "the handle keeps the coefficients in poly_alpha[8]");
+
+// Coefficients of p, z = sum_i alpha_i (A/shift)^i v ~ A^-1 v, for the spectrum of A/shift in [a, b] = [0.97, 1 + 1.15 lamJ/shift] (power
+// iteration converges from below: +15 %).  Returns the degree d (alpha[0 .. d] set); 0 = "do not precondition" (kappa = b/a < 1.3: GMRES
+// alone needs <= 3 iterations).  target: wanted size of the residual polynomial r(l) = 1 - l p(l) on [a, b]; max_deg <= CHEB_MAX_DEG.
+static inline int cheb_setup(double lamJ, double shift, double target, int max_deg, double alpha[8])
+{
+    const double a = 0.97, b = 1.0 + 1.15 * lamJ / shift;
+    const double kappa = b / a;
+    if (kappa < 1.3) return 0;
+    const double rc_ = (sqrt(kappa) - 1.0) / (sqrt(kappa) + 1.0);
+    int d = (int)ceil(log(target) / log(rc_)) - 1;                 // residual polynomial of degree d+1: ~2 rc^(d+1) <= 2*target
+    d = std::min(std::max(d, 1), std::max(std::min(max_deg, CHEB_MAX_DEG), 1));
+    // r(l) = T_{d+1}(mu(l)) / T_{d+1}(mu(0)), mu(l) = m0 + m1 l;  p(l) = (1 - r(l)) / l
+    const int n = d + 1;
+    double m0 = (b + a) / (b - a), m1 = -2.0 / (b - a);
+    double Tp[CHEB_NCOEF] = { 1.0 }, Tc[CHEB_NCOEF] = { m0, m1 }, Tn[CHEB_NCOEF];
+    int degc = 1;
+    for (int k = 1; k < n; k++) {                                  // T_{k+1} = 2 mu T_k - T_{k-1} in the monomial basis; degc = k <= CHEB_MAX_DEG
+        for (int i = 0; i < CHEB_NCOEF; i++) Tn[i] = 0.0;
+        for (int i = 0; i <= degc; i++) { Tn[i] += 2.0 * m0 * Tc[i]; Tn[i + 1] += 2.0 * m1 * Tc[i]; }
+        for (int i = 0; i <= degc - 1; i++) Tn[i] -= Tp[i];
+        for (int i = 0; i < CHEB_NCOEF; i++) { Tp[i] = Tc[i]; Tc[i] = Tn[i]; }
+        degc++;
+    }
+    const double t0 = Tc[0];                                       // T_n(mu(0))
+    for (int i = 0; i <= d; i++) alpha[i] = -(Tc[i + 1] / t0) / shift;   // p_i = -r_{i+1}; the 1/shift turns p(A/shift) into ~A^-1
+    return d;
 }
 
 }   // namespace ksfd_krylov

@@ -130,22 +130,15 @@ extern "C" int ksfd_create(const ksfd_config *cfg, const ksfd_dist *dist, ksfd_h
     h->nblk_vec = (int)std::min<long long>((G.nloc + KSFD_BLOCK - 1) / KSFD_BLOCK, 2048);
     build_tableau(h);
 
-    // Krylov storage is what scales with the restart length: V (m+1 vectors) + Zb (m).  Size it to the HBM that is free:
-    // ~30 other full-size vectors (state, stage vectors, temporaries, coefficient planes, multigrid level 0 + coarse levels)
-    // must fit first.  m = 30 on anything up to ~12k^2 x 2 fields on a 288 GB MI355X; larger grids run with a shorter restart.
-    // Round 3: where HBM is plentiful the basis may be longer than the first cycle's 30 vectors -- gmres() doubles the restart length after
-    // a cycle that did not converge (indefinite stage matrices late in a run), up to 120 and to 40 % of the free memory for V + Zb.
-    h->restart_alloc = 30;
-    int fit_local = 30;
+    // Krylov storage (V: m+1 vectors, Zb: m) is sized to the HBM that is free (ksfd_krylov::restart_fit): m = 30 on anything up to
+    // ~12k^2 x 2 fields on a 288 GB MI355X, up to 120 where HBM is plentiful; larger grids run with a shorter restart.
+    h->restart_alloc = ksfd_krylov::RESTART_DEFAULT;
+    int fit_local = ksfd_krylov::RESTART_DEFAULT;
     {
         size_t mfree = 0, mtotal = 0;
         if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree > 0) {
-            const double vecbytes = 8.0 * (double)h->vlen;
-            const double room = 0.92 * (double)mfree / vecbytes - 30.0;
-            const int fit_room = (int)floor(std::min((room - 1.0) / 2.0, 1.0e6));
-            const int fit_40 = (int)floor(std::min(0.4 * (double)mfree / vecbytes / 2.0, 1.0e6));
-            static const int cap = getenv("KSFD_RESTART_MAX") ? std::max(8, std::min(atoi(getenv("KSFD_RESTART_MAX")), 120)) : 120;
-            fit_local = std::max(std::min(std::min(cap, fit_room), fit_40), std::min(30, fit_room));
+            static const int cap = getenv("KSFD_RESTART_MAX") ? ksfd_krylov::restart_cap(atoi(getenv("KSFD_RESTART_MAX"))) : ksfd_krylov::RESTART_MAX;
+            fit_local = ksfd_krylov::restart_fit((double)mfree, 8.0 * (double)h->vlen, cap);
         }
     }
     if (alloc_d(h, &h->dres, 128)) CFAIL(KSFD_ENOMEM, "%s", h->err.c_str());
@@ -163,8 +156,8 @@ extern "C" int ksfd_create(const ksfd_config *cfg, const ksfd_dist *dist, ksfd_h
             CFAIL(KSFD_EHIP, "reading the agreed restart length failed");
         fit_local = (int)(-v + 0.5);
     }
-    if (fit_local != 30) {
-        if (fit_local < 8) CFAIL(KSFD_ENOMEM, "grid too large for this device: a vector is %.2f GB, the solver needs ~47 of them (restart length that fits: %d)", 8.0 * (double)h->vlen / 1e9, fit_local);
+    if (fit_local != ksfd_krylov::RESTART_DEFAULT) {
+        if (fit_local < ksfd_krylov::RESTART_MIN) CFAIL(KSFD_ENOMEM, "grid too large for this device: a vector is %.2f GB, the solver needs ~47 of them (restart length that fits: %d)", 8.0 * (double)h->vlen / 1e9, fit_local);
         h->restart_alloc = fit_local;
     }
     double **vecs[] = { &h->u, &h->usave, &h->Z, &h->bvec, &h->t1, &h->t2, &h->t3, &h->errv };
@@ -644,8 +637,7 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
     if (h->use_frozen && (rc = ensure_coef(h, true))) return rc;      // usually already there: the CFL check after the last step made them
     h->poly_shift = -1.0;
     m.nsteps++;
-    if (m.spec_rho_step > 0.0) m.spec_rho_prev = m.spec_rho_step;      // contraction memory of the spectral sweeps: this step's maximum replaces the last one's
-    m.spec_rho_step = 0.0;
+    ksfd_ctl::spec_rho_roll(m);                      // contraction memory of the spectral sweeps
     while (true) {
         AttemptPlan p;
         if ((rc = plan_attempt(h, opts, hh, direct, dr_on, lam_done, p))) return rc;
@@ -1072,7 +1064,7 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
 }
 extern "C" int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, double mg_threshold)
 {
-    if (!h || max_degree < 0 || max_degree > 7) return KSFD_EINVAL;
+    if (!h || max_degree < 0 || max_degree > ksfd_krylov::CHEB_MAX_DEG) return KSFD_EINVAL;
     if (mg_threshold > 0.0) h->mg_threshold = mg_threshold;
     h->poly_max_deg = max_degree;           // 0 disables the polynomial preconditioner
     if (target > 0.0 && target < 1.0) h->poly_target = target;

@@ -84,13 +84,10 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
     if (r.poly_wanted) {
         if (!h->Zb && alloc_d(h, &h->Zb, (int64_t)h->restart_alloc * h->vlen)) return KSFD_ENOMEM;
         if (!lam_done) {
-            if (m.lamJ < 0.0 || ++m.lam_age >= m.lam_period) {
+            if (ksfd_ctl::lam_due(m)) {
                 const double before = m.lamJ;
-                if ((rc = est_lambda_max(h, p.shift, before < 0.0 ? 8 : 2))) return rc;    // warm-started after the first step
-                // J changes slowly from step to step: while the estimate moves by < 2 %, look less often
-                const bool stable = before > 0.0 && fabs(m.lamJ - before) <= 0.02 * before;
-                m.lam_period = stable ? std::min(2 * m.lam_period, 8) : 1;
-                m.lam_age = 0;
+                if ((rc = est_lambda_max(h, p.shift, ksfd_ctl::lam_power_its(before)))) return rc;
+                ksfd_ctl::lam_estimated(m, before);
             }
             lam_done = true;
         }
@@ -200,13 +197,13 @@ static int stage_solve(ksfd_handle *h, const ksfd_step_opts *opts, const Attempt
         //  cheap attempt instead of four expensive ones: 440 -> 176 ms for such a step at 4096^2 x 3 fields)
         const bool skip = spec_failed && opts->pc_type == 2;
         if (!skip) {
-            rc = spec_solve(h, shift, r.b, xi, opts, &ls, r.bnorm2, opts->pc_type == 2 ? (h->memo.spec_backoff > 8 ? 8 : 40) : 0, sg.n ? &sg : nullptr);
+            rc = spec_solve(h, shift, r.b, xi, opts, &ls, r.bnorm2, ksfd_ctl::spec_gmres_cap(opts->pc_type, h->memo.spec_backoff), sg.n ? &sg : nullptr);
             st.pc_used |= 8;
         }
         if (skip || (rc == KSFD_ELINEAR && opts->pc_type == 2)) {
             if (!skip) st.linear_its += ls.its;
             spec_failed = true;
-            const bool mg_here = h->mg_ok && p.stiff > 0.3;
+            const bool mg_here = ksfd_ctl::spec_fallback_mg(h->mg_ok, p.stiff);
             rc = gmres(h, h->u, shift, r.b, xi, opts, &ls, mg_here ? 1 : 0);
             st.pc_used |= mg_here ? 2 : 1;
         }

@@ -8,6 +8,11 @@
 //   stage_guess          least-squares coefficients of a stage's right-hand side in the earlier ones (regularised Gram system)
 //   shift_floor_update   online search for the shift floor of the multigrid hierarchy
 //   spec_backoff_update  back-off of the automatic spectral choice after a step it suited badly
+//   spec_gmres_cap, spec_fallback_mg   leash of a spectral attempt's GMRES / which solver takes over after it (stage_solve)
+//   spec_predict_on, spec_sweep, spec_pred_bound, spec_rho_roll, spec_handover, spec_handover_rel
+//                        the defect-correction sweeps of spec_solve: verdict after a sweep's true residual, contraction memory,
+//                        predicted last sweep, hand-over of the rest to GMRES
+//   lam_due, lam_power_its, lam_estimated   when the eigenvalue estimate of the polynomial preconditioner is refreshed (plan_attempt)
 //   adapt_basic          PETSc's TSAdaptChoose_Basic
 #pragma once
 #include <math.h>
@@ -145,6 +150,82 @@ static inline void spec_backoff_update(StepMemo &m, bool failed, int its, long l
         m.spec_bad_until = nsteps + m.spec_backoff;
         m.spec_backoff = std::min(2 * m.spec_backoff, 512);
     } else m.spec_backoff = 8;
+}
+
+// A spectral attempt of the automatic choice (pc_type 2) caps the GMRES that takes over from slow sweeps, so that a state the
+// preconditioner does not suit costs little: 40 iterations, 8 on a re-trial after a back-off period (spec_backoff already doubled).
+// 0: no cap (pc_type 4).
+static inline int spec_gmres_cap(int pc_type, int backoff) { return pc_type == 2 ? (backoff > 8 ? 8 : 40) : 0; }
+// ... and what solves the stage after a failed attempt: the V cycle where there is one and the step is stiff enough for it, else plain GMRES
+static inline bool spec_fallback_mg(bool mg_ok, double stiff) { return mg_ok && stiff > 0.3; }
+
+// ---- defect-correction sweeps of the spectral stage solver (spec_solve) ----
+const int SPEC_SWEEP_CAP = 24;              // sweeps per solve before the rest goes to GMRES
+const double SPEC_SLOW_RATIO = 0.25;        // a sweep that leaves more than this of the residual is slow: the coefficients vary too much
+const double SPEC_PRED_SAFETY = 4.0;        // predicted last sweep: SAFETY * rho_hat * ||r_k|| <= tol
+const double SPEC_PRED_MIN_RTOL = 1e-8;     // ... off below this ksp_rtol (the parity tests verify every solve)
+
+// Predicted last sweep on?  spec_predict: the handle's switch (KSFD_TUNE bit 16); reserved bit 3: the caller's; verify_env: KSFD_SPEC_VERIFY
+// (2 = off, 1 = on and every skipped residual evaluated anyway).
+static inline bool spec_predict_on(bool spec_predict, int reserved, double ksp_rtol, int verify_env)
+{
+    return spec_predict && !(reserved & 8) && ksp_rtol >= SPEC_PRED_MIN_RTOL && verify_env != 2;
+}
+
+// rho_hat: the largest contraction measured in this step and the previous one
+static inline double spec_rho_hat(const StepMemo &m) { return std::max(m.spec_rho_step, m.spec_rho_prev); }
+
+// start of a step: this step's maximum replaces the last one's (a step that recorded none keeps it)
+static inline void spec_rho_roll(StepMemo &m)
+{
+    if (m.spec_rho_step > 0.0) m.spec_rho_prev = m.spec_rho_step;
+    m.spec_rho_step = 0.0;
+}
+
+enum SpecVerdict {
+    SPEC_NOT_FINITE,        // the residual is NaN
+    SPEC_CONVERGED,         // rn <= tol
+    SPEC_SLOW,              // rn > SPEC_SLOW_RATIO * rprev: hand the rest to GMRES
+    SPEC_CONTINUE,          // another sweep, its residual evaluated
+    SPEC_CONTINUE_FINAL     // another sweep, predicted to be the last: return after it without evaluating the residual
+};
+
+// Verdict after sweep k (0-based, cap sweeps at most) left the true residual norm rn; rprev: the one before it (||b|| for k = 0).
+// A contraction ratio enters the memory only between residuals of iterates that have been through a sweep (k >= 1), and only from a sweep
+// that goes on.  The first sweep from zero is a class of its own and is neither recorded nor predicted from: b = f(u) is
+// smooth, (I - A M^-1) b = dJ M^-1 b is several times larger relative to b (3-6 % on the bench window) than the same operator
+// makes of the rough residuals that follow (0.6-1 %), and after one sweep a residual never is that smooth again.  With an initial guess
+// (guess) the residual after sweep 0 is rough already, and a rho_prev left by the previous step may predict from it.
+static inline SpecVerdict spec_sweep(int k, int cap, double rn, double rprev, double tol, bool guess, bool predict, StepMemo &m)
+{
+    if (!(rn == rn)) return SPEC_NOT_FINITE;
+    if (rn <= tol) return SPEC_CONVERGED;
+    if (rn > SPEC_SLOW_RATIO * rprev) return SPEC_SLOW;
+    if (k >= 1) m.spec_rho_step = std::max(m.spec_rho_step, rn / rprev);
+    const double rho_hat = spec_rho_hat(m);
+    const bool final_next = predict && rho_hat > 0.0 && (k >= 1 || guess) && k + 1 < cap && SPEC_PRED_SAFETY * rho_hat * rn <= tol;
+    return final_next ? SPEC_CONTINUE_FINAL : SPEC_CONTINUE;
+}
+
+// what a predicted exit reports as its relative residual: the bound the decision was made on (rn: the last residual evaluated)
+static inline double spec_pred_bound(const StepMemo &m, double rn, double bn) { return SPEC_PRED_SAFETY * spec_rho_hat(m) * rn / bn; }
+
+// Hand-over of the correction equation A d = r to GMRES.  true: the sweeps made it worse than x = 0 -- forget x and solve A x = b.
+static inline bool spec_handover(double rn, double bn) { return !(rn < bn); }
+// ... and the relative residual of the whole solve from that of the correction solve (relative to its own right-hand side, r or b)
+static inline double spec_handover_rel(double gmres_rel, bool from_zero, double rn, double bn) { return gmres_rel * (from_zero ? 1.0 : rn / bn); }
+
+// ---- eigenvalue estimate of the polynomial preconditioner (plan_attempt, once per step) ----
+// Due on the first step (lamJ < 0) and every lam_period steps after an estimate; lam_age counts only once there is an estimate.
+static inline bool lam_due(StepMemo &m) { return m.lamJ < 0.0 || ++m.lam_age >= m.lam_period; }
+// power iterations: warm-started after the first estimate (before: lamJ as it was)
+static inline int lam_power_its(double before) { return before < 0.0 ? 8 : 2; }
+// J changes slowly from step to step: while the estimate moves by < 2 %, look less often (every 2, 4, 8 steps)
+static inline void lam_estimated(StepMemo &m, double before)
+{
+    const bool stable = before > 0.0 && fabs(m.lamJ - before) <= 0.02 * before;
+    m.lam_period = stable ? std::min(2 * m.lam_period, 8) : 1;
+    m.lam_age = 0;
 }
 
 // TSAdaptChoose_Basic

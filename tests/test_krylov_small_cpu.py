@@ -1,7 +1,8 @@
 """CPU: the small host algebra of the Krylov solvers (ksfd_amd/csrc/krylov_small.h) on its own.  The header is plain C++ without device
 code and without the handle -- that the small driver below compiles with the host compiler alone is the proof -- so the driver exercises
 exactly what gmres(), gmres_async() and gmres_dr() run: the incremental Hessenberg QR and hess_lsq against numpy.linalg.lstsq, the
-algebraic second Gram-Schmidt projection against the explicit one, and the recycling rules against restatements in Python."""
+algebraic second Gram-Schmidt projection against the explicit one, the recycling rules, the cycle lengths and the basis size against
+restatements in Python, and the Chebyshev coefficients of the polynomial preconditioner (poly_setup) against numpy's Chebyshev polynomials."""
 import contextlib
 import itertools
 import os
@@ -85,6 +86,29 @@ int main(int argc, char **argv)
             printf("%d %d %d %d %d\n", r.rec_on ? 1 : 0, r.rec_full ? 1 : 0, r.reset ? 1 : 0,
                    recycle_uses(stage, q, rec_mode, false) ? 1 : 0, recycle_uses(stage, q, rec_mode, true) ? 1 : 0);
         }
+    } else if (!strcmp(argv[1], "cheb")) {
+        for (int c = 0; c < n; c++) {
+            const double lamJ = rd(), shift = rd(), target = rd(); const int max_deg = ri();
+            double alpha[8] = { 0.0 };
+            printf("%d", cheb_setup(lamJ, shift, target, max_deg, alpha));
+            for (int i = 0; i < 8; i++) printf(" %.17g", alpha[i]);
+            printf("\n");
+        }
+    } else if (!strcmp(argv[1], "cycle")) {
+        for (int c = 0; c < n; c++) {
+            const int restart_alloc = ri(), vb = ri(), m_opt = ri(), rec_on = ri(), rec_full = ri(), m_cur = ri(), grow = ri(), reserved = ri(), k = ri();
+            const int ksp_restart = ri(), maxk = ri(); const double rn = rd(), bn = rd(), tol_abs = rd(), ksp_rtol = rd();
+            const int room = cycle_room(restart_alloc, vb);
+            printf("%d %d %d %d %d %.17g\n", room, cycle_first(m_opt, room, rec_on != 0, rec_full != 0), cycle_next(m_cur, room, grow != 0),
+                   gs_classic(reserved, k) ? 1 : 0, async_cycle(ksp_restart, restart_alloc, maxk), rel_of(rn, bn, tol_abs, ksp_rtol));
+        }
+    } else if (!strcmp(argv[1], "fit")) {           /* env < 0: KSFD_RESTART_MAX not set */
+        for (int c = 0; c < n; c++) {
+            const double mfree = rd(), vecbytes = rd(); const int env = ri();
+            const int cap = env < 0 ? RESTART_MAX : restart_cap(env);
+            printf("%d %d\n", cap, restart_fit(mfree, vecbytes, cap));
+        }
+        printf("%d %d %d\n", RESTART_DEFAULT, RESTART_MAX, RESTART_MIN);
     } else return 2;
     return 0;
 }
@@ -302,3 +326,105 @@ def test_recycling_rules(driver):
         seen.add(tuple(want[:3]))
     # every outcome occurs: off (reset), on and fresh (stage 0), on behind kept spaces, the same two with whole cycles
     assert seen == {(0, 0, 1), (1, 0, 1), (1, 0, 0), (1, 1, 1), (1, 1, 0), (0, 1, 1)}
+
+
+# ---- Chebyshev polynomial preconditioner ------------------------------------------------------------------------------------------------
+CHEB_CASES = list(itertools.product([0.5, 1.0, 3.0, 10.0, 30.0, 100.0, 1e3, 1e4], [0.1, 1.0, 2.3, 115.0], [1, 3, 6, 7]))
+CHEB_TARGET = 0.02
+# 1 - shift l p(l) against numpy's T_n(mu(l)) / T_n(mu(0)): the recurrence restated in Python is within 8.5e-11 of numpy on exactly this grid
+# (cancellation between monomial terms at the large-kappa end); the margin covers a different summation order
+CHEB_TOL = 1e-9
+
+
+def cheb_degree(lamJ, shift, target, max_deg):
+    """the degree rule restated: (a, b, kappa, degree), degree 0 = do not precondition"""
+    a, b = 0.97, 1.0 + 1.15 * lamJ / shift
+    kappa = b / a
+    if kappa < 1.3:
+        return a, b, kappa, 0
+    rc = (np.sqrt(kappa) - 1.0) / (np.sqrt(kappa) + 1.0)
+    d = int(np.ceil(np.log(target) / np.log(rc))) - 1
+    return a, b, kappa, min(max(d, 1), max(max_deg, 1))
+
+
+def test_chebyshev_coefficients_match_numpy(driver):
+    out = driver('cheb', [[lamJ, shift, CHEB_TARGET, md] for lamJ, shift, md in CHEB_CASES])
+    assert len(out) == len(CHEB_CASES)
+    degrees, worst, worst_over = set(), 0.0, 0.0
+    for (lamJ, shift, md), (d, *alpha) in zip(CHEB_CASES, out):
+        a, b, kappa, want = cheb_degree(lamJ, shift, CHEB_TARGET, md)
+        assert d == want, (lamJ, shift, md, d, want)
+        assert (d == 0) == (kappa < 1.3)
+        degrees.add(int(d))
+        if d == 0:
+            assert alpha == [0.0] * 8
+            continue
+        d = int(d)
+        assert all(x == 0.0 for x in alpha[d + 1:])
+        n = d + 1
+        m0, m1 = (b + a) / (b - a), -2.0 / (b - a)
+        ls = np.linspace(a, b, 65)
+        p = sum(alpha[i] * ls ** i for i in range(d + 1))
+        r = 1.0 - shift * ls * p
+        Tn = np.zeros(n + 1); Tn[n] = 1.0
+        t0 = np.polynomial.chebyshev.chebval(m0, Tn)
+        ref = np.polynomial.chebyshev.chebval(m0 + m1 * ls, Tn) / t0
+        err = float(np.max(np.abs(r - ref)))
+        worst = max(worst, err)
+        assert err <= CHEB_TOL, (lamJ, shift, md, d, err)
+        over = float(np.max(np.abs(r))) - 1.0 / abs(t0)             # equioscillation: |r| <= 1 / |T_n(mu(0))| on [a, b]
+        worst_over = max(worst_over, over)
+        assert over <= CHEB_TOL, (lamJ, shift, md, d, over)
+    print('degrees %s; largest deviation from numpy %.2e, largest excess over 1/|T_n(mu(0))| %.2e' % (sorted(degrees), worst, worst_over))
+    assert {0, 1, 3, 6, 7} <= degrees          # no preconditioner, and each max_deg active as the clamp
+
+
+# ---- cycle length and basis size -------------------------------------------------------------------------------------------------------
+def test_cycle_rules(driver):
+    rows = []
+    for ralloc, vb, ksp_restart, (rec_on, rec_full), grow, reserved, k in itertools.product(
+            (8, 30, 120), (0, 5), (0, 8, 30, 64, 200), [(0, 0), (1, 0), (1, 1), (0, 1)], (0, 1), (0, 1, 2), (1, 30, 31, 64)):
+        m_opt = min(ksp_restart if ksp_restart > 0 else 30, ralloc)
+        for m_cur in (m_opt, 2 * m_opt):
+            for rn, bn, tol_abs, rtol in [(1e-7, 2.0, -1.0, 1e-6), (1e-7, 2.0, 3e-6, 1e-6), (1e-7, 2.0, 3e-6, 0.0)]:
+                rows.append([ralloc, vb, m_opt, rec_on, rec_full, m_cur, grow, reserved, k, ksp_restart, 32, rn, bn, tol_abs, rtol])
+    out = driver('cycle', rows)
+    assert len(out) == len(rows)
+    seen = set()
+    for (ralloc, vb, m_opt, rec_on, rec_full, m_cur, grow, reserved, k, ksp_restart, maxk, rn, bn, tol_abs, rtol), got in zip(rows, out):
+        room = ralloc - vb
+        first = room if (rec_full and rec_on) else min(m_opt, room)              # whole cycles kept: the whole room
+        nxt = min(2 * m_cur, room) if grow else m_cur                            # doubling, capped at the room; growth off
+        classic = int(bool(reserved & 1) or k > 30)
+        pipelined = min(ksp_restart if ksp_restart > 0 else 30, ralloc, maxk)    # clamp of the pipelined solver
+        rel = rn / (tol_abs / rtol if (tol_abs > 0.0 and rtol > 0.0) else bn)
+        assert got == [room, first, nxt, classic, pipelined, rel], (ralloc, vb, m_opt, rec_on, rec_full, m_cur, grow, reserved, k, ksp_restart, got)
+        seen |= {('full', first == room and first > m_opt), ('capped', bool(grow) and nxt == room < 2 * m_cur), ('clamp', pipelined == 32 < ksp_restart)}
+    assert {('full', True), ('capped', True), ('clamp', True)} <= seen
+    # the two sides of the classical threshold, and the request bit
+    pick = lambda reserved, k: driver('cycle', [[30, 0, 30, 0, 0, 30, 1, reserved, k, 30, 32, 1.0, 1.0, -1.0, 1e-6]])[0][3]
+    assert (pick(0, 30), pick(0, 31), pick(1, 1), pick(2, 30)) == (0, 1, 1, 0)
+
+
+def fit_rule(mfree, vecbytes, cap):
+    room = 0.92 * mfree / vecbytes - 30.0
+    fit_room = int(np.floor(min((room - 1.0) / 2.0, 1.0e6)))
+    fit_40 = int(np.floor(min(0.4 * mfree / vecbytes / 2.0, 1.0e6)))
+    return max(min(cap, fit_room, fit_40), min(30, fit_room))
+
+
+def test_basis_size_from_free_memory(driver):
+    vecbytes = 8.0 * 4096 * 4096 * 2
+    # free memory in vectors -> what fits, by hand: below the floor of 8; between 8 and 30 (what fits behind the 30 other vectors);
+    # the 40 % bound; the cap of 120; a cap from the environment (it bounds only what goes beyond the default 30)
+    by_hand = [(40.0, -1, 2), (56.0, -1, 10), (80.0, -1, 21), (97.5, -1, 29), (300.0, -1, 60), (1000.0, -1, 120), (1e9, -1, 120),
+               (1000.0, 64, 64), (300.0, 64, 60), (1000.0, 8, 30), (80.0, 8, 21), (50.0, 8, 7), (1000.0, 4, 30), (1000.0, 500, 120)]
+    rows = [[nv * vecbytes, vecbytes, env] for nv, env, _ in by_hand]
+    grid = [[nv * vecbytes, vecbytes, env] for nv in np.linspace(31.3, 700.7, 97) for env in (-1, 8, 40, 120)]
+    out = driver('fit', rows + grid)
+    assert out.pop() == [30, 120, 8]
+    for (mfree, vb, env), (cap, fit), want in zip(rows, out, [w for _, _, w in by_hand]):
+        assert cap == (120 if env < 0 else max(8, min(env, 120)))
+        assert fit == want == fit_rule(mfree, vb, int(cap)), (mfree / vb, env, fit, want)
+    for (mfree, vb, env), (cap, fit) in zip(grid, out[len(rows):]):
+        assert fit == fit_rule(mfree, vb, int(cap)), (mfree / vb, env, fit)

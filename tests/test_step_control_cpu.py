@@ -1,7 +1,9 @@
 """CPU: the decisions of the step driver (ksfd_amd/csrc/step_control.h) on their own.  The header is plain C++ without device code and
 without the handle -- that the small driver below compiles with the host compiler alone is the proof -- so the driver exercises exactly
 what ksfd_step runs: the TSAdaptBasic controller against the oracle's, the stage-guess least squares against numpy, and the shift-floor
-search, the spectral back-off and the regime table against restatements of their rules in Python."""
+search, the spectral back-off and the regime table against restatements of their rules in Python; the verdict after a defect-correction
+sweep of the spectral solver (predicted last sweep, contraction memory) on residual histories with the verdicts written out by hand and
+on a grid against a restatement; the refresh schedule of the polynomial's eigenvalue estimate on a scripted run of steps."""
 import itertools
 import os
 import shutil
@@ -66,6 +68,37 @@ int main(int argc, char **argv)
             const Regime r = choose_regime(in);
             printf("%d %d %d %d %d\n", r.spec ? 1 : 0, r.mg ? 1 : 0, r.poly_wanted ? 1 : 0,
                    pipelined_allowed(in, r, r.poly_wanted) ? 1 : 0, pipelined_allowed(in, r, false) ? 1 : 0);
+        }
+    } else if (!strcmp(argv[1], "sweep")) {
+        /* a script over one StepMemo.  op 0: set (rho_step, rho_prev) = (a, b); 1: spec_rho_roll; 2: spec_sweep.  Every row prints
+           verdict (-1 for ops 0 and 1), rho_step, rho_prev, spec_pred_bound(m, rn, bn) */
+        StepMemo m;
+        for (int r = 0; r < n; r++) {
+            const int op = ri(), k = ri(), cap = ri(); const double rn = rd(), rprev = rd(), tol = rd(); const int guess = ri(), predict = ri(); const double bn = rd();
+            int v = -1;
+            if (op == 0) { m.spec_rho_step = rn; m.spec_rho_prev = rprev; }
+            else if (op == 1) spec_rho_roll(m);
+            else v = (int)spec_sweep(k, cap, rn, rprev, tol, guess != 0, predict != 0, m);
+            printf("%d %.17g %.17g %.17g\n", v, m.spec_rho_step, m.spec_rho_prev, spec_pred_bound(m, rn, bn));
+        }
+    } else if (!strcmp(argv[1], "specmisc")) {
+        for (int r = 0; r < n; r++) {
+            const int pc_type = ri(), backoff = ri(), mg_ok = ri(); const double stiff = rd(); const int sp = ri(), reserved = ri(); const double rtol = rd();
+            const int venv = ri(); const double rn = rd(), bn = rd(), grel = rd();
+            const bool zero = spec_handover(rn, bn);
+            printf("%d %d %d %d %.17g\n", spec_gmres_cap(pc_type, backoff), spec_fallback_mg(mg_ok != 0, stiff) ? 1 : 0,
+                   spec_predict_on(sp != 0, reserved, rtol, venv) ? 1 : 0, zero ? 1 : 0, spec_handover_rel(grel, zero, rn, bn));
+        }
+        printf("%d %.17g %.17g %.17g\n", SPEC_SWEEP_CAP, SPEC_SLOW_RATIO, SPEC_PRED_SAFETY, SPEC_PRED_MIN_RTOL);
+    } else if (!strcmp(argv[1], "lam")) {
+        /* one row per step: the estimate the power iteration would return if it ran.  Prints due, iterations, lam_age, lam_period */
+        StepMemo m;
+        for (int r = 0; r < n; r++) {
+            const double est = rd();
+            const bool due = lam_due(m);
+            int its = 0;
+            if (due) { const double before = m.lamJ; its = lam_power_its(before); m.lamJ = est; lam_estimated(m, before); }
+            printf("%d %d %d %d\n", due ? 1 : 0, its, m.lam_age, m.lam_period);
         }
     } else if (!strcmp(argv[1], "memo")) {          /* the initial values */
         StepMemo m;
@@ -301,3 +334,125 @@ def test_regime_table(driver):
         seen.add(tuple(want))
     # every regime occurs: spectral, V cycle, polynomial, pipelined, plain
     assert {(1, 0, 0, 0, 0), (0, 1, 0, 0, 0), (0, 0, 1, 0, 0), (0, 0, 1, 0, 1), (0, 0, 0, 1, 1), (0, 0, 0, 0, 0)} <= seen
+
+
+# ---- defect-correction sweeps of the spectral solver -----------------------------------------------------------------------------------
+NOT_FINITE, CONVERGED, SLOW, CONTINUE, FINAL = range(5)
+CAP = 24
+
+
+def _sweep_script(driver, rows):
+    """rows: ('set', rho_step, rho_prev) | ('roll',) | ('sweep', k, rn, rprev, tol, guess, predict[, cap]); ||b|| = 1"""
+    raw = []
+    for r in rows:
+        if r[0] == 'set':
+            raw.append([0, 0, 0, r[1], r[2], 0.0, 0, 0, 1.0])
+        elif r[0] == 'roll':
+            raw.append([1, 0, 0, 0.0, 0.0, 0.0, 0, 0, 1.0])
+        else:
+            _, k, rn, rprev, tol, guess, predict = r[:7]
+            raw.append([2, k, r[7] if len(r) > 7 else CAP, rn, rprev, tol, guess, predict, 1.0])
+    return driver('sweep', raw)
+
+
+def test_sweep_verdicts_on_scripted_histories(driver):
+    # contraction 0.01 per sweep from zero, no guess, nothing remembered, tol 1e-7: sweep 0 records nothing and predicts nothing; sweep 1
+    # records 0.01 but 4 * 0.01 * 1e-4 = 4e-6 > tol; sweep 2: 4 * 0.01 * 1e-6 = 4e-8 <= tol -- the next sweep is the predicted last one
+    out = _sweep_script(driver, [('sweep', 0, 1e-2, 1.0, 1e-7, 0, 1), ('sweep', 1, 1e-4, 1e-2, 1e-7, 0, 1), ('sweep', 2, 1e-6, 1e-4, 1e-7, 0, 1)])
+    assert [o[0] for o in out] == [CONTINUE, CONTINUE, FINAL]
+    assert out[0][1:3] == [0.0, 0.0]
+    assert out[1][1:3] == [1e-4 / 1e-2, 0.0] and out[2][1:3] == [max(1e-4 / 1e-2, 1e-6 / 1e-4), 0.0]
+    assert out[2][3] == 4.0 * out[2][1] * 1e-6                   # the bound a predicted exit reports (||b|| = 1)
+    # the previous step left rho_prev = 0.01 and tol = 1e-3 would allow 4 * 0.01 * 1e-2 = 4e-4 after sweep 0: from zero that sweep is
+    # not predicted from, with a guess it is
+    out = _sweep_script(driver, [('set', 0.0, 0.01), ('sweep', 0, 1e-2, 1.0, 1e-3, 0, 1), ('sweep', 0, 1e-2, 1.0, 1e-3, 1, 1),
+                                 ('sweep', 1, 1e-4, 1e-2, 1e-5, 0, 1)])
+    assert [o[0] for o in out[1:]] == [CONTINUE, FINAL, FINAL]
+    assert out[1][1:3] == [0.0, 0.01] and out[2][1:3] == [0.0, 0.01]      # sweep 0 is never recorded, guess or not
+    # with a guess but nothing remembered there is nothing to predict from
+    assert _sweep_script(driver, [('sweep', 0, 1e-2, 1.0, 1e-3, 1, 1)])[0][0] == CONTINUE
+    # exactly a quarter is not slow, the next double above it is; neither a slow nor a converged sweep is recorded
+    above = float(np.nextafter(0.25, 1.0))
+    out = _sweep_script(driver, [('sweep', 1, 0.25, 1.0, 1e-7, 0, 1), ('set', 0.0, 0.0), ('sweep', 1, above, 1.0, 1e-7, 0, 1),
+                                 ('sweep', 1, 1e-8, 1.0, 1e-7, 0, 1), ('sweep', 1, float('nan'), 1.0, 1e-7, 0, 1)])
+    assert [o[0] for o in out] == [CONTINUE, -1, SLOW, CONVERGED, NOT_FINITE]
+    assert out[0][1] == 0.25 and out[2][1] == 0.0 and out[3][1] == 0.0 and out[4][1] == 0.0
+    # no predicted last sweep when there is no sweep left under the cap
+    out = _sweep_script(driver, [('set', 0.0, 0.01), ('sweep', CAP - 2, 1e-4, 1e-2, 1e-5, 0, 1), ('sweep', CAP - 1, 1e-4, 1e-2, 1e-5, 0, 1),
+                                 ('sweep', 2, 1e-4, 1e-2, 1e-5, 0, 1, 3), ('sweep', 1, 1e-4, 1e-2, 1e-5, 0, 1, 3)])
+    assert [o[0] for o in out[1:]] == [FINAL, CONTINUE, CONTINUE, FINAL]
+    # prediction off: plain continue everywhere, the memory still fills
+    out = _sweep_script(driver, [('set', 0.0, 0.01), ('sweep', 0, 1e-2, 1.0, 1e-3, 1, 0), ('sweep', 1, 1e-4, 1e-2, 1e-5, 0, 0),
+                                 ('sweep', 2, 1e-6, 1e-4, 1e-7, 1, 0)])
+    assert [o[0] for o in out[1:]] == [CONTINUE] * 3 and out[3][1] > 0.0
+    # start of a step: this step's maximum replaces the last one's; a step that recorded none keeps the previous one
+    out = _sweep_script(driver, [('set', 0.02, 0.01), ('roll',), ('roll',), ('set', 0.0, 0.0), ('roll',)])
+    assert [o[1:3] for o in out] == [[0.02, 0.01], [0.0, 0.02], [0.0, 0.02], [0.0, 0.0], [0.0, 0.0]]
+
+
+def sweep_rule(k, cap, rn, rprev, tol, guess, predict, rho_step, rho_prev):
+    """spec_solve's rule after the true residual of sweep k, restated: -> (verdict, rho_step)"""
+    if rn != rn:
+        return NOT_FINITE, rho_step
+    if rn <= tol:
+        return CONVERGED, rho_step
+    if rn > 0.25 * rprev:
+        return SLOW, rho_step
+    if k >= 1:
+        rho_step = max(rho_step, rn / rprev)
+    rho_hat = max(rho_step, rho_prev)
+    final = predict and rho_hat > 0.0 and (k >= 1 or guess) and k + 1 < cap and 4.0 * rho_hat * rn <= tol
+    return (FINAL if final else CONTINUE), rho_step
+
+
+def test_sweep_verdict_grid(driver):
+    ratios = [1e-3, 0.1, 0.25, float(np.nextafter(0.25, 1.0)), 0.5, float('nan')]
+    over_tol = [0.5, 1.0, float(np.nextafter(1.0, 2.0)), 3.0, 30.0, 1e3]         # rn / tol
+    rows, want = [], []
+    for k, ratio, ot, guess, predict, rho_prev, rho_step in itertools.product(
+            [0, 1, 2, CAP - 2, CAP - 1], ratios, over_tol, (0, 1), (0, 1), [0.0, 0.005, 0.05, 0.3], [0.0, 0.02]):
+        rprev = 0.5
+        rn = ratio * rprev
+        tol = rn / ot if rn == rn else 1e-6
+        rows += [('set', rho_step, rho_prev), ('sweep', k, rn, rprev, tol, guess, predict)]
+        want.append(sweep_rule(k, CAP, rn, rprev, tol, guess, predict, rho_step, rho_prev))
+    out = _sweep_script(driver, rows)[1::2]
+    assert len(out) == len(want)
+    for (v, rs, rp, _), (wv, wrs), row in zip(out, want, rows[1::2]):
+        assert (v, rs) == (wv, wrs), (row, v, rs, wv, wrs)
+    assert {w[0] for w in want} == {NOT_FINITE, CONVERGED, SLOW, CONTINUE, FINAL}
+
+
+def test_spectral_attempt_rules(driver):
+    rows = []
+    for pc, backoff, mg_ok, stiff, sp, res, rtol, venv, (rn, bn) in itertools.product(
+            (0, 2, 4), (8, 9, 16, 512), (0, 1), (0.3, float(np.nextafter(0.3, 1.0)), 5.0), (0, 1), (0, 8, 9), (1e-6, 1e-8, float(np.nextafter(1e-8, 0.0))),
+            (0, 1, 2), [(0.5, 1.0), (1.0, 1.0), (2.0, 1.0), (float('nan'), 1.0)]):
+        rows.append([pc, backoff, mg_ok, stiff, sp, res, rtol, venv, rn, bn, 1e-3])
+    out = driver('specmisc', rows)
+    assert out.pop() == [24, 0.25, 4.0, 1e-8]
+    assert len(out) == len(rows)
+    for (pc, backoff, mg_ok, stiff, sp, res, rtol, venv, rn, bn, grel), got in zip(rows, out):
+        zero = not rn < bn                                          # the sweeps made it worse (or NaN): restart from zero
+        want = [(8 if backoff > 8 else 40) if pc == 2 else 0, int(bool(mg_ok) and stiff > 0.3),
+                int(bool(sp) and not (res & 8) and rtol >= 1e-8 and venv != 2), int(zero), grel * (1.0 if zero else rn / bn)]
+        assert got == want, (pc, backoff, mg_ok, stiff, sp, res, rtol, venv, rn, bn, got, want)
+
+
+def test_eigenvalue_estimate_policy(driver):
+    # estimates as the power iteration would return them, one per step (looked at only on the steps where one is due)
+    est = [10.0] + [10.1] * 22 + [10.1 * 1.03] + [10.4] * 3
+    out = driver('lam', [[e] for e in est])
+    due = [k for k, o in enumerate(out) if o[0] == 1]
+    # first step: due, 8 iterations; then every period steps with 2; the period doubles 1, 2, 4, 8, 8 while the estimate holds still,
+    # so estimates fall on steps 0, 1, 3, 7, 15, 23; the 3 % move at step 23 resets it to 1: step 24 is due again
+    assert due == [0, 1, 3, 7, 15, 23, 24, 26]
+    assert [out[k][1] for k in due] == [8] + [2] * 7
+    assert [out[k][3] for k in due] == [1, 2, 4, 8, 8, 1, 2, 4]
+    assert all(o[1] == 0 for k, o in enumerate(out) if k not in due)
+    # lam_age: untouched on the first step (there is no estimate yet), then steps since the last estimate
+    want_age, last = [], 0
+    for k in range(len(est)):
+        last = k if k in due else last
+        want_age.append(k - last)
+    assert [o[2] for o in out] == want_age
