@@ -10,237 +10,106 @@
 // right-preconditioned GMRES applies.  1-D, 2-D and 3-D, single rank or slab ranks.
 // Slab ranks: every level is distributed like level 0 (ghost units, halo exchange) down to the last level on which a rank keeps >= 4
 // slow units; ksfd_set_mg_agglomerate (opt-in, 2-D and 3-D) continues below it with REPLICATED levels that every rank holds whole and
-// computes redundantly with wrapped indices -- the *_border kernels below carry vectors and coefficient planes across.  What the one
-// all-reduce per cycle costs between devices against the halo exchanges it saves has not been measured.
+// computes redundantly with wrapped indices.  What the one all-reduce per cycle costs between devices against the halo exchanges it
+// saves has not been measured.
+// Transfers: ONE restriction kernel and ONE prolongation kernel (k_mg_restrict, k_mg_prolong_add) for every dimension, storage type and
+// placement; one rank, slab ranks and the border to the replicated levels differ in the slow-axis descriptor KMGSlow (and the border
+// is an instance of its own, BORDER, of the same text).
 #pragma once
 #include "stencil.hip.h"
 
-// coarse(I,J) = sum_{a,b in -1..1} w_a w_b fine(2I+a, 2J+b), w = (1/4, 1/2, 1/4).  x is periodic; the row axis either
-// wraps (one rank) or reads the ghost rows at local index -1 / nyf (slab ranks: the fine vector's halo must be current
-// and the slab must start on an even global row).  foff/coff = offset of local row 0 inside a plane (ng*nx).
-// TF / TK: storage type of the fine / coarse vector (the V cycle runs its level vectors in fp32 when the solve tolerance allows: mg_host.hip.h)
-template <typename TF = double, typename TK = double>
-__global__ void __launch_bounds__(KSFD_BLOCK) k_restrict2d(int nplanes, long long nxf, long long nyf, int wrap,
-                                                           const TF *__restrict__ fine, long long fplane, long long foff,
-                                                           TK *__restrict__ coarse, long long cplane, long long coff)
+// The slow axis of a transfer between a fine level and the next coarser one (x in 1-D, y in 2-D, z in 3-D; a slow unit is a point, a row
+// or a plane).  The inner axes are periodic and whole on every rank; the slow axis is this rank's slab, and how it is indexed is all
+// that distinguishes one rank from slab ranks from the border below a replicated level: mg_host.hip.h (mg_slow) fills this in.
+struct KMGSlow {
+    long long nf;    // fine slow units this rank holds
+    long long u0;    // restriction: first coarse slow unit of this rank's part inside the coarse array
+                     // prolongation: first (global) fine slow unit of this rank's slab; 0 except across the border
+    long long nc;    // slow extent of the coarse ARRAY: nf/2, or the global coarse extent across the border
+    int wrap;        // slow neighbours wrap (one rank, replicated level) or are ghost units (slab ranks: the halo must be current)
+};
+
+// Full weighting: coarse(I,J,K) = sum_{a,b,d in -1..1} w_a w_b w_d fine(2I+d, 2J+b, 2K+a), w = (1/4, 1/2, 1/4), over the DIM axes the
+// grid has.  The slow neighbours wrap or are the ghost units at local index -1 / nf (the slab must start on an even global unit).
+// foff/coff = offset of local slow unit 0 inside a field plane (ng*inner).  TF / TK: storage type of the fine / coarse vector (the V
+// cycle runs its level vectors in fp32 when the solve tolerance allows: mg_host.hip.h); the arithmetic is fp64.
+// Across the border between the last distributed level (fine: this rank's slab with its ghost units) and the first replicated one
+// (coarse: the WHOLE level on every rank, no ghost units; ksfd_set_mg_agglomerate) the kernel runs over the whole coarse array: the rank
+// full-weights its own units into its part [u0, u0 + nf/2) and writes zeros everywhere else, so that the sum over the ranks (the
+// transport's all-reduce; adding zeros is exact) is the gathered coarse vector, the same bits on every rank.  There the slow
+// neighbours never wrap.  Everywhere else u0 = 0 and nc = nf/2: every coarse unit is the rank's own.
+// BORDER: the same text compiled for the border alone, so that the launches of every other level pair carry neither the ownership test
+// nor the offset (one trace had them 1-2 us slower on 4096^2 with both folded into one instance: profiles/mg_transfer_refactor.log)
+template <int DIM, bool BORDER, typename TF, typename TK>
+__global__ void __launch_bounds__(KSFD_BLOCK) k_mg_restrict(int nplanes, long long nxf, long long nyf, KMGSlow Z,
+                                                            const TF *__restrict__ fine, long long fplane, long long foff,
+                                                            TK *__restrict__ coarse, long long cplane, long long coff)
 {
-    const long long nxc = nxf >> 1, nyc = nyf >> 1, nc = nxc * nyc;
+    const long long nxc = DIM > 1 ? nxf >> 1 : 1, nyc = DIM > 2 ? nyf >> 1 : 1, nsc = Z.nf >> 1, n = nxc * nyc * Z.nc;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nc; p += stride) {
-        const long long I = p % nxc, J = p / nxc;
-        const long long i0 = 2 * I, j0 = 2 * J;
-        const long long im = (i0 + nxf - 1) % nxf, ip = (i0 + 1) % nxf;
-        const long long jm = wrap ? (j0 + nyf - 1) % nyf : j0 - 1, jp = wrap ? (j0 + 1) % nyf : j0 + 1;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
+        const long long I = p % nxc, J = (p / nxc) % nyc, S = p / (nxc * nyc) - (BORDER ? Z.u0 : 0);
+        const bool own = !BORDER || (S >= 0 && S < nsc), wrap = !BORDER && Z.wrap;
+        long long xi[3], yj[3], zk[3];                          // fine indices -1, 0, +1 around (2I, 2J, 2S); the slow one is zk
+        xi[1] = 2 * I; xi[0] = (xi[1] + nxf - 1) % nxf; xi[2] = (xi[1] + 1) % nxf;
+        yj[1] = 2 * J; yj[0] = (yj[1] + nyf - 1) % nyf; yj[2] = (yj[1] + 1) % nyf;
+        zk[1] = 2 * S; zk[0] = wrap ? (zk[1] + Z.nf - 1) % Z.nf : zk[1] - 1; zk[2] = wrap ? (zk[1] + 1) % Z.nf : zk[1] + 1;
         for (int c = 0; c < nplanes; c++) {
-            const TF *f = fine + (long long)c * fplane + foff;
-            const double s = 0.25 * (double)f[i0 + nxf * j0] +
-                             0.125 * ((double)f[im + nxf * j0] + (double)f[ip + nxf * j0] + (double)f[i0 + nxf * jm] + (double)f[i0 + nxf * jp]) +
-                             0.0625 * ((double)f[im + nxf * jm] + (double)f[ip + nxf * jm] + (double)f[im + nxf * jp] + (double)f[ip + nxf * jp]);
+            double s = 0.0;
+            if (own) {
+                const TF *f = fine + (long long)c * fplane + foff;
+                if constexpr (DIM == 1) {
+                    s = 0.5 * (double)f[zk[1]] + 0.25 * ((double)f[zk[0]] + (double)f[zk[2]]);
+                } else if constexpr (DIM == 2) {
+                    const long long im = xi[0], i0 = xi[1], ip = xi[2], jm = zk[0], j0 = zk[1], jp = zk[2];
+                    s = 0.25 * (double)f[i0 + nxf * j0] +
+                        0.125 * ((double)f[im + nxf * j0] + (double)f[ip + nxf * j0] + (double)f[i0 + nxf * jm] + (double)f[i0 + nxf * jp]) +
+                        0.0625 * ((double)f[im + nxf * jm] + (double)f[ip + nxf * jm] + (double)f[im + nxf * jp] + (double)f[ip + nxf * jp]);
+                } else {
+                    const double w[3] = { 0.25, 0.5, 0.25 };
+#pragma unroll
+                    for (int a = 0; a < 3; a++)
+#pragma unroll
+                        for (int b = 0; b < 3; b++)
+#pragma unroll
+                            for (int d = 0; d < 3; d++) s += w[a] * w[b] * w[d] * (double)f[xi[d] + nxf * (yj[b] + nyf * zk[a])];
+                }
+            }
             coarse[(long long)c * cplane + coff + p] = (TK)s;
         }
     }
 }
 
-// fine += P coarse (bilinear interpolation); row axis wraps or reads the coarse ghost row nyc (slab ranks)
-template <typename TK = double, typename TF = double>
-__global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add2d(int nplanes, long long nxf, long long nyf, int wrap,
-                                                              const TK *__restrict__ coarse, long long cplane, long long coff,
-                                                              TF *__restrict__ fine, long long fplane, long long foff)
+// fine += P coarse: linear interpolation along each of the DIM axes.  k = the global fine slow unit (u0 is the slab's first one across
+// the border, where the whole coarse array is indexed with wrapped global units; 0 otherwise); the coarse neighbour K + 1 of an odd
+// unit wraps modulo nc or is the coarse ghost unit nc (slab ranks: the coarse halo must be current).
+template <int DIM, bool BORDER, typename TK, typename TF>
+__global__ void __launch_bounds__(KSFD_BLOCK) k_mg_prolong_add(int nplanes, long long nxf, long long nyf, KMGSlow Z,
+                                                               const TK *__restrict__ coarse, long long cplane, long long coff,
+                                                               TF *__restrict__ fine, long long fplane, long long foff)
 {
-    const long long nxc = nxf >> 1, nyc = nyf >> 1, nf = nxf * nyf;
+    const long long nxc = DIM > 1 ? nxf >> 1 : 1, nyc = DIM > 2 ? nyf >> 1 : 1;
+    const long long nxi = DIM > 1 ? nxf : 1, nyi = DIM > 2 ? nyf : 1, n = nxi * nyi * Z.nf;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nf; p += stride) {
-        const long long i = p % nxf, j = p / nxf;
-        const long long I = i >> 1, J = j >> 1;
-        const long long I1 = (i & 1) ? (I + 1) % nxc : I;
-        const long long J1 = (j & 1) ? (wrap ? (J + 1) % nyc : J + 1) : J;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
+        const long long i = p % nxi, j = (p / nxi) % nyi, k = (BORDER ? Z.u0 : 0) + p / (nxi * nyi);
+        const long long I = i >> 1, J = j >> 1, K = k >> 1;
+        const long long I1 = (i & 1) ? (I + 1) % nxc : I, J1 = (j & 1) ? (J + 1) % nyc : J;
+        const long long K1 = (k & 1) ? ((BORDER || Z.wrap) ? (K + 1) % Z.nc : K + 1) : K;
         for (int c = 0; c < nplanes; c++) {
             const TK *q = coarse + (long long)c * cplane + coff;
-            const double v = 0.25 * ((double)q[I + nxc * J] + (double)q[I1 + nxc * J] + (double)q[I + nxc * J1] + (double)q[I1 + nxc * J1]);
-            fine[(long long)c * fplane + foff + p] = (TF)((double)fine[(long long)c * fplane + foff + p] + v);
-        }
-    }
-}
-
-// 1-D transfer operators (the slab axis is x itself): weights (1/4, 1/2, 1/4) and linear interpolation; the axis wraps
-// (one rank) or reads the ghost points at local index -1 / nf (slab ranks).
-__global__ void __launch_bounds__(KSFD_BLOCK) k_restrict1d(int nplanes, long long nf, int wrap,
-                                                           const double *__restrict__ fine, long long fplane, long long foff,
-                                                           double *__restrict__ coarse, long long cplane, long long coff)
-{
-    const long long nc = nf >> 1;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nc; p += stride) {
-        const long long i0 = 2 * p;
-        const long long im = wrap ? (i0 + nf - 1) % nf : i0 - 1, ip = wrap ? (i0 + 1) % nf : i0 + 1;
-        for (int c = 0; c < nplanes; c++) {
-            const double *f = fine + (long long)c * fplane + foff;
-            coarse[(long long)c * cplane + coff + p] = 0.5 * f[i0] + 0.25 * (f[im] + f[ip]);
-        }
-    }
-}
-__global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add1d(int nplanes, long long nf, int wrap,
-                                                              const double *__restrict__ coarse, long long cplane, long long coff,
-                                                              double *__restrict__ fine, long long fplane, long long foff)
-{
-    const long long nc = nf >> 1;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nf; p += stride) {
-        const long long I = p >> 1;
-        const long long I1 = (p & 1) ? (wrap ? (I + 1) % nc : I + 1) : I;
-        for (int c = 0; c < nplanes; c++) {
-            const double *q = coarse + (long long)c * cplane + coff;
-            fine[(long long)c * fplane + foff + p] += 0.5 * (q[I] + q[I1]);
-        }
-    }
-}
-
-// 3-D transfer operators (slab axis = z): 27-point full weighting and trilinear interpolation.  x and y wrap; z wraps
-// (one rank) or reads ghost planes -1 / nzf (slab ranks).  foff/coff = offset of local plane 0 inside a field plane.
-__global__ void __launch_bounds__(KSFD_BLOCK) k_restrict3d(int nplanes, long long nxf, long long nyf, long long nzf, int wrap,
-                                                           const double *__restrict__ fine, long long fplane, long long foff,
-                                                           double *__restrict__ coarse, long long cplane, long long coff)
-{
-    const long long nxc = nxf >> 1, nyc = nyf >> 1, nzc = nzf >> 1, nc = nxc * nyc * nzc;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nc; p += stride) {
-        const long long I = p % nxc, J = (p / nxc) % nyc, K = p / (nxc * nyc);
-        long long xi[3], yj[3], zk[3];
-        xi[1] = 2 * I; xi[0] = (xi[1] + nxf - 1) % nxf; xi[2] = (xi[1] + 1) % nxf;
-        yj[1] = 2 * J; yj[0] = (yj[1] + nyf - 1) % nyf; yj[2] = (yj[1] + 1) % nyf;
-        zk[1] = 2 * K; zk[0] = wrap ? (zk[1] + nzf - 1) % nzf : zk[1] - 1; zk[2] = wrap ? (zk[1] + 1) % nzf : zk[1] + 1;
-        const double w[3] = { 0.25, 0.5, 0.25 };
-        for (int c = 0; c < nplanes; c++) {
-            const double *f = fine + (long long)c * fplane + foff;
-            double s = 0.0;
-#pragma unroll
-            for (int a = 0; a < 3; a++)
-#pragma unroll
-                for (int b = 0; b < 3; b++)
-#pragma unroll
-                    for (int d = 0; d < 3; d++) s += w[a] * w[b] * w[d] * f[xi[d] + nxf * (yj[b] + nyf * zk[a])];
-            coarse[(long long)c * cplane + coff + p] = s;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add3d(int nplanes, long long nxf, long long nyf, long long nzf, int wrap,
-                                                              const double *__restrict__ coarse, long long cplane, long long coff,
-                                                              double *__restrict__ fine, long long fplane, long long foff)
-{
-    const long long nxc = nxf >> 1, nyc = nyf >> 1, nzc = nzf >> 1, nf = nxf * nyf * nzf;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nf; p += stride) {
-        const long long i = p % nxf, j = (p / nxf) % nyf, k = p / (nxf * nyf);
-        const long long I = i >> 1, J = j >> 1, K = k >> 1;
-        const long long I1 = (i & 1) ? (I + 1) % nxc : I, J1 = (j & 1) ? (J + 1) % nyc : J;
-        const long long K1 = (k & 1) ? (wrap ? (K + 1) % nzc : K + 1) : K;
-        for (int c = 0; c < nplanes; c++) {
-            const double *q = coarse + (long long)c * cplane + coff;
-            const double v = 0.125 * (q[I + nxc * (J + nyc * K)] + q[I1 + nxc * (J + nyc * K)] + q[I + nxc * (J1 + nyc * K)] +
-                                      q[I1 + nxc * (J1 + nyc * K)] + q[I + nxc * (J + nyc * K1)] + q[I1 + nxc * (J + nyc * K1)] +
-                                      q[I + nxc * (J1 + nyc * K1)] + q[I1 + nxc * (J1 + nyc * K1)]);
-            fine[(long long)c * fplane + foff + p] += v;
-        }
-    }
-}
-
-// Transfers across the border between the last distributed level (fine: this rank's slab with its ghost units) and the first replicated
-// level (coarse: the WHOLE level on every rank, no ghost units; ksfd_set_mg_agglomerate).  Same weights as above.
-// Restriction: the rank full-weights its own rows into its slice [row0c, row0c + nyf/2) of the whole coarse vector and writes zeros
-// everywhere else, so that the sum over the ranks (the transport's all-reduce; adding zeros is exact) is the gathered coarse vector,
-// the same bits on every rank.  The fine ghost rows must be current and the slab starts on an even global row.  nycg: global coarse rows.
-template <typename TF = double>
-__global__ void __launch_bounds__(KSFD_BLOCK) k_restrict2d_border(int nplanes, long long nxf, long long nyf, long long row0c, long long nycg,
-                                                                  const TF *__restrict__ fine, long long fplane, long long foff,
-                                                                  double *__restrict__ coarse, long long cplane)
-{
-    const long long nxc = nxf >> 1, nyc = nyf >> 1, nc = nxc * nycg;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nc; p += stride) {
-        const long long I = p % nxc, J = p / nxc - row0c;
-        const bool own = J >= 0 && J < nyc;
-        const long long i0 = 2 * I, j0 = 2 * J;
-        const long long im = (i0 + nxf - 1) % nxf, ip = (i0 + 1) % nxf, jm = j0 - 1, jp = j0 + 1;
-        for (int c = 0; c < nplanes; c++) {
-            double s = 0.0;
-            if (own) {
-                const TF *f = fine + (long long)c * fplane + foff;
-                s = 0.25 * (double)f[i0 + nxf * j0] +
-                    0.125 * ((double)f[im + nxf * j0] + (double)f[ip + nxf * j0] + (double)f[i0 + nxf * jm] + (double)f[i0 + nxf * jp]) +
-                    0.0625 * ((double)f[im + nxf * jm] + (double)f[ip + nxf * jm] + (double)f[im + nxf * jp] + (double)f[ip + nxf * jp]);
+            const long long o = (long long)c * fplane + foff + p;
+            if constexpr (DIM == 1) {
+                fine[o] = (TF)((double)fine[o] + 0.5 * ((double)q[K] + (double)q[K1]));
+            } else if constexpr (DIM == 2) {
+                const double v = 0.25 * ((double)q[I + nxc * K] + (double)q[I1 + nxc * K] + (double)q[I + nxc * K1] + (double)q[I1 + nxc * K1]);
+                fine[o] = (TF)((double)fine[o] + v);
+            } else {
+                const double v = 0.125 * ((double)q[I + nxc * (J + nyc * K)] + (double)q[I1 + nxc * (J + nyc * K)] + (double)q[I + nxc * (J1 + nyc * K)] +
+                                          (double)q[I1 + nxc * (J1 + nyc * K)] + (double)q[I + nxc * (J + nyc * K1)] + (double)q[I1 + nxc * (J + nyc * K1)] +
+                                          (double)q[I + nxc * (J1 + nyc * K1)] + (double)q[I1 + nxc * (J1 + nyc * K1)]);
+                fine[o] = (TF)((double)fine[o] + v);
             }
-            coarse[(long long)c * cplane + p] = s;
-        }
-    }
-}
-// Prolongation: the rank interpolates its own fine rows [row0f, row0f + nyf) from the whole coarse vector with wrapped global indices
-template <typename TF = double>
-__global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add2d_border(int nplanes, long long nxf, long long nyf, long long row0f, long long nycg,
-                                                                     const double *__restrict__ coarse, long long cplane,
-                                                                     TF *__restrict__ fine, long long fplane, long long foff)
-{
-    const long long nxc = nxf >> 1, nf = nxf * nyf;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nf; p += stride) {
-        const long long i = p % nxf, j = row0f + p / nxf;
-        const long long I = i >> 1, J = j >> 1;
-        const long long I1 = (i & 1) ? (I + 1) % nxc : I;
-        const long long J1 = (j & 1) ? (J + 1) % nycg : J;
-        for (int c = 0; c < nplanes; c++) {
-            const double *q = coarse + (long long)c * cplane;
-            const double v = 0.25 * (q[I + nxc * J] + q[I1 + nxc * J] + q[I + nxc * J1] + q[I1 + nxc * J1]);
-            fine[(long long)c * fplane + foff + p] = (TF)((double)fine[(long long)c * fplane + foff + p] + v);
-        }
-    }
-}
-// ... in 3-D (slab axis z): planes [pl0c, pl0c + nzf/2) of nzcg coarse planes; fine planes [pl0f, pl0f + nzf)
-__global__ void __launch_bounds__(KSFD_BLOCK) k_restrict3d_border(int nplanes, long long nxf, long long nyf, long long nzf, long long pl0c, long long nzcg,
-                                                                  const double *__restrict__ fine, long long fplane, long long foff,
-                                                                  double *__restrict__ coarse, long long cplane)
-{
-    const long long nxc = nxf >> 1, nyc = nyf >> 1, nzc = nzf >> 1, nc = nxc * nyc * nzcg;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nc; p += stride) {
-        const long long I = p % nxc, J = (p / nxc) % nyc, K = p / (nxc * nyc) - pl0c;
-        const bool own = K >= 0 && K < nzc;
-        long long xi[3], yj[3], zk[3];
-        xi[1] = 2 * I; xi[0] = (xi[1] + nxf - 1) % nxf; xi[2] = (xi[1] + 1) % nxf;
-        yj[1] = 2 * J; yj[0] = (yj[1] + nyf - 1) % nyf; yj[2] = (yj[1] + 1) % nyf;
-        zk[1] = 2 * K; zk[0] = zk[1] - 1; zk[2] = zk[1] + 1;
-        const double w[3] = { 0.25, 0.5, 0.25 };
-        for (int c = 0; c < nplanes; c++) {
-            double s = 0.0;
-            if (own) {
-                const double *f = fine + (long long)c * fplane + foff;
-#pragma unroll
-                for (int a = 0; a < 3; a++)
-#pragma unroll
-                    for (int b = 0; b < 3; b++)
-#pragma unroll
-                        for (int d = 0; d < 3; d++) s += w[a] * w[b] * w[d] * f[xi[d] + nxf * (yj[b] + nyf * zk[a])];
-            }
-            coarse[(long long)c * cplane + p] = s;
-        }
-    }
-}
-__global__ void __launch_bounds__(KSFD_BLOCK) k_prolong_add3d_border(int nplanes, long long nxf, long long nyf, long long nzf, long long pl0f, long long nzcg,
-                                                                     const double *__restrict__ coarse, long long cplane,
-                                                                     double *__restrict__ fine, long long fplane, long long foff)
-{
-    const long long nxc = nxf >> 1, nyc = nyf >> 1, nf = nxf * nyf * nzf;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < nf; p += stride) {
-        const long long i = p % nxf, j = (p / nxf) % nyf, k = pl0f + p / (nxf * nyf);
-        const long long I = i >> 1, J = j >> 1, K = k >> 1;
-        const long long I1 = (i & 1) ? (I + 1) % nxc : I, J1 = (j & 1) ? (J + 1) % nyc : J;
-        const long long K1 = (k & 1) ? (K + 1) % nzcg : K;
-        for (int c = 0; c < nplanes; c++) {
-            const double *q = coarse + (long long)c * cplane;
-            const double v = 0.125 * (q[I + nxc * (J + nyc * K)] + q[I1 + nxc * (J + nyc * K)] + q[I + nxc * (J1 + nyc * K)] +
-                                      q[I1 + nxc * (J1 + nyc * K)] + q[I + nxc * (J + nyc * K1)] + q[I1 + nxc * (J + nyc * K1)] +
-                                      q[I + nxc * (J1 + nyc * K1)] + q[I1 + nxc * (J1 + nyc * K1)]);
-            fine[(long long)c * fplane + foff + p] += v;
         }
     }
 }

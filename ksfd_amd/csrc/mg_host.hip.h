@@ -67,39 +67,20 @@ static int mg_push_level(ksfd_handle *h, long long nx, long long ny, long long r
 static int mg_build(ksfd_handle *h)
 {
     const int dim = h->G.dim, nl = h->P.nlig;
-    long long nx = h->G.nx, ny = dim == 3 ? h->G.ny : 1, rows = h->G.sloc;   // rows = local slow units (y rows in 2-D, z planes in 3-D)
-    // NOTE: every decision below must be identical on all ranks (the levels exchange halos): use sloc, never slow0.
-    // Slab r starts at unit r*sloc; it stays on the coarse grid of level l as long as sloc is divisible by 2^l.
-    // Coarse-level agglomeration (h->mg_agg > 0): the plan says how many levels stay distributed and which replicated ones follow
-    ksfd_ctl::MGPlanLevel plan[64];
-    int nplan = 0, ndist = 0;
-    if (h->mg_agg > 0) {
-        const long long nglob[3] = { dim == 1 ? rows * h->size : nx, dim == 2 ? rows * h->size : ny, dim == 3 ? rows * h->size : 1 };
-        nplan = ksfd_ctl::mg_agglomerate_plan(dim, nglob, h->size, h->ring ? 1 : 0, h->mg_agg, plan, 64);
-        while (ndist < nplan && !plan[ndist].rep) ndist++;
-    }
+    // The level list is the plan's (mg_agglomerate_plan.h: a pure function of the global extents, the rank count and the ring, so every
+    // rank builds the same hierarchy; h->mg_agg = 0 gives the plain slab rule).  sloc: this rank's slow units (y rows in 2-D, z planes
+    // in 3-D) on a distributed level, the global slow extent on a replicated one
+    constexpr int cap = 64;
+    ksfd_ctl::MGPlanLevel plan[cap];
+    const long long slow = h->G.sloc * h->size;
+    const long long nglob[3] = { dim == 1 ? slow : h->G.nx, dim == 2 ? slow : dim == 3 ? h->G.ny : 1, dim == 3 ? slow : 1 };
+    const int nplan = ksfd_ctl::mg_agglomerate_plan(dim, nglob, h->size, h->ring ? 1 : 0, h->mg_agg, plan, cap);
+    if (nplan < 1) return fail(h, KSFD_EINVAL, "multigrid: the level plan describes no grid");
+    if (nplan == cap) return fail(h, KSFD_EINVAL, "multigrid: more than %d levels", cap - 1);
     KPhys P = h->P;
-    auto coarser = [&]() {
-        nx /= 2; rows /= 2;
-        if (dim == 3) ny /= 2;
-        for (int a = 0; a < 3; a++) { P.inv_h[a] *= 0.5; P.inv_h2[a] *= 0.25; }
-    };
-    for (int l = 0;; l++) {
-        int rc = mg_push_level(h, nx, ny, rows, P, false);
-        if (rc) return rc;
-        if (nplan > 0 && l + 1 == ndist) break;                               // the plan replicates the next level
-        // next level: every rank keeps >= 4 slow units (ghost width 2 + the 4th-order star), global grid >= 8 per axis
-        const long long rows_glob = rows * h->size;
-        if ((dim > 1 && ((nx % 2) || nx / 2 < 8)) || (rows % 2) || rows_glob / 2 < 8 || (h->ring && rows / 2 < 4)) break;
-        if (dim == 3 && ((ny % 2) || ny / 2 < 8)) break;
-        coarser();
-    }
-    // replicated levels: the global slow extent from here on (the plan's distributed prefix is the list of the loop above)
-    if (nplan > 0 && (int)h->mg.size() != ndist) return fail(h, KSFD_EINVAL, "multigrid: the agglomeration plan and the slab rule disagree on the distributed levels");
-    for (int l = ndist; l < nplan; l++) {
-        coarser();
-        if (l == ndist) rows *= h->size;
-        int rc = mg_push_level(h, nx, ny, rows, P, true);
+    for (int l = 0; l < nplan; l++) {
+        if (l) for (int a = 0; a < 3; a++) { P.inv_h[a] *= 0.5; P.inv_h2[a] *= 0.25; }
+        int rc = mg_push_level(h, plan[l].n[0], plan[l].n[1], plan[l].sloc, P, plan[l].rep != 0);
         if (rc) return rc;
     }
     h->mg_ok = h->mg.size() >= 2;
@@ -125,7 +106,7 @@ static int mg_build(ksfd_handle *h)
 
 // transfer operators for the storage types of the fine and the coarse vector.  fp64 on both sides: 1-D, 2-D or 3-D by the level geometry;
 // any other pair exists in 2-D only (levels with fp32 vectors, the fp32 coefficient copy)
-// Across the border from the last distributed level Lf to the first replicated one Lc (mg.hip.h: k_restrict2d_border) the restriction
+// Across the border from the last distributed level Lf to the first replicated one Lc (mg.hip.h: KMGSlow, k_mg_restrict) the restriction
 // is a launch (here) and one all-reduce of the whole coarse vector (mg_border_reduce, which the caller runs behind the launch and
 // outside the launch's Scope: the all-reduce is booked as communication, once), the prolongation a launch; the coarse side is fp64
 static inline bool mg_border(const MGLevel &Lf, const MGLevel &Lc) { return Lc.rep && !Lf.rep; }
@@ -141,69 +122,67 @@ template <typename T> static int mg_border_reduce(ksfd_handle *h, const MGLevel 
 {
     return mg_border(Lf, Lc) ? fail(h, KSFD_EINVAL, "multigrid: a replicated level has fp64 vectors") : KSFD_OK;
 }
+// the slow axis of the transfers between Lf and Lc on this rank (mg.hip.h: KMGSlow).  Lc.G.sloc is the slow extent of the coarse array
+// on either side of the border: half the rank's fine units, or the whole replicated level
+static KMGSlow mg_slow(const ksfd_handle *h, const MGLevel &Lf, const MGLevel &Lc, bool restriction)
+{
+    const bool border = mg_border(Lf, Lc);
+    const long long u0f = border ? (long long)h->rank * Lf.G.sloc : 0;       // first fine slow unit of this rank's slab
+    // across the border (the kernels' BORDER instances) the fine side has ghost units (no wrap) and the coarse side is whole (wrap)
+    return { Lf.G.sloc, restriction ? u0f / 2 : u0f, Lc.G.sloc, border ? (restriction ? 0 : 1) : (int)Lf.G.wrap_slow };
+}
+// what no transfer exists for
+template <typename TF, typename TK>
+static int mg_transfer_refused(ksfd_handle *h, const MGLevel &Lf, const MGLevel &Lc)
+{
+    constexpr bool f64 = std::is_same<TF, double>::value && std::is_same<TK, double>::value;
+    if (mg_border(Lf, Lc) && !std::is_same<TK, double>::value) return fail(h, KSFD_EINVAL, "multigrid: a replicated level has fp64 vectors");
+    if (!f64 && Lf.G.dim != 2) return fail(h, KSFD_EINVAL, "multigrid: fp32 level vectors exist in 2-D only");
+    if (mg_border(Lf, Lc) && Lf.G.dim == 1) return fail(h, KSFD_EINVAL, "multigrid: no replicated levels on a 1-D grid");
+    return KSFD_OK;
+}
 template <typename TF, typename TK>
 static int mg_launch_restrict(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TF *fine, TK *coarse)
 {
     constexpr bool f64 = std::is_same<TF, double>::value && std::is_same<TK, double>::value;
-    const int nb = point_blocks(Lc.G), dim = f64 ? Lf.G.dim : 2;
-    if (mg_border(Lf, Lc)) {
-        if constexpr (std::is_same<TK, double>::value) {
-            const long long u0c = (long long)h->rank * (Lf.G.sloc / 2);       // first coarse slow unit of this rank's slice
-            if (Lf.G.dim == 2)
-                hipLaunchKernelGGL((k_restrict2d_border<TF>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, u0c, Lc.G.sloc,
-                                   fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane);
-            else if constexpr (f64) {
-                if (Lf.G.dim != 3) return fail(h, KSFD_EINVAL, "multigrid: no replicated levels on a 1-D grid");
-                hipLaunchKernelGGL(k_restrict3d_border, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, u0c, Lc.G.sloc,
-                                   fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane);
-            } else return fail(h, KSFD_EINVAL, "multigrid: fp32 level vectors exist in 2-D only");
-            HIPCHK(h, hipGetLastError());
-            return KSFD_OK;
-        } else return fail(h, KSFD_EINVAL, "multigrid: a replicated level has fp64 vectors");
-    }
+    if (int rc = mg_transfer_refused<TF, TK>(h, Lf, Lc)) return rc;
+    const KMGSlow Z = mg_slow(h, Lf, Lc, true);
+    auto launch = [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(point_blocks(Lc.G)), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Z,
+                               fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+        };
+        if constexpr (D > 1 && std::is_same<TK, double>::value) if (mg_border(Lf, Lc)) return go(k_mg_restrict<D, true, TF, TK>);
+        go(k_mg_restrict<D, false, TF, TK>);
+    };
+    if (Lf.G.dim == 2) launch(std::integral_constant<int, 2>());
     if constexpr (f64) {
-        if (dim == 1)
-            hipLaunchKernelGGL(k_restrict1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
-                               fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
-        if (dim == 3)
-            hipLaunchKernelGGL(k_restrict3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
-                               fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
+        if (Lf.G.dim == 1) launch(std::integral_constant<int, 1>());
+        if (Lf.G.dim == 3) launch(std::integral_constant<int, 3>());
     }
-    if (dim == 2)
-        hipLaunchKernelGGL((k_restrict2d<TF, TK>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
-                           fine, Lf.G.plane, Lf.kv.off, coarse, Lc.G.plane, Lc.kv.off);
     return KSFD_OK;
 }
 template <typename TK, typename TF>
 static int mg_launch_prolong(ksfd_handle *h, MGLevel &Lf, MGLevel &Lc, int np, const TK *coarse, TF *fine)
 {
     constexpr bool f64 = std::is_same<TF, double>::value && std::is_same<TK, double>::value;
-    const int nb = point_blocks(Lf.G), dim = f64 ? Lf.G.dim : 2;
-    if (mg_border(Lf, Lc)) {
-        if constexpr (std::is_same<TK, double>::value) {
-            const long long u0f = (long long)h->rank * Lf.G.sloc;             // first fine slow unit of this rank's slab
-            if (Lf.G.dim == 2)
-                hipLaunchKernelGGL((k_prolong_add2d_border<TF>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, u0f, Lc.G.sloc,
-                                   coarse, Lc.G.plane, fine, Lf.G.plane, Lf.kv.off);
-            else if constexpr (f64) {
-                if (Lf.G.dim != 3) return fail(h, KSFD_EINVAL, "multigrid: no replicated levels on a 1-D grid");
-                hipLaunchKernelGGL(k_prolong_add3d_border, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, u0f, Lc.G.sloc,
-                                   coarse, Lc.G.plane, fine, Lf.G.plane, Lf.kv.off);
-            } else return fail(h, KSFD_EINVAL, "multigrid: fp32 level vectors exist in 2-D only");
-            return KSFD_OK;
-        } else return fail(h, KSFD_EINVAL, "multigrid: a replicated level has fp64 vectors");
-    }
+    if (int rc = mg_transfer_refused<TF, TK>(h, Lf, Lc)) return rc;
+    const KMGSlow Z = mg_slow(h, Lf, Lc, false);
+    auto launch = [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(point_blocks(Lf.G)), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Z,
+                               coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
+        };
+        if constexpr (D > 1 && std::is_same<TK, double>::value) if (mg_border(Lf, Lc)) return go(k_mg_prolong_add<D, true, TK, TF>);
+        go(k_mg_prolong_add<D, false, TK, TF>);
+    };
+    if (Lf.G.dim == 2) launch(std::integral_constant<int, 2>());
     if constexpr (f64) {
-        if (dim == 1)
-            hipLaunchKernelGGL(k_prolong_add1d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.sloc, Lf.G.wrap_slow,
-                               coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
-        if (dim == 3)
-            hipLaunchKernelGGL(k_prolong_add3d, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.ny, Lf.G.sloc, Lf.G.wrap_slow,
-                               coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
+        if (Lf.G.dim == 1) launch(std::integral_constant<int, 1>());
+        if (Lf.G.dim == 3) launch(std::integral_constant<int, 3>());
     }
-    if (dim == 2)
-        hipLaunchKernelGGL((k_prolong_add2d<TK, TF>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, np, Lf.G.nx, Lf.G.sloc, Lf.G.wrap_slow,
-                           coarse, Lc.G.plane, Lc.kv.off, fine, Lf.G.plane, Lf.kv.off);
     return KSFD_OK;
 }
 
@@ -372,6 +351,21 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
     return KSFD_OK;
 }
 
+// Chebyshev iteration on the eigen-interval [lam_max/ratio, lam_max] in the "direction" form: d_0 = Dinv r_0 / theta, then
+// d_{k+1} = c1 d_k + c2 Dinv r with c1 = rho_{k+1} rho_k, c2 = 2 rho_{k+1} / delta, rho_0 = 1/sig1, rho_{k+1} = 1/(2 sig1 - rho_k)
+struct MGCheb {
+    double theta, delta, sig1, rho0, rhon;                      // rhon = rho_1
+    double next(double rho) const { return 1.0 / (2.0 * sig1 - rho); }
+};
+static inline MGCheb mg_cheb(double lam_max, double ratio)
+{
+    const double lmax = lam_max, lmin = lmax / ratio;
+    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
+    MGCheb C = { theta, delta, sig1, 1.0 / sig1, 0.0 };
+    C.rhon = C.next(C.rho0);
+    return C;
+}
+
 // The V(2,2) smoother pair with the algebra in the Jacobian-action epilogues (modes 5 and 6, KSmoothT), level vectors stored in T: 2 launches
 // instead of 3 (zero guess) or 4 (correction), and the residual / A d round trips through memory disappear.
 //   zero guess:  d0 = Dinv b / theta, then x = d0 + d1 in the epilogue of A d0 (mode 6)
@@ -384,18 +378,16 @@ static int mg_smooth_fused(ksfd_handle *h, MGLevel &L, double shift, const T *b,
     int rc;
     const int F = L.G.F;
     MGVecs<T> &V = L.vecs<T>();
-    const double lmax = L.lam_max, lmin = lmax / ratio;
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
-    const double rho0 = 1.0 / sig1, rhon = 1.0 / (2.0 * sig1 - rho0);
+    const MGCheb C = mg_cheb(L.lam_max, ratio);
     KSmoothT<T> S = KSmoothT<T>{};
-    S.dinv = L.dinv; S.x = x; S.c1 = rhon * rho0; S.c2 = 2.0 * rhon / delta;
+    S.dinv = L.dinv; S.x = x; S.c1 = C.rhon * C.rho0; S.c2 = 2.0 * C.rhon / C.delta;
     if (zero_init) {
         const double by = ((b64 ? 8.0 + sizeof(T) : sizeof(T)) * F + sizeof(T) * F + 4.0 * F * F) * (double)L.G.nloc;
-        if (b64) mg_dinv_apply(h, L, by, b64, 1.0 / theta, V.d, (T *)nullptr, const_cast<T *>(b));
-        else mg_dinv_apply(h, L, by, b, 1.0 / theta, V.d);
+        if (b64) mg_dinv_apply(h, L, by, b64, 1.0 / C.theta, V.d, (T *)nullptr, const_cast<T *>(b));
+        else mg_dinv_apply(h, L, by, b, 1.0 / C.theta, V.d);
         S.rr = b; S.x_has_d = 1;
     } else {
-        S.out2 = V.d; S.scale = 1.0 / theta;
+        S.out2 = V.d; S.scale = 1.0 / C.theta;
         if ((rc = mg_op<T>(h, L, x, 5, shift, V.r, b, &S))) return rc;
         S.rr = V.r; S.x_has_d = 0;
     }
@@ -413,8 +405,7 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
     int rc;
     const int F = L.G.F;
     const int nb = point_blocks(L.G);
-    const double lmax = L.lam_max, lmin = lmax / ratio;
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig1 = theta / delta;
+    const MGCheb C = mg_cheb(L.lam_max, ratio);
     const long long off = L.kv.off;     // owned rows start here inside a (ghosted) plane
     double *const r = L.v64.r, *const d = L.v64.d;
     const double *res = b;
@@ -422,16 +413,16 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
         if ((rc = mg_op(h, L, x, 2, shift, r, b))) return rc;        // r = b - A x
         res = r;
     }
-    mg_dinv_apply(h, L, 8.0 * ((zero_init ? 3 : 2) * F + 0.5 * F * F) * L.G.nloc, res, 1.0 / theta, d, zero_init ? x : (double *)nullptr);
+    mg_dinv_apply(h, L, 8.0 * ((zero_init ? 3 : 2) * F + 0.5 * F * F) * L.G.nloc, res, 1.0 / C.theta, d, zero_init ? x : (double *)nullptr);
     bool x_has_d = zero_init;          // x == d_0 already
-    double rho = 1.0 / sig1;
+    double rho = C.rho0;
     for (int k = 1; k < nu; k++) {
         if ((rc = mg_op<double>(h, L, d, 1, shift, L.Ad, nullptr))) return rc;
-        const double rhon = 1.0 / (2.0 * sig1 - rho);
+        const double rhon = C.next(rho);
         const double *rsrc = (zero_init && k == 1) ? b : r;             // first sweep from a zero guess: r_0 = b, never copied
         if (k == nu - 1) {
             Scope sc(h, KC_MG, 8.0 * (5 * F + 0.5 * F * F) * L.G.nloc);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_last<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, rsrc + off, (const double *)(d + off), (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / delta, x_has_d ? 1 : 0));
+            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_last<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, rsrc + off, (const double *)(d + off), (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / C.delta, x_has_d ? 1 : 0));
             x_has_d = true;
         } else {
             if (rsrc != r) HIPCHK(h, hipMemcpyAsync(r, b, sizeof(double) * (size_t)L.vlen, hipMemcpyDeviceToDevice, h->st));
@@ -439,7 +430,7 @@ static int mg_smooth(ksfd_handle *h, MGLevel &L, double shift, const double *b, 
                 HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)L.vlen, h->st));
             }
             Scope sc(h, KC_MG, 8.0 * (7 * F + 0.5 * F * F) * L.G.nloc);
-            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_step<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, r + off, d + off, (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / delta));
+            NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_cheb_step<NL>), dim3(nb), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), x + off, r + off, d + off, (const double *)(L.Ad + off), rhon * rho, 2.0 * rhon / C.delta));
             x_has_d = false;
         }
         rho = rhon;

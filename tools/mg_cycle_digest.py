@@ -9,7 +9,11 @@ library per process) and diff.  Items, all on seeded inputs at the state of test
   smooth   MGP_SMOOTH nu = 2 (zero guess, nonzero guess) and nu = 3 on levels 0 and 1 of 32x32
   operator MGP_OPERATOR variants 2 and 32 on level 1 of 64x48
   steps    the state after 3 multigrid-preconditioned steps on 64x64 at ksp_rtol 1e-5 (fp32 cycle) and 1e-11 (fp64 cycle), and with each
-           the launches, bytes and algorithmic bytes of every kernel class (ksfd_get_profile)"""
+           the launches, bytes and algorithmic bytes of every kernel class (ksfd_get_profile)
+  transfer MGP_RESTRICT (variants 0, 1, 2) and MGP_PROLONG_ADD (0, 1) on every level of 32x32, 64x48, 16x16x16 and 96, in every variant the
+           level admits; the same on a ring of one rank (host transport) with set_mg_agglomerate(300) on 64x64 and (5000) on 32x32x32:
+           the transfers across the border to the replicated levels in one process (rank offset 0; the offsets of further ranks need
+           more than one rank: tests/test_gpu_mg_agglomerate.py::test_transfers)"""
 import hashlib
 import os
 import sys
@@ -29,10 +33,14 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
 
 
-def handle(shape, nlig):
+def handle(shape, nlig, ring=False):
     cfg = ProblemConfig.standard(len(shape), shape, L=tuple((0.01 if len(shape) == 3 else 0.0025) * n for n in shape), nlig=nlig)
     rho = 9000.0 * (1.0 + 0.05 * np.random.default_rng(3).standard_normal(cfg.N))
-    k = klib.KSFDHip(cfg)
+    if ring:
+        from ksfd_amd.dist import open_self_ring
+        k, k.keep = open_self_ring(cfg, 0, 'host')
+    else:
+        k = klib.KSFDHip(cfg)
     k.set_state(np.concatenate([rho] + [rho * cfg.lig_s[l] / cfg.lig_gamma[l] for l in range(cfg.nlig)]))
     return cfg, k
 
@@ -85,6 +93,20 @@ def steps(ksp_rtol):
     k.close()
 
 
+def transfers(name, shape, nlig, agglomerate=0):
+    cfg, k = handle(shape, nlig, ring=agglomerate > 0)
+    if agglomerate:
+        k.set_mg_agglomerate(agglomerate)
+    info = [k.mg_level_info(l) for l in range(k.mg_level_info(0)['nlevels'])]
+    for l, (fine, coarse) in enumerate(zip(info, info[1:])):
+        v, w = vec(k, l, 51 + l), vec(k, l + 1, 61 + l)
+        for variant in [0] + [1] * fine['f32'] + [2] * (len(shape) == 2 and coarse['f32']):
+            print('transfer %s level %d restrict variant %d %s' % (name, l, variant, sha(k.mg_part(klib.MGP_RESTRICT, l, v, variant=variant))))
+        for variant in [0] + [1] * fine['f32']:
+            print('transfer %s level %d prolong variant %d %s' % (name, l, variant, sha(k.mg_part(klib.MGP_PROLONG_ADD, l, v, w, variant=variant))))
+    k.close()
+
+
 def main():
     if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
         sys.exit(__doc__)
@@ -96,6 +118,10 @@ def main():
     smoother_and_operator()
     for ksp_rtol in (1e-5, 1e-11):
         steps(ksp_rtol)
+    for name, shape, nlig in (('32x32', (32, 32), 1), ('64x48', (64, 48), 2), ('16x16x16', (16, 16, 16), 1), ('96', (96,), 1)):
+        transfers(name, shape, nlig)
+    transfers('64x64 ring of one, agglomerate 300', (64, 64), 1, 300)
+    transfers('32x32x32 ring of one, agglomerate 5000', (32, 32, 32), 1, 5000)
 
 
 if __name__ == '__main__':
