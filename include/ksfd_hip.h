@@ -190,7 +190,9 @@ int ksfd_set_state_random(ksfd_handle *h, const int64_t nc[3], const double *z_c
  * preconditioner adaptation): op 0 = save, op 1 = restore.  One slot, allocated on first use.  Used by bench.py to time a
  * pinned window of steps repeatedly and by callers that want to retry from a known state without a host round trip. */
 int ksfd_checkpoint(ksfd_handle *h, int32_t op);
-double *ksfd_device_state(ksfd_handle *h);      /* device pointer, SoA with ghost rows; plane stride below */
+/* device pointer, SoA with ghost rows; plane stride below.  Good until the next ksfd_step: an accepted step leaves the new state in the
+ * handle's other buffer (the completion is out of place), so ask again after every step */
+double *ksfd_device_state(ksfd_handle *h);
 int64_t ksfd_device_plane_stride(const ksfd_handle *h);
 int64_t ksfd_device_interior_offset(const ksfd_handle *h);
 
@@ -227,7 +229,10 @@ int ksfd_jacobian_csr(ksfd_handle *h, int64_t *rowptr /* nrows+1 */, int64_t *co
  *    in: *t, *hstep (step to try).  out: *t advanced when accepted, *hstep = next proposed step. */
 void ksfd_default_step_opts(ksfd_step_opts *o);
 int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_step_opts *opts, ksfd_step_stats *stats);
-int ksfd_get_last_error_vector(ksfd_handle *h, double *err_host, int32_t layout); /* embedded-minus-main of last attempt */
+/* embedded-minus-main of the last completed attempt, accepted or rejected.  Formed on this call from the stage vectors of that attempt,
+ * which stay in place until the stage solves of the next attempt begin; a ksfd_step that fails before it completes an attempt (a stage
+ * solve that returns an error) therefore leaves no vector, and the call fails with KSFD_EINVAL until an attempt completes again */
+int ksfd_get_last_error_vector(ksfd_handle *h, double *err_host, int32_t layout);
 
 /* -- measurement
  * on: 0 off; 1 HIP-event pair around every launch (costs ~8 us of device time per launch); 2+c events only around
@@ -262,6 +267,12 @@ int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, double *avg_ms,
  * bit20 set = multigrid-preconditioned stage solves keep the whole first GMRES cycle of every stage and project the later stages of the step
  * on it first (experiment, measured slower: krylov.hip.h);
  * bit19 set = the V cycle keeps its level vectors in fp64 at every tolerance (default: fp32 level vectors when ksp_rtol >= 1e-7, 2-D);
+ * bit22 set = the step boundary as it was before the passes nobody reads were taken out: groom at the head of every step (default: only
+ * when a value can be under its floor), the embedded error vector stored by every completion (default: formed from the stage vectors
+ * when ksfd_get_last_error_vector asks), the fp32 coefficient copy stored with the fp64 planes (default: converted when the polynomial
+ * preconditioner or the V cycle first reads it).  Same results bit for bit; for tests and A/B timing;
+ * bit23 set = the first stage's right-hand side evaluates G(u) itself (default, 2-D strip path: it loads G from the coefficient planes
+ * the step has just made of the same state, which may differ from its own evaluation in the last bit);
  * yseg_*: rows per wave segment; <=0 keeps */
 int ksfd_set_tuning(ksfd_handle *h, int32_t use_fused, int32_t yseg_rhs, int32_t yseg_jvp);
 /* multigrid knobs (<=0 keeps): smoothing sweeps per side, cap on coarsest-grid sweeps, power iterations for the

@@ -133,6 +133,8 @@ struct ksfd_handle {
     int64_t vlen = 0;
     double *u = nullptr, *usave = nullptr, *Z = nullptr, *bvec = nullptr, *Y = nullptr, *V = nullptr;
     double *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *errv = nullptr;
+    // u and usave trade places at every accepted step (step_run): the completion writes the new state into usave.  Nothing may keep
+    // either pointer across a step
     double *ckpt = nullptr;                 // ksfd_checkpoint slot (allocated on first save)
     double *bstore = nullptr;               // right-hand sides of stages 0..2 of the current step (initial guesses of the spectral solves)
     bool spec_guess = true;
@@ -152,7 +154,15 @@ struct ksfd_handle {
     double *Gb = nullptr, *dGb = nullptr;   // generic-path scratch planes
     double *coef = nullptr;                 // frozen-Jacobian coefficient planes [rho, G, G_rho, G_U..]
     bool use_frozen = true;
-    bool coef_fresh = false;                // coef (and coef32) belong to the resident state u as it is now (ensure_coef)
+    bool coef_fresh = false;                // coef belongs to the resident state u as it is now (ensure_coef)
+    bool coef32_fresh = false;              // coef32 is the rounded copy of coef as it is now (ensure_coef32; cleared by whatever writes coef)
+    bool floor_ok = false;                  // every owned value of u is at or above its floor (rhomin / Umin): k_groom would store what it loads.
+                                            // True after a groom and after an accepted completion that counted no value below; false after everything
+                                            // else that writes u or moves the floors
+    bool ckpt_floor_ok = false;             // ... of the state in the checkpoint slot
+    bool err_pending = false;               // errv has not been formed yet: it is sum (b2t_j - bt_j) Y_j of the stage vectors still in Y (err_materialize)
+    bool old_boundary = false;              // KSFD_TUNE bit 22: groom every step, error vector stored by the completion, fp32 coefficient copy made by k_jcoef
+    bool rhs_gplane = true;                 // stage-0 RHS of the 2-D strip path takes G from plane 1 of coef (KSFD_TUNE bit 23 clears)
     double *flat = nullptr;                 // staging for host layouts: max(F,dim)*nloc
     double *src[4][KSFD_MAXL + 1];          // dense source planes per stage (lazy)
     double *part = nullptr;                 // block partials

@@ -52,6 +52,7 @@ static int poly_apply(ksfd_handle *h, double shift, double *v, double *z)
     int rc;
     const int d = h->poly_deg;
     const double *al = h->poly_alpha;
+    if ((rc = ensure_coef32(h))) return rc;                  // first application since the planes were made: the fp32 copy is formed here
     if (h->poly_fp32 && h->coef32 && fused_ok(h)) {
         // mixed precision: the Horner temporaries and the coefficient planes live in fp32 (half the traffic of every
         // application but the arithmetic stays fp64); v is read and z written in fp64.  p(A) becomes a slightly

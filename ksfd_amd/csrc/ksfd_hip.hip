@@ -238,6 +238,7 @@ extern "C" int ksfd_update_params(ksfd_handle *h, const ksfd_config *cfg)
     h->cfg.lig_group = nullptr; h->cfg.lig_w = h->cfg.lig_s = h->cfg.lig_gamma = h->cfg.lig_D = nullptr;
     h->cfg.grp_alpha = h->cfg.grp_beta = nullptr;
     h->coef_fresh = false;                                   // G, G_rho, G_U depend on the parameters
+    h->floor_ok = h->ckpt_floor_ok = false;                  // rhomin / Umin may have moved: under the state and under the one in the checkpoint slot
     return fill_phys(h, cfg);
 }
 
@@ -267,7 +268,9 @@ extern "C" int ksfd_local_range(const ksfd_handle *h, int64_t *b, int64_t *e)
     return KSFD_OK;
 }
 extern "C" int64_t ksfd_local_size(const ksfd_handle *h) { return h ? (int64_t)h->G.F * h->G.nloc : 0; }
-extern "C" double *ksfd_device_state(ksfd_handle *h) { return h ? h->u : nullptr; }
+// the pointer is good until the next ksfd_step (an accepted step moves the state to the handle's other buffer); handing it out ends what
+// the handle knows about the values it points at
+extern "C" double *ksfd_device_state(ksfd_handle *h) { if (h) h->floor_ok = false; return h ? h->u : nullptr; }
 extern "C" int64_t ksfd_device_plane_stride(const ksfd_handle *h) { return h ? h->G.plane : 0; }
 extern "C" int64_t ksfd_device_interior_offset(const ksfd_handle *h) { return h ? (int64_t)h->G.ng * h->G.inner : 0; }
 
@@ -277,6 +280,7 @@ extern "C" int ksfd_set_state(ksfd_handle *h, const double *u, int32_t layout)
     hipSetDevice(h->device);
     int rc = upload(h, u, layout, h->u);
     h->coef_fresh = false;
+    h->floor_ok = false;
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->st));
     return KSFD_OK;
@@ -339,6 +343,7 @@ extern "C" int ksfd_checkpoint(ksfd_handle *h, int32_t op)
         if (!h->ckpt && alloc_d(h, &h->ckpt, h->vlen)) return KSFD_ENOMEM;
         HIPCHK(h, hipMemcpyAsync(h->ckpt, h->u, sizeof(double) * (size_t)h->vlen, hipMemcpyDeviceToDevice, h->st));
         h->ckpt_memo = h->memo;
+        h->ckpt_floor_ok = h->floor_ok;                  // a property of the state being copied
         for (MGLevel &L : h->mg) L.pv_norm = 0.0;       // the step after a save and the step after a restore both set the hierarchy up cold
         h->ckpt_valid = true;
         return KSFD_OK;
@@ -346,9 +351,10 @@ extern "C" int ksfd_checkpoint(ksfd_handle *h, int32_t op)
     if (!h->ckpt_valid) return fail(h, KSFD_EINVAL, "no checkpoint has been saved");
     HIPCHK(h, hipMemcpyAsync(h->u, h->ckpt, sizeof(double) * (size_t)h->vlen, hipMemcpyDeviceToDevice, h->st));
     h->coef_fresh = false;
+    h->floor_ok = h->ckpt_floor_ok;
     h->memo = h->ckpt_memo;
     h->spec.means_valid = false;
-    h->mg_coef_valid = false; h->mg_shift = -1.0; h->poly_shift = -1.0; h->have_err = false;
+    h->mg_coef_valid = false; h->mg_shift = -1.0; h->poly_shift = -1.0; h->have_err = false; h->err_pending = false;
     for (MGLevel &L : h->mg) L.pv_norm = 0.0;
     rec_reset(h);
     return KSFD_OK;
@@ -365,6 +371,7 @@ extern "C" int ksfd_set_state_random(ksfd_handle *h, const int64_t *nc, const do
     }
     double *dz = nullptr;
     h->coef_fresh = false;
+    h->floor_ok = false;
     if (hipMalloc((void **)&dz, sizeof(double) * (size_t)n) != hipSuccess) return fail(h, KSFD_ENOMEM, "hipMalloc of the coarse samples failed");
     hipError_t e = hipMemcpyAsync(dz, z, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->st);
     const KGeom &G = h->G;
@@ -505,6 +512,7 @@ extern "C" int ksfd_groom(ksfd_handle *h)
     Scope sc(h, KC_MISC, vbytes(h, 2));
     hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin);
     HIPCHK(h, hipGetLastError());
+    h->floor_ok = true;
     return KSFD_OK;
 }
 
@@ -528,6 +536,7 @@ extern "C" int ksfd_scale_rho(ksfd_handle *h, double factor)
     if (!h) return KSFD_EINVAL;
     hipSetDevice(h->device);
     h->coef_fresh = false;
+    h->floor_ok = false;
     Scope sc(h, KC_MISC, 16.0 * (double)h->G.nloc);
     hipLaunchKernelGGL(k_mul_rho, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, (const double *)nullptr, factor);
     HIPCHK(h, hipGetLastError());
@@ -540,6 +549,7 @@ extern "C" int ksfd_mul_rho(ksfd_handle *h, const double *fh)
     hipSetDevice(h->device);
     HIPCHK(h, hipMemcpyAsync(h->flat, fh, sizeof(double) * (size_t)h->G.nloc, hipMemcpyHostToDevice, h->st));
     h->coef_fresh = false;
+    h->floor_ok = false;
     Scope sc(h, KC_MISC, 24.0 * (double)h->G.nloc);
     hipLaunchKernelGGL(k_mul_rho, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, (const double *)h->flat, 1.0);
     HIPCHK(h, hipGetLastError());
@@ -614,8 +624,9 @@ extern "C" void ksfd_default_step_opts(ksfd_step_opts *o)
 }
 
 // One TSStep_RosW attempt loop (PETSc rosw.c restated; tableau/derivation in oracle/ksfd_oracle.c) over the parts in step.hip.h.
-// Grooms and saves the state, then tries step sizes until the controller accepts one: plan, four stages, the solvers' own adaptation,
-// completion with the embedded error norm, TSAdaptChoose_Basic.  Every rejection rolls the state back from usave.
+// Grooms the state where that can change it, then tries step sizes until the controller accepts one: plan, four stages, the solvers' own
+// adaptation, completion with the embedded error norm, TSAdaptChoose_Basic.  The stages only read h->u and the completion writes the new
+// state into h->usave, so an attempt that fails or is rejected has nothing to roll back; acceptance swaps the two pointers.
 static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_opts *opts, bool direct, bool dr_on, ksfd_step_stats &st)
 {
     int rc;
@@ -627,11 +638,13 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
     const int max_rej = opts->max_reject < 0 ? 0x7fffffff : opts->max_reject;      // PETSc: -ts_max_reject -1 = unlimited
     const bool single = (opts->reserved & 2) != 0;                                   // one attempt per call (the caller owns the reject loop)
     // KSFDTS.solve grooms the global vector before every TS.step (KSFD/ksfdts.py:210)
-    {
-        // groom + roll-back copy of the owned points in one pass (ghost units of usave are never used: every roll-back is followed by a halo exchange)
-        Scope sc(h, KC_MISC, vbytes(h, 3));
-        hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin, h->usave);
+    // floor_ok: every owned value is at or above its floor already (the last completion counted none below and nothing has written u or
+    // moved the floors since), so the groom would store the bits it loads and is left out
+    if (!h->floor_ok || h->old_boundary) {
+        Scope sc(h, KC_MISC, vbytes(h, 2));
+        hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin);
         if (hipGetLastError() != hipSuccess) return fail(h, KSFD_EHIP, "k_groom launch failed");
+        h->floor_ok = true;
     }
     if ((rc = halo(h, h->u))) return rc;
     if (h->use_frozen && (rc = ensure_coef(h, true))) return rc;      // usually already there: the CFL check after the last step made them
@@ -643,6 +656,9 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
         if ((rc = plan_attempt(h, opts, hh, direct, dr_on, lam_done, p))) return rc;
         const int its_before = st.linear_its;
         bool spec_failed = false;
+        // the stage solves overwrite Y: an error vector nobody has asked for goes with it, and the query has nothing to return until the
+        // next completion (it fails instead of returning the vector of an older attempt)
+        if (h->err_pending) { h->err_pending = false; h->have_err = false; }
         rc = step_attempt(h, opts, p, spec_failed, st);
         const int its = st.linear_its - its_before;
         if (p.use_spec && opts->pc_type == 2) ksfd_ctl::spec_backoff_update(m, spec_failed, its, m.nsteps);
@@ -654,23 +670,24 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
             rejects++;
             st.rejections = rejects;
             prev_accept = false;
-            if ((rc = op_copy(h, h->u, h->usave))) return rc;
             hh *= 0.25;
             *hstep = hh;
-            if ((rc = halo(h, h->u))) return rc;
             continue;
         }
-        if (rc) { op_copy(h, h->u, h->usave); hipStreamSynchronize(h->st); return rc; }
-        if ((rc = step_finish(h, opts, &st.wrms))) return rc;
+        if (rc) { hipStreamSynchronize(h->st); return rc; }
+        double below = 0.0;
+        if ((rc = step_finish(h, opts, &st.wrms, &below))) return rc;
         if (!(st.wrms == st.wrms) || isinf(st.wrms)) {
-            op_copy(h, h->u, h->usave); hipStreamSynchronize(h->st);
-            h->coef_fresh = h->use_frozen;
+            hipStreamSynchronize(h->st);
             return fail(h, KSFD_ENAN, "non-finite error norm at t=%g h=%g", *t, hh);
         }
         ksfd_ctl::AdaptChoice next = { true, hh };
         if (opts->adapt) next = ksfd_ctl::adapt_basic(hh, st.wrms, prev_accept, opts->safety, opts->reject_safety, opts->clip_lo, opts->clip_hi, opts->dt_min, opts->dt_max);
         prev_accept = next.accept;
         if (next.accept) {
+            std::swap(h->u, h->usave);                               // the new state; its ghost rows are stale until the next halo exchange
+            h->coef_fresh = false;
+            h->floor_ok = below == 0.0;
             st.accepted = 1; st.h_used = hh;
             *t += hh;
             *hstep = next.hnext;
@@ -678,13 +695,10 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
         }
         rejects++;
         st.rejections = rejects;
-        if ((rc = op_copy(h, h->u, h->usave))) return rc;
-        h->coef_fresh = h->use_frozen;                           // the planes were made from exactly this state
-        hh = next.hnext;
+        hh = next.hnext;                                         // h->u, its ghost rows and the coefficient planes made of it are untouched
         *hstep = next.hnext;
         if (single) return KSFD_OK;                              // single attempt: report the rejection
         if (rejects > max_rej) return fail(h, KSFD_EREJECT, "step rejected %d times at t=%g", rejects, *t);
-        if ((rc = halo(h, h->u))) return rc;
     }
 }
 
@@ -724,6 +738,8 @@ extern "C" int ksfd_get_last_error_vector(ksfd_handle *h, double *eh, int32_t la
     if (!h || !eh) return KSFD_EINVAL;
     if (!h->have_err) return fail(h, KSFD_EINVAL, "no step has been attempted yet");
     hipSetDevice(h->device);
+    int rc = err_materialize(h);
+    if (rc) return rc;
     return download(h, h->errv, layout, eh);
 }
 
@@ -902,7 +918,7 @@ static int mgp_get(ksfd_handle *h, const MGLevel &L, int np, const T *dev, doubl
 static int mgp_begin(ksfd_handle *h, bool setup, double shift)
 {
     int rc;
-    if ((rc = ensure_coef(h))) return rc;
+    if ((rc = ensure_coef(h)) || (rc = ensure_coef32(h))) return rc;      // level 0 reads the fp32 copy of the planes where the handle has one (mg_sys)
     if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
     if (setup) {
         for (MGLevel &L : h->mg) L.pv_norm = 0.0;
@@ -1263,6 +1279,8 @@ extern "C" int ksfd_set_tuning(ksfd_handle *h, int32_t use_fused, int32_t yseg, 
         h->mg_fp32 = !(use_fused & 524288);
         h->rec_mg = (use_fused & 1048576) != 0;
         h->rhs_dots = !(use_fused & 2097152);
+        h->old_boundary = (use_fused & 4194304) != 0;
+        h->rhs_gplane = !(use_fused & 8388608);
         if (h->mg_fuse != !(use_fused & 4096)) { h->mg_fuse = !(use_fused & 4096); h->mg_shift = -1.0; if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; } }
     }
     if (yseg > 0) h->yseg = yseg;

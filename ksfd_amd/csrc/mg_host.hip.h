@@ -13,7 +13,7 @@ static inline size_t mg_end(const ksfd_handle *h) { return h->mgc.kind == 1 ? (s
 static inline bool mg_f32(const ksfd_handle *h, size_t l) { return h->mg[l].f32 && !(h->mgc.kind == 1 && l == (size_t)h->mgc.level); }
 
 // The frozen Jacobian action on level L (ops.hip.h: JvpSys, jvp_path).  Level 0 is the handle's grid: booked as its Jacobian actions are,
-// and its fp32 coefficient copy is the handle's.  The levels have no launch of the second-generation 3-D kernel: the strip kernel serves
+// and its fp32 coefficient copy is the handle's (made on demand: ensure_coef32 before the first launch).  The levels have no launch of the second-generation 3-D kernel: the strip kernel serves
 static JvpSys mg_sys(const ksfd_handle *h, const MGLevel &L)
 {
     const bool l0 = &L == &h->mg[0];
@@ -569,6 +569,7 @@ static bool mg_cycle32_ok(const ksfd_handle *h) { return h->mg_fp32 && h->mg[0].
 static int mg_precond(ksfd_handle *h, double shift, const double *in, double *out)
 {
     int rc;
+    if ((rc = ensure_coef32(h))) return rc;                  // level 0 reads the fp32 copy of the planes (mg_sys)
     if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
     if (h->mg_shift != shift && (rc = mg_setup_shift(h, shift))) return rc;
     MGVecs<float> &V = h->mg[0].v32;

@@ -300,9 +300,13 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         // the vectors added at the store are the ones the stage argument is formed from: one read serves both (k_rhs2d_fused<NL, true>)
         bool carry = h->rhs_carry && C.nout > 0 && C.nout == C.nin;
         for (int j = 0; j < C.nout && carry; j++) carry = C.yin[j] == C.yout[j];
+        // first stage of a step: the argument is the resident state itself and G(u) is plane 1 of the frozen coefficients the step has
+        // just made of it (same parameters, same clamped inputs): loaded, not evaluated (the rule of the 3-D path below)
+        const bool reuse_G = h->rhs_gplane && C.nin == 0 && C.nout == 0 && u == h->u && h->coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
         auto launch = [&](const KStrips &Kx, double frac, double *np) -> int {
-            Scope sc(h, KC_RHS, vbytes(h, 2 + C.nin + (carry ? 0 : C.nout) + D.n) * frac, vbytes(h, 2 + C.nin + C.nout + D.n) * frac);
-            if (carry) { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL, true>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D)); }
+            Scope sc(h, KC_RHS, (vbytes(h, 2 + C.nin + (carry ? 0 : C.nout) + D.n) + (reuse_G ? 8.0 * (double)G.nloc : 0.0)) * frac, vbytes(h, 2 + C.nin + C.nout + D.n) * frac);
+            if (reuse_G) { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL, false, true>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D, (const double *)(h->coef + G.plane))); }
+            else if (carry) { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL, true>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D)); }
             else { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D)); }
             return KSFD_OK;
         };
@@ -369,15 +373,25 @@ static int op_jvp(ksfd_handle *h, const double *u, const double *v, int mode, do
     return KSFD_OK;
 }
 
+// The buffer of the fp32 coefficient copy, allocated when first wanted (2-D strip path only).  false: no copy on this handle (poly_fp32
+// off, another kernel path, or no memory, which switches poly_fp32 off)
+static bool coef32_alloc(ksfd_handle *h)
+{
+    const KGeom &G = h->G;
+    if (!h->coef32 && h->poly_fp32 && fused_ok(h) && h->P.nlig <= 4 && G.plane % 2 == 0 && G.inner % 2 == 0 &&
+        hipMalloc((void **)&h->coef32, sizeof(float) * (size_t)(3 + h->P.nlig) * G.plane) != hipSuccess) { h->coef32 = nullptr; h->poly_fp32 = false; (void)hipGetLastError(); }
+    return h->poly_fp32 && h->coef32;
+}
+
 // Once per step: C = [rho, G, G_rho, G_U..] of the (ghost-filled) state u
 // want_means: the grid means of the spectral preconditioner come out of the same launch (resident state only)
 static int op_jcoef(ksfd_handle *h, const double *u, bool want_means = false)
 {
     const KGeom &G = h->G;
     const int nbp = plane_blocks(G);
-    if (!h->coef32 && h->poly_fp32 && fused_ok(h) && h->P.nlig <= 4 && G.plane % 2 == 0 && G.inner % 2 == 0 &&
-        hipMalloc((void **)&h->coef32, sizeof(float) * (size_t)(3 + h->P.nlig) * G.plane) != hipSuccess) { h->coef32 = nullptr; h->poly_fp32 = false; }
-    float *c32 = h->poly_fp32 ? h->coef32 : nullptr;
+    // the fp32 copy is made when a consumer asks for it (ensure_coef32); only the old step boundary has k_jcoef store it
+    float *c32 = h->old_boundary && coef32_alloc(h) ? h->coef32 : nullptr;
+    h->coef32_fresh = c32 != nullptr;
     want_means = want_means && (long long)(1 + h->P.nlig) * nbp <= part_capacity();
     {
     Scope sc(h, KC_GFIELD, (8.0 * (G.F + 3 + h->P.nlig) + (c32 ? 4.0 * (3 + h->P.nlig) : 0.0)) * (double)G.plane);
@@ -406,6 +420,22 @@ static int ensure_coef(ksfd_handle *h, bool ghosts_done = false)
     h->coef_fresh = true;
     h->mg_coef_valid = false; h->mg_shift = -1.0;
     h->spec.means_valid = h->spec.ok && (long long)(1 + h->P.nlig) * plane_blocks(h->G) <= part_capacity();
+    return KSFD_OK;
+}
+
+// fp32 copy of the coefficient planes as they are now, for the readers that take it: the Horner path of the polynomial preconditioner
+// (poly_apply) and level 0 of the V cycle (mg_sys).  The spectral regime never asks.  (float) of the stored double is what k_jcoef's
+// own store rounds, so the readers see the same bits either way.
+static int ensure_coef32(ksfd_handle *h)
+{
+    if (!coef32_alloc(h) || h->coef32_fresh) return KSFD_OK;
+    const long long n = (long long)(3 + h->P.nlig) * h->G.plane;
+    {
+        Scope sc(h, KC_GFIELD, 12.0 * (double)n);
+        hipLaunchKernelGGL(k_coef32, dim3(blocks_for(n / 2)), dim3(KSFD_BLOCK), 0, h->st, n, (const double *)h->coef, h->coef32);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->coef32_fresh = true;
     return KSFD_OK;
 }
 

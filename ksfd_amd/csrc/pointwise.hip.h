@@ -460,52 +460,79 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_basis_rotate(KVec g, double *V, 
 // Step completion (PETSc TSEvaluateStep_RosW + TSErrorWeightedNorm, restated):
 //   unew = u + sum_j bt[j] Y_j ;  err = sum_j (b2t[j]-bt[j]) Y_j ;
 //   partial sum of (err / (atol + rtol*max(|unew|, |unew+err|)))^2.
-// Writes unew over u (the caller keeps a rollback copy) and, if errout != NULL, err.
-__global__ void __launch_bounds__(KSFD_BLOCK) k_rosw_finish(KVec g, double *__restrict__ u,
+// Out of place: reads u, writes unew to unew_out (the caller swaps the two buffers when the controller accepts; a rejected attempt has
+// touched nothing).  Row 1 of part: how many owned unew are NOT at or above their floor (rhomin for field 0, Umin for the others; NaN
+// counts) -- 0 proves that the groom of the next step would store the bits it loads.  errout != NULL: err is stored as well;
+// otherwise k_rosw_error makes it from Y on demand.
+__device__ __forceinline__ double ksfd_rosw_err(double e0, double e1, double e2, double e3, double y0, double y1, double y2, double y3)
+{
+    return e0 * y0 + e1 * y1 + e2 * y2 + e3 * y3;
+}
+__global__ void __launch_bounds__(KSFD_BLOCK) k_rosw_finish(KVec g, const double *__restrict__ u, double *__restrict__ unew_out,
                                                             const double *__restrict__ Y, long long ystride,
                                                             double bt0, double bt1, double bt2, double bt3,
                                                             double e0, double e1, double e2, double e3,
-                                                            double atol, double rtol, double *__restrict__ errout,
-                                                            double *__restrict__ part)
+                                                            double atol, double rtol, double rhomin, double Umin,
+                                                            double *__restrict__ errout, double *__restrict__ part)
 {
-    __shared__ double red[KSFD_BLOCK / KSFD_WAVE];
-    double acc = 0.0;
+    __shared__ double red[2][KSFD_BLOCK / KSFD_WAVE];
+    double acc = 0.0, below = 0.0;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (int c = 0; c < g.nf; c++) {
         const long long base = (long long)c * g.plane + g.off;
+        const double lo = c == 0 ? rhomin : Umin;
         for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < g.nloc; p += stride) {
             const double y0 = Y[base + p], y1 = Y[ystride + base + p], y2 = Y[2 * ystride + base + p],
                          y3 = Y[3 * ystride + base + p];
             const double un = u[base + p] + (bt0 * y0 + bt1 * y1 + bt2 * y2 + bt3 * y3);
-            const double er = e0 * y0 + e1 * y1 + e2 * y2 + e3 * y3;
+            const double er = ksfd_rosw_err(e0, e1, e2, e3, y0, y1, y2, y3);
             const double tol = atol + rtol * fmax(fabs(un), fabs(un + er));
             const double q = er / tol;
             acc += q * q;
-            u[base + p] = un;
+            below += (un >= lo) ? 0.0 : 1.0;
+            unew_out[base + p] = un;
             if (errout) errout[base + p] = er;
         }
     }
     acc = ksfd_wave_sum(acc);
-    if ((threadIdx.x & (KSFD_WAVE - 1)) == 0) red[threadIdx.x / KSFD_WAVE] = acc;
+    below = ksfd_wave_sum(below);
+    if ((threadIdx.x & (KSFD_WAVE - 1)) == 0) { red[0][threadIdx.x / KSFD_WAVE] = acc; red[1][threadIdx.x / KSFD_WAVE] = below; }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x < 2) {
         double t = 0.0;
-        for (int q = 0; q < KSFD_BLOCK / KSFD_WAVE; q++) t += red[q];
-        part[blockIdx.x] = t;
+        for (int q = 0; q < KSFD_BLOCK / KSFD_WAVE; q++) t += red[threadIdx.x][q];
+        part[(long long)threadIdx.x * gridDim.x + blockIdx.x] = t;
     }
 }
 
+// The embedded error vector of the last attempt from its stage vectors, for ksfd_get_last_error_vector: the expression k_rosw_finish
+// uses, so the same bits as its errout store
+__global__ void __launch_bounds__(KSFD_BLOCK) k_rosw_error(KVec g, const double *__restrict__ Y, long long ystride,
+                                                           double e0, double e1, double e2, double e3, double *__restrict__ errout)
+{
+    const long long base = (long long)blockIdx.y * g.plane + g.off;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < g.nloc; p += stride)
+        errout[base + p] = ksfd_rosw_err(e0, e1, e2, e3, Y[base + p], Y[ystride + base + p], Y[2 * ystride + base + p], Y[3 * ystride + base + p]);
+}
+
 // KSFDTS.groom on the stored state (KSFD/ksfdts.py:231-237)
-// copy != NULL: the groomed owned points are stored there as well (the step's roll-back copy: no pass of its own)
-__global__ void __launch_bounds__(KSFD_BLOCK) k_groom(KVec g, double *__restrict__ u, double rhomin, double Umin, double *__restrict__ copy = nullptr)
+__global__ void __launch_bounds__(KSFD_BLOCK) k_groom(KVec g, double *__restrict__ u, double rhomin, double Umin)
 {
     const long long base = (long long)blockIdx.y * g.plane + g.off;
     const double lo = blockIdx.y == 0 ? rhomin : Umin;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < g.nloc; p += stride) {
-        const double v = ksfd_clamp(u[base + p], lo);
-        u[base + p] = v;
-        if (copy) copy[base + p] = v;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < g.nloc; p += stride)
+        u[base + p] = ksfd_clamp(u[base + p], lo);
+}
+
+// fp32 copy of np coefficient planes (ensure_coef32): (float) of the stored double, what k_jcoef's own C32 store rounds
+__global__ void __launch_bounds__(KSFD_BLOCK) k_coef32(long long n, const double *__restrict__ C, float *__restrict__ C32)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x * 2;
+    for (long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 2; e < n; e += stride) {
+        const double2 c = *reinterpret_cast<const double2 *>(C + e);
+        *reinterpret_cast<float2 *>(C32 + e) = make_float2((float)c.x, (float)c.y);
     }
 }
 

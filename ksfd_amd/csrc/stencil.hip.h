@@ -562,10 +562,13 @@ __device__ __forceinline__ KWaveJob ksfd_wave_job(const KGeom &G, const KStrips 
 // is three rows behind by the time it is stored: 24 KB per wave further on, more than a CU's share of the L2 holds): 20 -> 14 vector
 // passes over the four RHS launches of a step.  The delay line is a wave-private LDS ring (8 KB per wave and ligand pair): kept in
 // registers it cost a wave per SIMD and most of the gain.
-template <int NL, bool CARRY = false>
+// GPLANE (stage 0 of a step only: no stage vectors, CARRY false): the G rows are loaded from the plane Gp -- plane 1 of the frozen
+// coefficient planes, G of the same clamped state with its ghost rows filled -- instead of evaluated.
+template <int NL, bool CARRY = false, bool GPLANE = false>
 __global__ void __launch_bounds__(KSFD_BLOCK) k_rhs2d_fused(KGeom G, KPhys P, KStrips S, const double *__restrict__ u,
                                                             KSrc src, double *__restrict__ out, KComb cmb = KComb{},
-                                                            double *__restrict__ normpart = nullptr, KDots dots = KDots{})
+                                                            double *__restrict__ normpart = nullptr, KDots dots = KDots{},
+                                                            const double *__restrict__ Gp = nullptr)
 {
     // normpart != NULL: every wave also leaves the sum of squares of what it stored in normpart[wave id] (||out||^2 without
     // a pass of its own; finished by k_reduce_rows in a fixed order), and its share of the inner products `dots` asks for
@@ -575,6 +578,7 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_rhs2d_fused(KGeom G, KPhys P, KS
     // 5-row windows, two columns per lane: slot s <-> row (r - 2 + s)
     double rw[5][2], gw[5][2], uw[NL][5][2];
     double nr[2], nu[NL][2];                   // raw values of the row being prefetched
+    double ng[2];                              // GPLANE: its G
     // CARRY: sum_j aout[j] Y_j of a row waits in a wave-private LDS ring of four rows from the load of the row until its store three rows
     // later (in registers the 16-32 doubles cost a wave per SIMD: 178 VGPRs against 146; wave-private and in program order: no barrier)
     __shared__ double2 cring[CARRY ? KSFD_BLOCK / KSFD_WAVE : 1][CARRY ? 4 : 1][CARRY ? NL + 1 : 1][CARRY ? KSFD_WAVE : 1];
@@ -585,6 +589,7 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_rhs2d_fused(KGeom G, KPhys P, KS
         const long long o = ksfd_rowoff(G, r) + J.c0;
         double2 t = ksfd_ld2(u + o);
         nr[0] = t.x; nr[1] = t.y;
+        if (GPLANE) { const double2 gq = ksfd_ld2(Gp + o); ng[0] = gq.x; ng[1] = gq.y; }
 #pragma unroll
         for (int l = 0; l < NL; l++) {
             double2 q = ksfd_ld2(u + (long long)(l + 1) * G.plane + o);
@@ -628,7 +633,8 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_rhs2d_fused(KGeom G, KPhys P, KS
             double rho = ksfd_clamp(nr[e], P.rhomin);
 #pragma unroll
             for (int l = 0; l < NL; l++) { U[l] = ksfd_clamp(nu[l][e], P.Umin); uw[l][4][e] = U[l]; }
-            ksfd_G<NL, false>(P, rho, U, gw[4][e], gr, GU);
+            if (GPLANE) gw[4][e] = ng[e];
+            else ksfd_G<NL, false>(P, rho, U, gw[4][e], gr, GU);
             rw[4][e] = rho;
         }
     };

@@ -5,7 +5,8 @@
 //   stage_gram_guess      Gram matrix of the right-hand sides of the attempt -> coefficients of the stage guess (stage_guess)
 //   stage_solve           direct (dense or banded) / spectral with its fallbacks / V cycle from a guess / the GMRES variants, and the multigrid retry
 //   step_attempt          the four stages
-//   step_finish           completion u <- u + sum bt_i Y_i with the embedded error vector, and its WRMS norm
+//   step_finish           completion u_new = u + sum bt_i Y_i (out of place), the WRMS norm of the embedded error, the count of values under their floor
+//   err_materialize       the embedded error vector itself, when somebody asks for it
 //   stats_begin / _end    the ksfd_step_stats counters
 // ksfd_step (ksfd_hip.hip) is the attempt loop of TSStep_RosW over them.
 // (part of the single translation unit ksfd_hip.hip; included last)
@@ -261,20 +262,38 @@ static int step_attempt(ksfd_handle *h, const ksfd_step_opts *opts, const Attemp
     return rc;
 }
 
-// completion + embedded error norm
-static int step_finish(ksfd_handle *h, const ksfd_step_opts *opts, double *wrms)
+// The embedded error vector of the last completed attempt into h->errv, if the completion left it in the stage vectors.  Nothing
+// outside a step attempt writes the owned points of Y (halo exchanges fill ghost rows only); the next attempt's first stage solve does.
+static int err_materialize(ksfd_handle *h)
+{
+    if (!h->err_pending) return KSFD_OK;
+    {
+        Scope sc(h, KC_FINISH, vbytes(h, 5));
+        hipLaunchKernelGGL(k_rosw_error, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)h->Y, h->vlen, h->b2t[0] - h->bt[0],
+                           h->b2t[1] - h->bt[1], h->b2t[2] - h->bt[2], h->b2t[3] - h->bt[3], h->errv);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->err_pending = false;
+    return KSFD_OK;
+}
+
+// completion + embedded error norm.  The new state goes to h->usave: h->u is as it was until the caller accepts (step_run swaps).
+// *below: owned values of the new state under their floor (exact: a count carried in doubles; summed over the ranks of a ring)
+static int step_finish(ksfd_handle *h, const ksfd_step_opts *opts, double *wrms, double *below)
 {
     int rc;
     {
-        Scope sc(h, KC_FINISH, vbytes(h, 7));
-        hipLaunchKernelGGL(k_rosw_finish, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->Y, h->vlen,
+        Scope sc(h, KC_FINISH, vbytes(h, h->old_boundary ? 7 : 6));
+        hipLaunchKernelGGL(k_rosw_finish, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)h->u, h->usave, h->Y, h->vlen,
                            h->bt[0], h->bt[1], h->bt[2], h->bt[3], h->b2t[0] - h->bt[0], h->b2t[1] - h->bt[1],
-                           h->b2t[2] - h->bt[2], h->b2t[3] - h->bt[3], opts->atol, opts->rtol, h->errv, h->part);
+                           h->b2t[2] - h->bt[2], h->b2t[3] - h->bt[3], opts->atol, opts->rtol, h->P.rhomin, h->P.Umin,
+                           h->old_boundary ? h->errv : (double *)nullptr, h->part);
     }
     h->have_err = true;
-    h->coef_fresh = false;                                   // u <- u_new (a rollback makes the planes current again)
-    if ((rc = reduce_rows(h, 1, h->nblk_vec, 0))) return rc;
+    h->err_pending = !h->old_boundary;
+    if ((rc = reduce_rows(h, 2, h->nblk_vec, 0))) return rc;
     const double ntot = (double)h->G.F * (double)h->cfg.n[0] * (double)h->cfg.n[1] * (double)h->cfg.n[2];
     *wrms = sqrt(h->hres[0] / ntot);
+    *below = h->hres[1];
     return KSFD_OK;
 }
