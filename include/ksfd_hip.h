@@ -306,6 +306,26 @@ int ksfd_set_mg_coarse(ksfd_handle *h, int32_t kind, int32_t max_unknowns);
  * KSFD_EINVAL, nothing changed: a negative value, a 1-D handle with a transport, a handle without a hierarchy.
  * ksfd_set_mg_coarse kind 1 stays refused on handles with a transport. */
 int ksfd_set_mg_agglomerate(ksfd_handle *h, int64_t max_points);
+/* The coarse TAIL of the V cycle in one workgroup launch (opt-in).  The last levels of every hierarchy hold 64 .. ~1500 points; a
+ * V cycle spends tens of dependent tiny launches on them.  With the tail the sub-cycle from a level t down to the level the cycle ends on
+ * and back -- pre-smoothing, residual, restriction, the Chebyshev sweeps of the end level, prolongation, post-smoothing: mathematically
+ * the same operator -- is ONE launch of one workgroup that keeps every level vector of those levels in the LDS (k_mg_tail); inside
+ * the captured graph it is one node, on handles with a halo transport one eager launch.
+ * max_points = 0: off (the default): every bit is that of a handle that never made the call.
+ * max_points > 0: t = the smallest level >= 1 for which every level t .. end is whole on this rank (a handle without a halo transport,
+ * or a replicated level of ksfd_set_mg_agglomerate; a distributed level never qualifies), has at most max_points points, and the levels
+ * together fit the LDS a workgroup may have (160 KB; 8 * points * (4 F + 1) bytes per level), in at most 8 levels.  Level 0 is never
+ * part of the tail.  The tail's levels keep fp64 vectors in the cycle with fp32 level vectors.  If no level qualifies the call returns
+ * KSFD_OK and the cycle is the one without it (info.level = -1).  The plan is remade whenever the hierarchy is rebuilt
+ * (ksfd_set_mg_agglomerate).  The call is collective on handles with a transport (every rank passes the same value) and leaves the
+ * hierarchy "not set up", as ksfd_mg_part does.  Nothing joins the checkpoint.
+ * KSFD_EINVAL, nothing changed: a negative value, a handle without a hierarchy (max_points > 0), an exact coarse solve in force
+ * (ksfd_set_mg_coarse kind 1) -- the two exclude each other: ksfd_set_mg_coarse kind 1 is refused while max_points > 0.
+ * ksfd_get_mg_tail_info: level = t or -1, nlevels and points of the tail's levels, the LDS bytes of the launch, and the launches of the
+ * tail over the life of the handle (replays of the captured graph counted). */
+typedef struct ksfd_mg_tail_info { int32_t level, nlevels; int64_t max_points; int64_t points[8]; int64_t lds_bytes, launches; } ksfd_mg_tail_info;
+int ksfd_set_mg_tail(ksfd_handle *h, int64_t max_points);
+int ksfd_get_mg_tail_info(ksfd_handle *h, ksfd_mg_tail_info *info);
 typedef struct ksfd_mg_coarse_info { int32_t kind, level, nlevels, F; int64_t n[3]; int64_t unknowns;
                                      int32_t factorizations, solves, fallbacks, reserved; } ksfd_mg_coarse_info;
 /* valid with kind 0 too: describes the level the cycle ends on; the counters run over the life of the handle */
@@ -353,11 +373,13 @@ int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double 
  *   SMOOTH       out0 = mg_smooth(level, shift, b = in0, x0 = in1 or NULL for the zero guess, nu = 1 .. 5, ratio) after a set-up at shift
  *   CYCLE        level 0: out0 = mg_precond(shift, in0); variant 0: fp64 level vectors, 1: fp32 level vectors (what ksp_rtol >= 1e-7
  *                selects in ksfd_step; KSFD_EINVAL where the handle would not run that cycle).  Captured graph or eager launches as the
- *                handle is set (ksfd_set_mg_params). */
+ *                handle is set (ksfd_set_mg_params).
+ *   TAIL         level = the first tail level of ksfd_set_mg_tail (any other level: KSFD_EINVAL): out0 = the tail applied to in0 after a
+ *                set-up at shift, through the wrapper the cycle calls (mg_tail_apply), with the handle's nu and smoothing ratio */
 typedef struct ksfd_mg_level_info_t { int32_t level, nlevels, end_level, F; int64_t n[3]; int64_t sloc, points;
                                       int32_t path, f32, coef32, can_fuse, have_setup, coarse_sweeps; double lam_max, ratio; } ksfd_mg_level_info_t;
 enum { KSFD_MGP_COEF = 0, KSFD_MGP_RESTRICT = 1, KSFD_MGP_PROLONG_ADD = 2, KSFD_MGP_OPERATOR = 3, KSFD_MGP_DINV = 4, KSFD_MGP_DINV_APPLY = 5,
-       KSFD_MGP_SMOOTH = 6, KSFD_MGP_CYCLE = 7 };
+       KSFD_MGP_SMOOTH = 6, KSFD_MGP_CYCLE = 7, KSFD_MGP_TAIL = 8 };
 int ksfd_mg_level_info(ksfd_handle *h, int32_t level, int32_t setup, double shift, ksfd_mg_level_info_t *info);
 int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t variant, int32_t nu, double shift, double ratio,
                  const double *in0, const double *in1, double *out0, double *out1);

@@ -93,6 +93,17 @@ struct MGCoarse {
     int32_t graph_solves = 0;                // coarse solves inside the captured part of the cycle, counted at every replay
 };
 
+// the coarse tail of the V cycle in one workgroup launch (ksfd_set_mg_tail; mg_tail_plan.h, k_mg_tail in mg.hip.h, mg_tail_* in
+// mg_host.hip.h).  The plan is remade by every mg_build from max_points; nothing of this joins a checkpoint.
+struct MGTail {
+    int64_t max_points = 0;                  // 0: off (the default)
+    int level = -1;                          // first tail level t >= 1, or -1: no level qualifies, the cycle is the one without the call
+    int nlev = 0;                            // levels t .. the level the cycle ends on
+    long long lds = 0;                       // dynamic LDS bytes of the launch (the plan's sum)
+    int64_t launches = 0;                    // over the handle's life
+    int64_t graph_launches = 0;              // launches inside the captured part of the cycle, counted at every replay
+};
+
 // banded direct solver for 1-D grids, pc_type 6 (banded_plan.h / banded.hip.h / banded_host.hip.h): allocated on first use, factors
 // rebuilt every step attempt; the pivot indices never leave the device
 struct BandState {
@@ -244,6 +255,7 @@ struct ksfd_handle {
     LUState lu;
     BandState band;
     MGCoarse mgc;
+    MGTail mgt;
 
     // multigrid preconditioner
     std::vector<MGLevel> mg;

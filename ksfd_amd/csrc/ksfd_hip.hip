@@ -23,6 +23,7 @@
 #include "step_control.h"
 #include "mg_coarse_plan.h"
 #include "mg_agglomerate_plan.h"
+#include "mg_tail_plan.h"
 
 #include "handle.hip.h"
 #include "ops.hip.h"
@@ -787,6 +788,7 @@ extern "C" int ksfd_set_mg_coarse(ksfd_handle *h, int32_t kind, int32_t max_unkn
         if (h->ring) return fail(h, KSFD_EINVAL, "mg_coarse: the exact coarse solve is single rank only (this handle has a halo transport)");
         if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_coarse: this handle has no multigrid hierarchy");
         if (max_unknowns > KSFD_MG_DIRECT_MAX) return fail(h, KSFD_EINVAL, "mg_coarse: max_unknowns = %d above KSFD_MG_DIRECT_MAX = %d", (int)max_unknowns, KSFD_MG_DIRECT_MAX);
+        if (h->mgt.max_points > 0) return fail(h, KSFD_EINVAL, "mg_coarse: the exact coarse solve and the coarse tail exclude each other (ksfd_set_mg_tail(%lld) is in force)", (long long)h->mgt.max_points);
     } else if (!h->mg_ok) return KSFD_OK;               // nothing to switch off
     const int level = mg_coarse_choice(h, kind, max_unknowns);
     if (level < 0) {
@@ -991,6 +993,9 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
     case KSFD_MGP_DINV_APPLY: ok = variant == 0 || (variant == 1 && L.f32); setup = true; need_o1 = true; break;
     case KSFD_MGP_SMOOTH: ok = variant == 0; setup = true; break;
     case KSFD_MGP_CYCLE: ok = level == 0 && (variant == 0 || variant == 1); setup = true; break;
+    case KSFD_MGP_TAIL:
+        if (level != h->mgt.level) return fail(h, KSFD_EINVAL, "mg_part: level %d is not the first level of the coarse tail (%d; -1: this handle has none)", (int)level, h->mgt.level);
+        ok = variant == 0; setup = true; break;
     default: return fail(h, KSFD_EINVAL, "mg_part: unknown part %d", (int)part);
     }
     if (!ok) return fail(h, KSFD_EINVAL, "mg_part %d: level %d has no variant %d", (int)part, (int)level, (int)variant);
@@ -1061,6 +1066,11 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
             else HIPCHK(h, hipMemsetAsync(b, 0x7f, sizeof(double) * (size_t)L.vlen, h->st));      // zero guess: x is not to be read (1.4e306 if it is)
             if ((r = mg_smooth(h, L, shift, a, b, nu, !in1, ratio))) return r;
             return mgp_get(h, L, F, (const double *)b, out0);
+        case KSFD_MGP_TAIL:                                    // b and x are the level's own, as in the cycle
+            if ((r = mgp_put(h, L, F, in0, L.v64.b))) return r;
+            HIPCHK(h, hipMemsetAsync(L.v64.x, 0x7f, sizeof(double) * (size_t)L.vlen, h->st));
+            if ((r = mg_tail_apply(h, shift, L.v64.b, L.v64.x))) return r;
+            return mgp_get(h, L, F, (const double *)L.v64.x, out0);
         default: {                                             // KSFD_MGP_CYCLE
             if ((r = mgp_put(h, L, F, in0, a))) return r;
             HIPCHK(h, hipMemsetAsync(b, 0x7f, sizeof(double) * (size_t)L.vlen, h->st));
@@ -1077,6 +1087,35 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
     if (!rc && hipGetLastError() != hipSuccess) rc = fail(h, KSFD_EHIP, "mg_part %d: launch failed", (int)part);
     mgp_end(h);
     return rc;
+}
+extern "C" int ksfd_set_mg_tail(ksfd_handle *h, int64_t max_points)
+{
+    if (!h) return KSFD_EINVAL;
+    if (max_points < 0) return fail(h, KSFD_EINVAL, "mg_tail: max_points = %lld is negative", (long long)max_points);
+    if (max_points == h->mgt.max_points) return KSFD_OK;
+    if (max_points > 0) {
+        if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_tail: this handle has no multigrid hierarchy");
+        if (h->mgc.kind == 1) return fail(h, KSFD_EINVAL, "mg_tail: the coarse tail and the exact coarse solve exclude each other (ksfd_set_mg_coarse kind 1 is in force)");
+    }
+    hipSetDevice(h->device);
+    const MGTail before = h->mgt;
+    h->mgt.max_points = max_points;
+    const int rc = mg_tail_replan(h);
+    if (rc) { h->mgt = before; return rc; }
+    mgp_end(h);                                          // another cycle: the next one sets the hierarchy up again and captures its graph again
+    h->dr.valid = false;                                 // the recycled subspace belongs to the preconditioner that is gone
+    return KSFD_OK;
+}
+extern "C" int ksfd_get_mg_tail_info(ksfd_handle *h, ksfd_mg_tail_info *info)
+{
+    if (!h || !info) return KSFD_EINVAL;
+    memset(info, 0, sizeof *info);
+    info->level = -1;
+    if (!h->mg_ok) return fail(h, KSFD_EINVAL, "mg_tail: this handle has no multigrid hierarchy");
+    const MGTail &M = h->mgt;
+    info->level = M.level; info->nlevels = M.nlev; info->max_points = M.max_points; info->lds_bytes = M.lds; info->launches = M.launches;
+    for (int q = 0; q < M.nlev && q < 8; q++) info->points[q] = h->mg[M.level + q].G.nloc;
+    return KSFD_OK;
 }
 extern "C" int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double target, double mg_threshold)
 {

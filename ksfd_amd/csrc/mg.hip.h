@@ -17,6 +17,7 @@
 // is an instance of its own, BORDER, of the same text).
 #pragma once
 #include "stencil.hip.h"
+#include "mg_tail_plan.h"
 
 // The slow axis of a transfer between a fine level and the next coarser one (x in 1-D, y in 2-D, z in 3-D; a slow unit is a point, a row
 // or a plane).  The inner axes are periodic and whole on every rank; the slow axis is this rank's slab, and how it is indexed is all
@@ -282,5 +283,319 @@ __global__ void __launch_bounds__(KSFD_BLOCK) k_ratio_est(long long n, const flo
         double t = 0.0;
         for (int q = 0; q < KSFD_BLOCK / KSFD_WAVE; q++) t = fmax(t, red[q]);
         part[blockIdx.x] = t;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The coarse TAIL of the V cycle in one workgroup (ksfd_set_mg_tail, opt-in; which levels: mg_tail_plan.h).  The sub-cycle from the
+// first tail level down to the level the cycle ends on and back -- pre-smoothing, residual, restriction, the Chebyshev sweeps of the
+// end level, prolongation, post-smoothing: what mg_vcycle<double>(t) of mg_host.hip.h runs as tens of tiny launches -- is pointwise in
+// every phase, so ONE block of MG_TAIL_THREADS threads runs it with every level vector in the LDS and __syncthreads() between the phases.
+// The coefficient planes and the fp32 inverse point blocks stay in global memory (read-only, L2-resident).
+//
+// Rules of the text below:
+//  * thread `tid` owns the points tid, tid + NT, ... of EVERY level (the loop has the compile-time trip count PPT of the plan and
+//    tests p < np), so whatever a phase reads at its own point alone needs no barrier behind the phase that wrote it;
+//  * every __syncthreads() stands in control flow that depends on kernel arguments alone (level count, sweep counts): uniform over
+//    the block.  No loop bound is read from data; no atomics, no waiting on memory;
+//  * a phase that replaces a vector whose neighbours other threads still read (d under A d) keeps the new values in registers (dn)
+//    and stores them behind the barrier.
+// The levels are whole (no ghost units, plane = points) and every axis wraps.  Formulas: the operator of k_jvp_generic on the dG plane of
+// k_dg_frozen, the transfers of k_mg_restrict / k_mg_prolong_add, the Chebyshev recurrence of mg_smooth (direction form) with the
+// coefficients of mg_cheb, the blocks of k_blockdiag_inv as they are in memory.
+struct KMGTailLevel {
+    const double *coef;                // [rho, G, G_rho, G_U..] planes of np doubles
+    const float *dinv;                 // F*F planes of the inverse point blocks
+    int n[3];                          // extents per axis (1 on the axes the grid does not have)
+    int np;                            // points
+    int sweeps;                        // Chebyshev sweeps: nu, on the last level those of the coarse solve
+    int pad;
+    double inv_h[3], inv_h2[3];
+    double theta, delta, sig1, rho0;   // mg_cheb of the level's interval [lam_max / ratio, lam_max]
+};
+struct KMGTail {
+    int nlev, dim;
+    double shift;
+    KMGTailLevel L[ksfd_ctl::MG_TAIL_MAX_LEVELS];
+};
+struct KMGTailVecs { double *x, *b, *r, *d, *dG; };
+
+// the LDS of level q: behind the levels before it, each mg_tail_level_bytes long (the plan's formula): x, b, r, d (F planes), dG
+__device__ __forceinline__ KMGTailVecs ksfd_tail_vecs(double *lds, const KMGTail &T, int q, int F)
+{
+    long long off = 0;
+    for (int s = 0; s < q; s++) off += ksfd_ctl::mg_tail_level_bytes(T.L[s].np, F) / 8;
+    const long long fp = (long long)F * T.L[q].np;
+    KMGTailVecs V;
+    V.x = lds + off; V.b = V.x + fp; V.r = V.b + fp; V.d = V.r + fp; V.dG = V.d + fp;
+    return V;
+}
+
+// q = (shift I - J) v at point p of level D; v and dG in the LDS
+template <int NL>
+__device__ __forceinline__ void ksfd_tail_op(const KMGTailLevel &D, int dim, const KPhys &P, double shift, const double *v,
+                                             const double *dG, int p, double *q)
+{
+    const int np = D.np, nx = D.n[0], ny = D.n[1];
+    const double *__restrict__ rho = D.coef, *__restrict__ Gb = D.coef + np;
+    const int idx[3] = { p % nx, (p / nx) % ny, p / (nx * ny) };
+    const int str[3] = { 1, nx, nx * ny };
+    double acc = 0.0, lapG = 0.0, lapdG = 0.0, lapV[NL];
+#pragma unroll
+    for (int l = 0; l < NL; l++) lapV[l] = 0.0;
+    for (int a = 0; a < dim; a++) {
+        const int ext = D.n[a], base = p - idx[a] * str[a];
+        int o[5];
+#pragma unroll
+        for (int m = 0; m < 5; m++) o[m] = base + ((idx[a] + m - 2) % ext + ext) % ext * str[a];
+        const double r_m2 = ksfd_clamp(rho[o[0]], P.rhomin), r_m1 = ksfd_clamp(rho[o[1]], P.rhomin),
+                     r_p1 = ksfd_clamp(rho[o[3]], P.rhomin), r_p2 = ksfd_clamp(rho[o[4]], P.rhomin);
+        const double d1r = KSFD_D1(r_m2, r_m1, r_p1, r_p2) * D.inv_h[a];
+        const double d1v = KSFD_D1(v[o[0]], v[o[1]], v[o[3]], v[o[4]]) * D.inv_h[a];
+        const double d1g = KSFD_D1(Gb[o[0]], Gb[o[1]], Gb[o[3]], Gb[o[4]]) * D.inv_h[a];
+        const double d1e = KSFD_D1(dG[o[0]], dG[o[1]], dG[o[3]], dG[o[4]]) * D.inv_h[a];
+        acc += d1v * d1g + d1r * d1e;
+        lapG += KSFD_D2(Gb[o[0]], Gb[o[1]], Gb[o[2]], Gb[o[3]], Gb[o[4]]) * D.inv_h2[a];
+        lapdG += KSFD_D2(dG[o[0]], dG[o[1]], dG[o[2]], dG[o[3]], dG[o[4]]) * D.inv_h2[a];
+#pragma unroll
+        for (int l = 0; l < NL; l++) {
+            const double *V = v + (l + 1) * np;
+            lapV[l] += KSFD_D2(V[o[0]], V[o[1]], V[o[2]], V[o[3]], V[o[4]]) * D.inv_h2[a];
+        }
+    }
+    const double v0 = v[p], rho0 = ksfd_clamp(rho[p], P.rhomin);
+    q[0] = shift * v0 - (acc + v0 * lapG + rho0 * lapdG);
+#pragma unroll
+    for (int l = 0; l < NL; l++) {
+        const double V0 = v[(l + 1) * np + p];
+        q[l + 1] = shift * V0 - (-P.lig_gamma[l] * V0 + P.lig_s[l] * v0 + P.lig_D[l] * lapV[l]);
+    }
+}
+
+// dG = G_rho v_rho + sum_l G_Ul v_Ul at point p from the F values w of v there
+template <int NL>
+__device__ __forceinline__ double ksfd_tail_dg(const KMGTailLevel &D, int p, const double *w)
+{
+    double d = D.coef[2 * D.np + p] * w[0];
+#pragma unroll
+    for (int l = 0; l < NL; l++) d += D.coef[(3 + l) * D.np + p] * w[l + 1];
+    return d;
+}
+
+// z = scale * Dinv r at point p
+template <int NL>
+__device__ __forceinline__ void ksfd_tail_dinv(const KMGTailLevel &D, int p, const double *r, double scale, double *z)
+{
+    constexpr int F = NL + 1;
+#pragma unroll
+    for (int a = 0; a < F; a++) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < F; c++) s += D.dinv[(a * F + c) * D.np + p] * r[c];
+        z[a] = scale * s;
+    }
+}
+
+// dG of the vector v over the thread's points (own points only: no barrier needed behind the phase that wrote v there)
+template <int NL, int PPT>
+__device__ __forceinline__ void ksfd_tail_dg_pass(const KMGTailLevel &D, const double *v, double *dG)
+{
+    constexpr int F = NL + 1, NT = ksfd_ctl::MG_TAIL_THREADS;
+#pragma unroll
+    for (int s = 0; s < PPT; s++) {
+        const int p = (int)threadIdx.x + s * NT;
+        if (p < D.np) {
+            double w[F];
+#pragma unroll
+            for (int c = 0; c < F; c++) w[c] = v[c * D.np + p];
+            dG[p] = ksfd_tail_dg<NL>(D, p, w);
+        }
+    }
+}
+
+// D.sweeps Chebyshev sweeps on A x = b (V.b -> V.x), from the zero guess or as a correction of V.x.  On entry V.b (and V.x) are complete
+// at the thread's own points at least -- and, for a correction, NOTHING but the own points of V.x is read before the first barrier.  On
+// exit V.x is complete at the thread's own points: the caller puts a barrier before anything reads its neighbours.
+template <int NL, int PPT>
+__device__ __forceinline__ void ksfd_tail_smooth(const KMGTailLevel &D, int dim, const KPhys &P, double shift, const KMGTailVecs &V, bool zero_init)
+{
+    constexpr int F = NL + 1, NT = ksfd_ctl::MG_TAIL_THREADS;
+    const int np = D.np, tid = (int)threadIdx.x;
+    double dn[PPT][F];                                       // the direction d_k at the thread's points
+    if (zero_init) {
+        // r_0 = b, d_0 = Dinv b / theta, x = 0
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+                double rv[F];
+#pragma unroll
+                for (int c = 0; c < F; c++) { rv[c] = V.b[c * np + p]; V.r[c * np + p] = rv[c]; V.x[c * np + p] = 0.0; }
+                ksfd_tail_dinv<NL>(D, p, rv, 1.0 / D.theta, dn[s]);
+            }
+        }
+    } else {
+        // r_0 = b - A x, d_0 = Dinv r_0 / theta
+        ksfd_tail_dg_pass<NL, PPT>(D, V.x, V.dG);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+                double q[F], rv[F];
+                ksfd_tail_op<NL>(D, dim, P, shift, V.x, V.dG, p, q);
+#pragma unroll
+                for (int c = 0; c < F; c++) { rv[c] = V.b[c * np + p] - q[c]; V.r[c * np + p] = rv[c]; }
+                ksfd_tail_dinv<NL>(D, p, rv, 1.0 / D.theta, dn[s]);
+            }
+        }
+        __syncthreads();                                     // the reads of x and dG are over: both change below
+    }
+    double rho = D.rho0;
+    for (int k = 1; k < D.sweeps; k++) {
+        // d_{k-1} and its dG plane into the LDS
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+#pragma unroll
+                for (int c = 0; c < F; c++) V.d[c * np + p] = dn[s][c];
+                V.dG[p] = ksfd_tail_dg<NL>(D, p, dn[s]);
+            }
+        }
+        __syncthreads();
+        // x += d ; r -= A d ; d = c1 d + c2 Dinv r
+        const double rhon = 1.0 / (2.0 * D.sig1 - rho), c1 = rhon * rho, c2 = 2.0 * rhon / D.delta;
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+                double q[F], rv[F], z[F];
+                ksfd_tail_op<NL>(D, dim, P, shift, V.d, V.dG, p, q);
+#pragma unroll
+                for (int c = 0; c < F; c++) { V.x[c * np + p] += dn[s][c]; rv[c] = V.r[c * np + p] - q[c]; V.r[c * np + p] = rv[c]; }
+                ksfd_tail_dinv<NL>(D, p, rv, c2, z);
+#pragma unroll
+                for (int c = 0; c < F; c++) dn[s][c] = c1 * dn[s][c] + z[c];
+            }
+        }
+        __syncthreads();                                     // the reads of d and dG are over
+        rho = rhon;
+    }
+#pragma unroll
+    for (int s = 0; s < PPT; s++) {
+        const int p = tid + s * NT;
+        if (p < np) {
+#pragma unroll
+            for (int c = 0; c < F; c++) V.x[c * np + p] += dn[s][c];
+        }
+    }
+}
+
+// x = (one V cycle from level T.L[0] down to T.L[nlev - 1] and back) b; b and x: F planes of T.L[0].np doubles in global memory
+template <int NL>
+__global__ void __launch_bounds__(ksfd_ctl::MG_TAIL_THREADS) k_mg_tail(KMGTail T, KPhys P, const double *__restrict__ bg, double *__restrict__ xg)
+{
+    constexpr int F = NL + 1, NT = ksfd_ctl::MG_TAIL_THREADS, PPT = ksfd_ctl::mg_tail_points_per_thread(F);
+    extern __shared__ double mg_tail_lds[];
+    const int tid = (int)threadIdx.x, dim = T.dim, last = T.nlev - 1;
+    {
+        const KMGTailVecs V = ksfd_tail_vecs(mg_tail_lds, T, 0, F);
+        const int np = T.L[0].np;
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+#pragma unroll
+                for (int c = 0; c < F; c++) V.b[c * np + p] = bg[(long long)c * np + p];
+            }
+        }
+    }
+    // down: pre-smoothing from the zero guess, residual, full weighting onto the next level
+    for (int q = 0; q < last; q++) {
+        const KMGTailLevel &D = T.L[q], &Dc = T.L[q + 1];
+        const KMGTailVecs V = ksfd_tail_vecs(mg_tail_lds, T, q, F), Vc = ksfd_tail_vecs(mg_tail_lds, T, q + 1, F);
+        const int np = D.np;
+        ksfd_tail_smooth<NL, PPT>(D, dim, P, T.shift, V, true);
+        ksfd_tail_dg_pass<NL, PPT>(D, V.x, V.dG);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+                double w[F];
+                ksfd_tail_op<NL>(D, dim, P, T.shift, V.x, V.dG, p, w);
+#pragma unroll
+                for (int c = 0; c < F; c++) V.r[c * np + p] = V.b[c * np + p] - w[c];
+            }
+        }
+        __syncthreads();
+        // coarse b(I, J, K) = sum w_a w_b w_d r(2I + d, 2J + b, 2K + a), w = (1/4, 1/2, 1/4), over the axes the grid has
+        const int nxf = D.n[0], nyf = D.n[1], nzf = D.n[2], nxc = Dc.n[0], nyc = Dc.n[1], npc = Dc.np;
+        const int cx = 3, cy = dim > 1 ? 3 : 1, cz = dim > 2 ? 3 : 1;
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < npc) {
+                const int I = p % nxc, J = (p / nxc) % nyc, K = p / (nxc * nyc);
+                const double wt[3] = { 0.25, 0.5, 0.25 };
+                for (int c = 0; c < F; c++) {
+                    const double *f = V.r + c * np;
+                    double sum = 0.0;
+                    for (int a = 0; a < cz; a++) {
+                        const int kz = cz == 1 ? 0 : (2 * K + a - 1 + nzf) % nzf;
+                        for (int b = 0; b < cy; b++) {
+                            const int jy = cy == 1 ? 0 : (2 * J + b - 1 + nyf) % nyf;
+                            const double wab = (cz == 1 ? 1.0 : wt[a]) * (cy == 1 ? 1.0 : wt[b]);
+                            for (int d = 0; d < cx; d++) sum += wab * wt[d] * f[(2 * I + d - 1 + nxf) % nxf + nxf * (jy + nyf * kz)];
+                        }
+                    }
+                    Vc.b[c * npc + p] = sum;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // the level the cycle ends on: its Chebyshev sweeps over the whole interval, from the zero guess
+    ksfd_tail_smooth<NL, PPT>(T.L[last], dim, P, T.shift, ksfd_tail_vecs(mg_tail_lds, T, last, F), true);
+    __syncthreads();
+    // up: x += P x_coarse (linear interpolation along each axis), post-smoothing as a correction
+    for (int q = last - 1; q >= 0; q--) {
+        const KMGTailLevel &D = T.L[q], &Dc = T.L[q + 1];
+        const KMGTailVecs V = ksfd_tail_vecs(mg_tail_lds, T, q, F), Vc = ksfd_tail_vecs(mg_tail_lds, T, q + 1, F);
+        const int np = D.np, nxf = D.n[0], nyf = D.n[1], nxc = Dc.n[0], nyc = Dc.n[1], nzc = Dc.n[2], npc = Dc.np;
+        const int cy = dim > 1 ? 2 : 1, cz = dim > 2 ? 2 : 1;
+        const double wsum = 1.0 / (2 * cy * cz);
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+                const int i = p % nxf, j = (p / nxf) % nyf, k = p / (nxf * nyf);
+                const int Ii[2] = { i >> 1, (i & 1) ? ((i >> 1) + 1) % nxc : i >> 1 };
+                const int Jj[2] = { j >> 1, (j & 1) ? ((j >> 1) + 1) % nyc : j >> 1 };
+                const int Kk[2] = { k >> 1, (k & 1) ? ((k >> 1) + 1) % nzc : k >> 1 };
+                for (int c = 0; c < F; c++) {
+                    const double *g = Vc.x + c * npc;
+                    double sum = 0.0;
+                    for (int a = 0; a < cz; a++)
+                        for (int b = 0; b < cy; b++) sum += g[Ii[0] + nxc * (Jj[b] + nyc * Kk[a])] + g[Ii[1] + nxc * (Jj[b] + nyc * Kk[a])];
+                    V.x[c * np + p] += wsum * sum;
+                }
+            }
+        }
+        ksfd_tail_smooth<NL, PPT>(D, dim, P, T.shift, V, false);
+        __syncthreads();
+    }
+    {
+        const KMGTailVecs V = ksfd_tail_vecs(mg_tail_lds, T, 0, F);
+        const int np = T.L[0].np;
+#pragma unroll
+        for (int s = 0; s < PPT; s++) {
+            const int p = tid + s * NT;
+            if (p < np) {
+#pragma unroll
+                for (int c = 0; c < F; c++) xg[(long long)c * np + p] = V.x[c * np + p];
+            }
+        }
     }
 }

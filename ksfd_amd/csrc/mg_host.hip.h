@@ -10,7 +10,10 @@ static int mgc_apply(ksfd_handle *h, MGLevel &L, const double *b, double *x);
 static inline size_t mg_end(const ksfd_handle *h) { return h->mgc.kind == 1 ? (size_t)h->mgc.level : h->mg.size() - 1; }
 // level l keeps fp32 vectors in the cycle with fp32 level vectors (the level of an exact coarse solve stays in fp64, like the coarsest
 // level of the Chebyshev cycle)
-static inline bool mg_f32(const ksfd_handle *h, size_t l) { return h->mg[l].f32 && !(h->mgc.kind == 1 && l == (size_t)h->mgc.level); }
+static inline bool mg_f32(const ksfd_handle *h, size_t l)
+{
+    return h->mg[l].f32 && !(h->mgc.kind == 1 && l == (size_t)h->mgc.level) && !(h->mgt.level >= 1 && l >= (size_t)h->mgt.level);   // the tail's levels: fp64, in the LDS
+}
 
 // The frozen Jacobian action on level L (ops.hip.h: JvpSys, jvp_path).  Level 0 is the handle's grid: booked as its Jacobian actions are,
 // and its fp32 coefficient copy is the handle's (made on demand: ensure_coef32 before the first launch).  The levels have no launch of the second-generation 3-D kernel: the strip kernel serves
@@ -25,6 +28,7 @@ static void mg_free(ksfd_handle *h)
 {
     mgc_free(h);
     h->mgc = MGCoarse();
+    h->mgt.level = -1; h->mgt.nlev = 0; h->mgt.lds = 0;      // max_points stays: mg_build plans the tail again
     if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
     for (size_t l = 0; l < h->mg.size(); l++) {
         MGLevel &L = h->mg[l];
@@ -61,6 +65,30 @@ static int mg_push_level(ksfd_handle *h, long long nx, long long ny, long long r
         alloc_d(h, &M.Ad, M.vlen) || alloc_d(h, &M.dG, M.G.plane) || alloc_d(h, &M.pv, M.vlen)) return KSFD_ENOMEM;
     double *zero[] = { M.v64.x, M.v64.b, M.v64.r, M.v64.d, M.Ad, M.pv };
     for (double *z : zero) if (z) hipMemsetAsync(z, 0, sizeof(double) * (size_t)M.vlen, h->st);
+    return KSFD_OK;
+}
+
+// The coarse tail (ksfd_set_mg_tail): which levels run as one workgroup launch, from the stored max_points (mg_tail_plan.h), and the
+// dynamic LDS size of the kernel instance this handle launches.  max_points = 0: nothing is touched, no HIP call is made.
+static int mg_tail_replan(ksfd_handle *h)
+{
+    MGTail &M = h->mgt;
+    M.level = -1; M.nlev = 0; M.lds = 0;
+    if (M.max_points <= 0 || !h->mg_ok) return KSFD_OK;
+    std::vector<long long> points;
+    std::vector<int> local;
+    for (const MGLevel &L : h->mg) {
+        points.push_back(L.G.nloc);
+        local.push_back((!h->ring || L.rep) && L.G.ng == 0 && L.G.plane == L.G.nloc ? 1 : 0);
+    }
+    const int end = (int)mg_end(h);
+    long long lds = 0;
+    const int t = ksfd_ctl::mg_tail_first_level(points.data(), local.data(), end, h->G.F, M.max_points, ksfd_ctl::MG_TAIL_LDS_BUDGET, &lds);
+    if (t < 1) return KSFD_OK;
+    hipError_t e = hipSuccess;
+    NL_DISPATCH(h->P.nlig, e = hipFuncSetAttribute((const void *)k_mg_tail<NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, KSFD_EHIP, "mg_tail: %lld bytes of dynamic LDS refused: %s", lds, hipGetErrorString(e)); }
+    M.level = t; M.nlev = end - t + 1; M.lds = lds;
     return KSFD_OK;
 }
 
@@ -101,7 +129,7 @@ static int mg_build(ksfd_handle *h)
             L.f32 = true;
         }
     }
-    return KSFD_OK;
+    return mg_tail_replan(h);
 }
 
 // transfer operators for the storage types of the fine and the coarse vector.  fp64 on both sides: 1-D, 2-D or 3-D by the level geometry;
@@ -457,6 +485,54 @@ static int mg_coarse_sweeps(const ksfd_handle *h, const MGLevel &L)
     return std::min(std::max(sweeps, 4), h->mg_ncoarse);
 }
 
+// The tail of the cycle in ONE launch (k_mg_tail in mg.hip.h; ksfd_set_mg_tail): x = mg_vcycle<double>(t) b for the first tail level
+// t = h->mgt.level, b and x the fp64 vectors of that level (whole, no ghost units).  By-value level descriptors from what mg_setup_shift
+// left on the levels (dinv, lam_max, ratio) and the handle's smoothing parameters; one node of the captured graph on graph handles.
+// Booked under KC_MG with the bytes the launch moves through global memory: per level the coefficient planes and the fp32 blocks once,
+// plus b in and x out -- everything else stays in the LDS.
+static double mg_tail_bytes(const ksfd_handle *h)
+{
+    const int F = h->G.F;
+    double by = 0.0;
+    for (int q = 0; q < h->mgt.nlev; q++) by += (8.0 * (3 + h->P.nlig) + 4.0 * F * F) * (double)h->mg[h->mgt.level + q].G.nloc;
+    return by + 16.0 * F * (double)h->mg[h->mgt.level].G.nloc;
+}
+static int mg_tail_apply(ksfd_handle *h, double shift, const double *b, double *x)
+{
+    const MGTail &M = h->mgt;
+    if (M.level < 1 || M.nlev < 1 || M.nlev > ksfd_ctl::MG_TAIL_MAX_LEVELS || (size_t)(M.level + M.nlev) != mg_end(h) + 1)
+        return fail(h, KSFD_EINVAL, "mg_tail: this handle has no tail planned");
+    KMGTail T;
+    memset(&T, 0, sizeof T);
+    T.nlev = M.nlev; T.dim = h->G.dim; T.shift = shift;
+    long long lds = 0;
+    for (int q = 0; q < M.nlev; q++) {
+        const MGLevel &L = h->mg[M.level + q];
+        const bool last = q == M.nlev - 1;
+        // what the kernel's indexing rests on: a whole level with wrapped indices, few enough points for the threads' point loops
+        if (L.G.ng != 0 || L.G.plane != L.G.nloc || L.G.nloc > ksfd_ctl::mg_tail_max_points(L.G.F) || !L.coef || !L.dinv)
+            return fail(h, KSFD_EINVAL, "mg_tail: level %d is not a whole local level", M.level + q);
+        KMGTailLevel &D = T.L[q];
+        D.coef = L.coef; D.dinv = L.dinv;
+        D.n[0] = (int)L.G.nx; D.n[1] = L.G.dim >= 2 ? (int)L.G.ny : 1; D.n[2] = L.G.dim >= 3 ? (int)L.G.nz : 1;
+        D.np = (int)L.G.nloc;
+        if ((long long)D.n[0] * D.n[1] * D.n[2] != L.G.nloc) return fail(h, KSFD_EINVAL, "mg_tail: level %d: extents and point count disagree", M.level + q);
+        D.sweeps = last ? mg_coarse_sweeps(h, L) : h->mg_nu;
+        const MGCheb C = mg_cheb(L.lam_max, last ? L.ratio : h->mg_ratio);
+        D.theta = C.theta; D.delta = C.delta; D.sig1 = C.sig1; D.rho0 = C.rho0;
+        for (int a = 0; a < 3; a++) { D.inv_h[a] = L.P.inv_h[a]; D.inv_h2[a] = L.P.inv_h2[a]; }
+        lds += ksfd_ctl::mg_tail_level_bytes(L.G.nloc, L.G.F);
+    }
+    if (lds != M.lds || lds > ksfd_ctl::MG_TAIL_LDS_BUDGET) return fail(h, KSFD_EINVAL, "mg_tail: the levels need %lld bytes of LDS, the plan has %lld", lds, M.lds);
+    {
+        Scope sc(h, KC_MG, mg_tail_bytes(h));
+        NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_mg_tail<NL>), dim3(1), dim3(ksfd_ctl::MG_TAIL_THREADS), (size_t)lds, h->st, T, h->mg[M.level].P, b, x));
+    }
+    HIPCHK(h, hipGetLastError());
+    h->mgt.launches++;
+    return KSFD_OK;
+}
+
 // coarse-grid correction of level l, vectors stored in T and those of level l + 1 in TC: restrict r, recurse, prolong-add into x
 template <typename T, typename TC>
 static int mg_coarse_correction_in(ksfd_handle *h, size_t l, double shift, T *x)
@@ -473,7 +549,10 @@ static int mg_coarse_correction_in(ksfd_handle *h, size_t l, double shift, T *x)
         if ((rc = mg_launch_restrict(h, L, Lc, F, (const T *)V.r, Vc.b))) return rc;
     }
     if ((rc = mg_border_reduce(h, L, Lc, F, Vc.b))) return rc;
-    if ((rc = mg_vcycle<TC>(h, l + 1, shift, Vc.b, Vc.x))) return rc;
+    // the rest of the cycle in one launch where the tail begins (its levels are fp64: mg_f32)
+    if constexpr (std::is_same<TC, double>::value) rc = (int)l + 1 == h->mgt.level ? mg_tail_apply(h, shift, Vc.b, Vc.x) : mg_vcycle<TC>(h, l + 1, shift, Vc.b, Vc.x);
+    else rc = mg_vcycle<TC>(h, l + 1, shift, Vc.b, Vc.x);
+    if (rc) return rc;
     if ((rc = mg_halo(h, Lc, Vc.x, F))) return rc;                    // prolongation reads coarse row sloc_c
     {
         Scope sc(h, KC_MG, F * (2.0 * sf * L.G.nloc + sk * Lc.G.nloc));
@@ -502,6 +581,7 @@ static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool 
         hipGraph_t g = nullptr;
         const double b0 = h->bytes_acc;
         const int32_t s0 = h->mgc.solves;
+        const int64_t t0 = h->mgt.launches;
         HIPCHK(h, hipStreamBeginCapture(h->st, hipStreamCaptureModeThreadLocal));
         h->capturing = true;
         rc = body();
@@ -516,6 +596,8 @@ static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool 
         h->bytes_acc = b0;
         h->mgc.graph_solves = h->mgc.solves - s0;
         h->mgc.solves = s0;
+        h->mgt.graph_launches = h->mgt.launches - t0;
+        h->mgt.launches = t0;
         h->mg_graph_shift = shift;
         h->mg_graph_x = xkey;
         h->mg_graph_f32 = f32;
@@ -523,6 +605,7 @@ static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool 
     Scope sc(h, KC_MG, h->mg_graph_bytes);
     HIPCHK(h, hipGraphLaunch(h->mg_graph, h->st));
     h->mgc.solves += h->mgc.graph_solves;
+    h->mgt.launches += h->mgt.graph_launches;
     return KSFD_OK;
 }
 

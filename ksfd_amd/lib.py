@@ -79,6 +79,11 @@ class MGCoarseInfo(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class MGTailInfo(C.Structure):
+    _fields_ = [('level', C.c_int32), ('nlevels', C.c_int32), ('max_points', C.c_int64), ('points', C.c_int64 * 8),
+                ('lds_bytes', C.c_int64), ('launches', C.c_int64)]
+
+
 class MGLevelInfo(C.Structure):
     _fields_ = [('level', C.c_int32), ('nlevels', C.c_int32), ('end_level', C.c_int32), ('F', C.c_int32), ('n', C.c_int64 * 3),
                 ('sloc', C.c_int64), ('points', C.c_int64), ('path', C.c_int32), ('f32', C.c_int32), ('coef32', C.c_int32),
@@ -88,6 +93,7 @@ class MGLevelInfo(C.Structure):
 
 # parts of ksfd_mg_part (KSFD_MGP_*) and the kernel paths ksfd_mg_level_info reports
 MGP_COEF, MGP_RESTRICT, MGP_PROLONG_ADD, MGP_OPERATOR, MGP_DINV, MGP_DINV_APPLY, MGP_SMOOTH, MGP_CYCLE = range(8)
+MGP_TAIL = 8                                        # the coarse tail of set_mg_tail, at its first level
 MG_PATH_STRIP2D, MG_PATH_STRIP3D, MG_PATH_GENERIC = 0, 2, 3
 
 ROT_MAXIN, ROT_MAXOUT = 121, 18     # KSFD_ROT_MAXIN / KSFD_ROT_MAXOUT: limits of the basis rotation kernel
@@ -111,6 +117,7 @@ ABI_SYMBOLS = [
     'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply', 'ksfd_banded_apply',
     'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity', 'ksfd_krylov_op',
     'ksfd_set_mg_agglomerate', 'ksfd_set_mg_coarse', 'ksfd_get_mg_coarse_info', 'ksfd_mg_coarse_apply', 'ksfd_mg_level_info', 'ksfd_mg_part',
+    'ksfd_set_mg_tail', 'ksfd_get_mg_tail_info',
 ]
 
 
@@ -184,6 +191,8 @@ def load():
     L.ksfd_set_mg_coarse.argtypes = [vp, C.c_int32, C.c_int32]
     L.ksfd_set_mg_agglomerate.argtypes = [vp, C.c_int64]
     L.ksfd_get_mg_coarse_info.argtypes = [vp, C.POINTER(MGCoarseInfo)]
+    L.ksfd_set_mg_tail.argtypes = [vp, C.c_int64]
+    L.ksfd_get_mg_tail_info.argtypes = [vp, C.POINTER(MGTailInfo)]
     L.ksfd_mg_coarse_apply.argtypes = [vp, C.c_double, C.c_int32, dp, dp]
     L.ksfd_mg_level_info.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.POINTER(MGLevelInfo)]
     L.ksfd_mg_part.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp]
@@ -445,6 +454,22 @@ class KSFDHip:
         are replicated on every rank and coarsening goes on by the single-rank rule.  The hierarchy is rebuilt.  No effect on a handle
         without a halo transport; KSFDError(EINVAL) leaves the handle as it was."""
         self._chk(self.L.ksfd_set_mg_agglomerate(self.h, int(max_points)))
+
+    def set_mg_tail(self, max_points):
+        """The coarse tail of the multigrid V cycle in one workgroup launch (opt-in; collective on handles with a transport).  0: off, the
+        default.  > 0: the sub-cycle from the first level t >= 1 below which every level is whole on this rank, has at most that many
+        points and fits the LDS together, down to the level the cycle ends on and back, runs as ONE launch with the level vectors in
+        the LDS.  No level qualifies: the cycle stays as it is (mg_tail_info()['level'] == -1).  Excludes set_mg_coarse(1);
+        KSFDError(EINVAL) leaves the handle as it was.  Afterwards the hierarchy counts as not set up."""
+        self._chk(self.L.ksfd_set_mg_tail(self.h, int(max_points)))
+
+    def mg_tail_info(self):
+        """dict(level (first tail level or -1), nlevels, max_points, points (per tail level), lds_bytes, launches (over the life of the
+        handle))"""
+        s = MGTailInfo()
+        self._chk(self.L.ksfd_get_mg_tail_info(self.h, C.byref(s)))
+        return dict(level=s.level, nlevels=s.nlevels, max_points=int(s.max_points), points=[int(x) for x in s.points[:s.nlevels]],
+                    lds_bytes=int(s.lds_bytes), launches=int(s.launches))
 
     def mg_coarse_info(self):
         """the level the V cycle ends on and the counters of the exact coarse solve over the life of the handle:

@@ -426,6 +426,23 @@ def mg_agglomerate_from(petsc_args):
     return pts
 
 
+def mg_tail_from(petsc_args):
+    """max_points for KSFDHip.set_mg_tail from -ksfd_mg_tail <points> (0 = off: the coarse tail of the V cycle stays the launches it
+    is), or None when the list does not name the flag (the handle is left alone)."""
+    a = list(petsc_args)
+    pts = None
+    for i, k in enumerate(a):
+        if k == '-ksfd_mg_tail':
+            nxt = a[i + 1] if i + 1 < len(a) else None
+            try:
+                pts = int(nxt)
+            except (TypeError, ValueError):
+                pts = -1
+            if not 0 <= pts < 2 ** 63:
+                raise ValueError('-ksfd_mg_tail must be a non-negative integer number of points, got %s' % nxt)
+    return pts
+
+
 def _isnum(s):
     try:
         float(s.split(',')[0])

@@ -121,7 +121,8 @@ def main(*args):
     ts = implicitTS(derivs, t0=t_start, dt=dt0, tmax=float(v['tmax']),
                     maxsteps=0 if cl.onestep else int(v['maxsteps']), rtol=float(v['rtol']), atol=float(v['atol']),
                     opts=opt.step_opts_from(ps, cl.petsc), rng=rng, deflation=opt.deflation_from(cl.petsc),
-                    mg_coarse=opt.mg_coarse_from(cl.petsc), mg_agglomerate=opt.mg_agglomerate_from(cl.petsc))
+                    mg_coarse=opt.mg_coarse_from(cl.petsc), mg_agglomerate=opt.mg_agglomerate_from(cl.petsc),
+                    mg_tail=opt.mg_tail_from(cl.petsc))
     ts.setMonitor(ts.printMonitor)
     tseries = None
     if cl.save:

@@ -188,7 +188,7 @@ class KSFDTS:
     default_hmin = 1e-20
 
     def __init__(self, derivs, t0=0.0, dt=0.001, tmax=20, maxsteps=100, rtol=1e-5, atol=1e-5, restart=True,
-                 hmin=None, comm=None, opts=None, rng=None, deflation=None, mg_coarse=None, mg_agglomerate=None):
+                 hmin=None, comm=None, opts=None, rng=None, deflation=None, mg_coarse=None, mg_agglomerate=None, mg_tail=None):
         self.derivs = derivs
         self.ks = derivs.ks
         self.comm = comm if comm is not None else derivs.grid.comm
@@ -204,6 +204,8 @@ class KSFDTS:
             self.ks.set_mg_agglomerate(mg_agglomerate)
         if mg_coarse is not None:                   # (kind, max_unknowns) of -ksfd_mg_coarse: ksfd_amd.options.mg_coarse_from
             self.ks.set_mg_coarse(*mg_coarse)
+        if mg_tail is not None:                     # max_points of -ksfd_mg_tail (after the hierarchy has its replicated levels): ksfd_amd.options.mg_tail_from
+            self.ks.set_mg_tail(mg_tail)
         self.history = []
         self.u = derivs.u0
         self._t, self._h, self._k = self.t0, float(dt), 0
