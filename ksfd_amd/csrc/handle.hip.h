@@ -2,6 +2,7 @@
 // (part of the single translation unit ksfd_hip.hip, first of its host-side headers: the include list there gives the order)
 #pragma once
 #include "spectral_plan.h"
+#include "handle_state.h"
 // ------------------------------------------------------------------------------------------------
 // kernel classes for the profile
 enum { KC_RHS = 0, KC_JVP, KC_MULTIDOT, KC_GSUPDATE, KC_LINCOMB, KC_BASISAXPY, KC_FINISH, KC_REDUCE,
@@ -43,7 +44,7 @@ struct MGLevel {
 
 // spectral preconditioner (spectral.hip.h / spectral_plan.h / spectral_host.hip.h): what spec_build makes of the planner's shape
 struct SpecState {
-    bool ok = false, means_valid = false;
+    bool ok = false;
     SpecShape shape;
     // work arrays W: [pair][pos_x][y_local]; W2: after the all-to-all, [rank][pair][own pos][y_local] (nch = 3: [chunk] in front of [pair] in both)
     kcf *W = nullptr, *W2 = nullptr, *twx = nullptr, *twy = nullptr, *twz = nullptr;
@@ -74,7 +75,8 @@ struct LUState {
     double *val = nullptr;
     double *y = nullptr, *z = nullptr;       // triangular-solve work vectors
     std::vector<int> piv_h, perm_h;
-    bool valid = false;                      // A holds the factors of shift*I - J at the resident coefficient planes
+    bool valid = false;                      // a factorization exists: A holds the factors of shift*I - J for `shift`, at the planes as they were when
+                                             // it was made (every step attempt and every apply entry factors before it solves; nothing ends this)
     double shift = 0.0;
 };
 
@@ -87,7 +89,6 @@ struct MGCoarse {
     int level = -1;                          // level the cycle ends on (mg_build: the coarsest)
     LUState lu;                              // shift*I - J_c and its factors
     double *inv = nullptr;                   // (shift*I - J_c)^-1, row-major
-    bool ready = false;                      // inv belongs to the set-up in force (false: that set-up fell back to Chebyshev)
     int info_h = 0;
     int32_t factorizations = 0, solves = 0, fallbacks = 0;
     int32_t graph_solves = 0;                // coarse solves inside the captured part of the cycle, counted at every replay
@@ -115,7 +116,7 @@ struct BandState {
     double *val = nullptr;
     double *z = nullptr;                     // L^-1 P b between the two sweeps of a solve
     int threads = 0;                         // workgroup of k_band_factor (64 or 256)
-    bool valid = false;
+    bool valid = false;                      // a factorization exists (as LUState::valid)
     double shift = 0.0;
 };
 
@@ -165,13 +166,9 @@ struct ksfd_handle {
     double *Gb = nullptr, *dGb = nullptr;   // generic-path scratch planes
     double *coef = nullptr;                 // frozen-Jacobian coefficient planes [rho, G, G_rho, G_U..]
     bool use_frozen = true;
-    bool coef_fresh = false;                // coef belongs to the resident state u as it is now (ensure_coef)
-    bool coef32_fresh = false;              // coef32 is the rounded copy of coef as it is now (ensure_coef32; cleared by whatever writes coef)
-    bool floor_ok = false;                  // every owned value of u is at or above its floor (rhomin / Umin): k_groom would store what it loads.
-                                            // True after a groom and after an accepted completion that counted no value below; false after everything
-                                            // else that writes u or moves the floors
-    bool ckpt_floor_ok = false;             // ... of the state in the checkpoint slot
-    bool err_pending = false;               // errv has not been formed yet: it is sum (b2t_j - bt_j) Y_j of the stage vectors still in Y (err_materialize)
+    // which of the derived data below still belongs to the state and the configuration as they are now: handle_state.h, whose events
+    // are the only writers
+    ksfd_ctl::Current cur;
     bool old_boundary = false;              // KSFD_TUNE bit 22: groom every step, error vector stored by the completion, fp32 coefficient copy made by k_jcoef
     bool rhs_gplane = true;                 // stage-0 RHS of the 2-D strip path takes G from plane 1 of coef (KSFD_TUNE bit 23 clears)
     double *flat = nullptr;                 // staging for host layouts: max(F,dim)*nloc
@@ -187,7 +184,6 @@ struct ksfd_handle {
     int restart_alloc = 0;                  // basis vectors V / Zb hold (ksfd_create: 30 ... 120 by the free HBM)
     bool restart_grow = true;               // a GMRES cycle that ends without convergence is followed by one of twice the length (KSFD_TUNE bit 17 switches it off)
     int nblk_vec = 0;                       // grid.x of the BLAS-1 kernels
-    bool have_err = false;
 
     // tuning
     int use_fused = 1;
@@ -215,7 +211,6 @@ struct ksfd_handle {
     double *pvec = nullptr;         // power-iteration vector for lambda_max(A)
     int poly_deg = 0;
     double poly_alpha[8];           // z = sum_i alpha_i (A/shift)^i v
-    double poly_shift = -1.0;
     int poly_max_deg = 6;
     double mg_threshold = 75.0;      // stiffness above which pc_type 2 switches from the polynomial to multigrid
     double poly_target = 0.02;      // wanted reduction per outer iteration (picks the degree)
@@ -235,9 +230,8 @@ struct ksfd_handle {
     int snap_next = 0;
 
     // Krylov recycling across the four stage systems of one step (same matrix): see gmres()
-    struct RecSpace { bool valid = false; int vb = 0, zb = 0, k = 0, pc = 0; std::vector<double> H; };   // leading (k+1) x k raw Hessenberg, ld = k+1
+    struct RecSpace { int vb = 0, zb = 0, k = 0, pc = 0; std::vector<double> H; };   // leading (k+1) x k raw Hessenberg, ld = k+1; in force while cur.rec_valid[stage]
     RecSpace rec[4];
-    int rec_vtop = 0, rec_ztop = 0;  // first free slot of V / Zb behind the kept vectors
     int rec_mode = 1;                // 0 off, 1 selected earlier stages (default), 2 every earlier stage
     int rec_keep = 3;                // leading vectors kept per stage (<= 4)
     bool rhs_dots = true;            // inner products for the stage guesses from the RHS kernel's store epilogue (KSFD_TUNE bit 21 clears)
@@ -247,8 +241,8 @@ struct ksfd_handle {
     int dr_keep = 0;                 // harmonic Ritz vectors kept across a restart (1..16)
     bool dr_carry = false;           // the kept relation also serves the later stage systems of a step attempt
     double *dr_P = nullptr, *dr_Phost = nullptr;      // rotation matrix of op_basis_rotate: device copy and pinned staging (KSFD_ROT_MAXIN x KSFD_ROT_MAXOUT)
-    // A M^-1 V_kk = V_kk+1 H (H (kk+1) x kk column-major) in the leading slots of V (and Zb): valid for this matrix, shift and preconditioner only
-    struct DrKept { bool valid = false; int kk = 0, pc = -1; double shift = 0.0, shift_pc = 0.0; std::vector<double> H; };
+    // A M^-1 V_kk = V_kk+1 H (H (kk+1) x kk column-major) in the leading slots of V (and Zb) while cur.dr_valid: for this matrix, shift and preconditioner only
+    struct DrKept { int kk = 0, pc = -1; double shift = 0.0, shift_pc = 0.0; std::vector<double> H; };
     DrKept dr;
     ksfd_deflation_stats dr_stats = {};
 
@@ -262,16 +256,12 @@ struct ksfd_handle {
     bool sf_auto = true;         // online search for memo.mg_shift_floor (shift_floor_update); KSFD_PC_SIGMA fixes the floor instead
     bool mg_fp32 = true;         // V cycle with fp32 level vectors when the solve tolerance allows (KSFD_TUNE bit 19 clears); see mg_vcycle
     bool mg_use32 = false;       // ... decided per step by ksfd_step (ksp_rtol >= 1e-7)
-    bool mg_graph_f32 = false;   // precision the captured coarse cycle was recorded in
     bool mg_warm_power = true;   // power iteration of a level starts from the vector of the previous set-up (KSFD_TUNE bit 18 clears)
     bool mg_fuse = true;         // smoother algebra inside the Jacobian-action epilogues (modes 5/6)
     bool mg_ok = false;          // hierarchy exists (2-D, single rank, >= 2 levels)
-    double mg_shift = -1.0;      // shift the block diagonals / eigen-bounds were built for
-    bool mg_coef_valid = false;  // coarse coefficient planes match the current frozen state
     int64_t mg_agg = 0;          // slab ranks: 0 = every level distributed; > 0: coarse levels replicated (mg_agglomerate_plan.h)
-    hipGraphExec_t mg_graph = nullptr;   // captured coarse part of the V cycle (levels >= 1) for mg_graph_shift/x
-    double mg_graph_shift = -1.0, mg_graph_bytes = 0.0;
-    const void *mg_graph_x = nullptr;
+    hipGraphExec_t mg_graph = nullptr;   // captured coarse part of the V cycle (levels >= 1) under the key in cur (graph_current)
+    double mg_graph_bytes = 0.0;
     bool capturing = false, mg_use_graph = true;
     int mg_nu = 2, mg_ncoarse = 400, mg_power_its = 8;   // smoothing sweeps, cap on coarsest-grid sweeps, power iterations
     double mg_ratio = 6.0, mg_coarse_tol = 0.3;    // coarsest-grid reduction target: 0.3 is enough (tools/mg_longrun_tune.py: 24.3 -> 19.9 ms/step at 384^2, same iterations)

@@ -42,7 +42,7 @@ static int est_lambda_max(ksfd_handle *h, double shift, int nits)
 // coefficients of p for this shift (ksfd_krylov::cheb_setup); degree 0 = "do not precondition"
 static void poly_setup(ksfd_handle *h, double shift)
 {
-    h->poly_shift = shift;
+    ksfd_ctl::poly_set_up(h->cur, shift);
     h->poly_deg = ksfd_krylov::cheb_setup(h->memo.lamJ, shift, h->poly_target, h->poly_max_deg, h->poly_alpha);
 }
 
@@ -91,12 +91,6 @@ static int poly_apply(ksfd_handle *h, double shift, double *v, double *z)
 // The small host algebra (Hessenberg QR, algebraic second projection, recycling and cycle-length rules) is in krylov_small.h.
 // ------------------------------------------------------------------------------------------------
 struct LinStats { int its; double rel; };
-
-static void rec_reset(ksfd_handle *h)
-{
-    for (auto &r : h->rec) r.valid = false;
-    h->rec_vtop = h->rec_ztop = 0;
-}
 
 // A right-hand side of norm bn with nothing to iterate on: zero (x = 0 is the solution) or not finite (nan_msg: the solver's own error
 // text).  *empty: the solver returns what this returns.
@@ -193,7 +187,7 @@ static int rhs_norm(ksfd_handle *h, GmresRun &R, const double *b)
     int rc;
     if (R.rec_on && R.stage > 0)
         for (int q = 0; q < R.stage; q++)
-            if (ksfd_krylov::recycle_uses(R.stage, q, h->rec_mode, R.rec_full) && h->rec[q].valid && h->rec[q].pc == R.pcmode) R.spaces.push_back(q);
+            if (ksfd_krylov::recycle_uses(R.stage, q, h->rec_mode, R.rec_full) && h->cur.rec_valid[q] && h->rec[q].pc == R.pcmode) R.spaces.push_back(q);
     if (R.spaces.empty()) {
         if ((rc = op_multidot(h, b, R.V, 0))) return rc;
         R.bn = sqrt(h->hres[0]);
@@ -301,9 +295,7 @@ static void recycle_keep(ksfd_handle *h, const GmresRun &R, int j, const double 
     S.H.assign((size_t)(S.k + 1) * S.k, 0.0);
     for (int c = 0; c < S.k; c++)
         for (int i = 0; i <= S.k; i++) S.H[c * (S.k + 1) + i] = Hraw[(size_t)ld * c + i];
-    S.valid = true;
-    h->rec_vtop = R.vb + S.k + 1;
-    h->rec_ztop = R.zb + (R.use_poly ? S.k : 0);
+    ksfd_ctl::recycled_space_kept(h->cur, R.stage, R.vb + S.k + 1, R.zb + (R.use_poly ? S.k : 0));
 }
 
 // resolve, project on the kept spaces (recycle_project), then per cycle { start vector, per column { w = A M^-1 v_j, orthogonalise,
@@ -316,7 +308,6 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
     GmresRun R;
     R.pcmode = pcmode; R.stage = stage;
     R.use_pc = pcmode == 1;
-    h->dr.valid = false;                   // this solve builds in V: a relation kept by the deflated solver (krylov_dr.hip.h) is gone
     // the hierarchy may be built for a LARGER shift than the system's (h->memo.mg_shift_floor): when 1/(gamma h) falls below the growth
     // rate of the chemotactic instability, shift*I - J is indefinite and a V cycle of it is no contraction; the V cycle of the
     // positively shifted operator still is, and GMRES (true residual of the real system) takes care of the difference
@@ -325,10 +316,11 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
     const int m_opt = std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc);
     const int maxit = o->ksp_max_it > 0 ? o->ksp_max_it : 2000;
     const int64_t vs = h->vlen;
-    const ksfd_krylov::RecycleChoice rcy = ksfd_krylov::recycle_decide(pcmode, stage, h->rec_mode, h->rec_mg, h->use_frozen, h->restart_alloc, h->rec_vtop);
-    if (rcy.reset) rec_reset(h);
+    const ksfd_krylov::RecycleChoice rcy = ksfd_krylov::recycle_decide(pcmode, stage, h->rec_mode, h->rec_mg, h->use_frozen, h->restart_alloc, h->cur.rec_vtop);
+    // this solve builds in V: a relation kept by the deflated solver (krylov_dr.hip.h) is gone, the recycled spaces unless it builds behind them
+    ksfd_ctl::krylov_basis_overwritten(h->cur, !rcy.reset);
     R.rec_on = rcy.rec_on; R.rec_full = rcy.rec_full;
-    R.vb = R.rec_on ? h->rec_vtop : 0; R.zb = R.rec_on ? h->rec_ztop : 0;
+    R.vb = R.rec_on ? h->cur.rec_vtop : 0; R.zb = R.rec_on ? h->cur.rec_ztop : 0;
     // restart length: ksfd_krylov::cycle_first / cycle_next.  Host arrays are sized for the longest cycle.
     const int m = ksfd_krylov::cycle_room(h->restart_alloc, R.vb);
     int m_cur = ksfd_krylov::cycle_first(m_opt, m, R.rec_on, R.rec_full);
@@ -433,7 +425,7 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
 {
     int rc;
     ls->its = 0; ls->rel = 0.0;
-    rec_reset(h);
+    ksfd_ctl::recycled_spaces_dropped(h->cur);
     if (bnorm2 < 0.0) {
         if ((rc = op_multidot(h, b, b, 0))) return rc;
         bnorm2 = h->hres[0];
@@ -538,7 +530,7 @@ static void launch_gs_update_dev(ksfd_handle *h, double *w, const double *V, int
 
 static int gmres_async(ksfd_handle *h, double shift, const double *b, double *x, const ksfd_step_opts *o, LinStats *ls)
 {
-    rec_reset(h);
+    ksfd_ctl::recycled_spaces_dropped(h->cur);
     // Cycle length: what the kernels of an iteration hold, whatever the basis has room for.  k_multidot_gram / k_gs_update_dev stop at the
     // top of the KB ladder (32 vectors), k_gmres_coef keeps its coefficients in KSFD_MAXDOT slots: a longer ksp_restart runs as cycles of
     // KSFD_ASYNC_MAXK (gmres() goes on classically and in chunks beyond that length; there is no such path here).

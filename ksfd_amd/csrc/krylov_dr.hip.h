@@ -46,7 +46,6 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     ksfd_handle::DrKept &K = h->dr;
     ksfd_deflation_stats &S = h->dr_stats;
     int rc;
-    rec_reset(h);
     ls->its = 0; ls->rel = 0.0;
     if (keep < 1 || keep > m - 3) return fail(h, KSFD_EINVAL, "deflation: keep = %d needs 1 <= keep <= restart - 3 = %d", keep, m - 3);
     const int ld = m + 1;                                  // rows of Hb
@@ -54,11 +53,11 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     std::vector<double> Hb((size_t)ld * m, 0.0), c(ld, 0.0), y(m, 0.0), rho(ld, 0.0), hcol(ld + 1, 0.0), dcol(ld + 1, 0.0);
     const int e = 1;                                       // trailing vectors of the relation (dense_small.h handles more; this solver never has them)
     int kk = 0;                                            // the relation in front of the basis: kk columns, kk + 1 vectors
-    if (K.valid && h->dr_carry && stage > 0 && stage < 4 && K.pc == pcmode && K.shift == shift && K.shift_pc == shift_pc && K.kk >= 1 && K.kk + 1 <= m) {
+    if (h->cur.dr_valid && h->dr_carry && stage > 0 && stage < 4 && K.pc == pcmode && K.shift == shift && K.shift_pc == shift_pc && K.kk >= 1 && K.kk + 1 <= m) {
         kk = K.kk;
         for (int j = 0; j < kk; j++) for (int i = 0; i < kk + e; i++) Hb[(size_t)j * ld + i] = K.H[(size_t)j * (kk + e) + i];
     }
-    K.valid = false;                                       // V is about to change; set again where a relation is left behind
+    ksfd_ctl::krylov_basis_overwritten(h->cur);            // V is about to change; dr_relation_kept where a relation is left behind
 
     auto true_residual = [&](double *r) -> int {           // r = b - A x
         int q;
@@ -228,7 +227,8 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     ls->rel = rn / rel_den;
     if (!accepted) return fail(h, KSFD_ELINEAR, "GMRES-DR did not converge: %d iterations, true relative residual %.3e (tol %.3e)", total, rn / bn, tol / bn);
     if (kk >= 1) {
-        K.valid = true; K.kk = kk; K.pc = pcmode; K.shift = shift; K.shift_pc = shift_pc;
+        ksfd_ctl::dr_relation_kept(h->cur);
+        K.kk = kk; K.pc = pcmode; K.shift = shift; K.shift_pc = shift_pc;
         K.H.assign((size_t)(kk + e) * kk, 0.0);
         for (int j = 0; j < kk; j++) for (int i = 0; i < kk + e; i++) K.H[(size_t)j * (kk + e) + i] = Hb[(size_t)j * ld + i];
     }

@@ -1,6 +1,7 @@
 // libksfd_hip.so -- C ABI (include/ksfd_hip.h) and the attempt loop of the Rosenbrock-W step (ksfd_step); handle, launch wrappers,
 // multigrid and Krylov solvers live in handle.hip.h / ops.hip.h / mg_host.hip.h / krylov.hip.h, the parts of a step attempt in
-// step.hip.h (one translation unit), the step's decisions and its step-to-step memory (StepMemo) as plain C++ in step_control.h.
+// step.hip.h (one translation unit), the step's decisions and its step-to-step memory (StepMemo) as plain C++ in step_control.h, the
+// record of which derived data is current (h->cur) and the events that write it in handle_state.h.
 // Together they stand in for petsc4py TS.step() in the reference (KSFD/ksfdts.py:211).
 // gfx950 only.  No CPU fallback: every entry point runs HIP kernels or fails.
 #include <hip/hip_runtime.h>
@@ -238,8 +239,7 @@ extern "C" int ksfd_update_params(ksfd_handle *h, const ksfd_config *cfg)
     h->cfg = *cfg;
     h->cfg.lig_group = nullptr; h->cfg.lig_w = h->cfg.lig_s = h->cfg.lig_gamma = h->cfg.lig_D = nullptr;
     h->cfg.grp_alpha = h->cfg.grp_beta = nullptr;
-    h->coef_fresh = false;                                   // G, G_rho, G_U depend on the parameters
-    h->floor_ok = h->ckpt_floor_ok = false;                  // rhomin / Umin may have moved: under the state and under the one in the checkpoint slot
+    ksfd_ctl::params_changed(h->cur);
     return fill_phys(h, cfg);
 }
 
@@ -269,9 +269,9 @@ extern "C" int ksfd_local_range(const ksfd_handle *h, int64_t *b, int64_t *e)
     return KSFD_OK;
 }
 extern "C" int64_t ksfd_local_size(const ksfd_handle *h) { return h ? (int64_t)h->G.F * h->G.nloc : 0; }
-// the pointer is good until the next ksfd_step (an accepted step moves the state to the handle's other buffer); handing it out ends what
-// the handle knows about the values it points at
-extern "C" double *ksfd_device_state(ksfd_handle *h) { if (h) h->floor_ok = false; return h ? h->u : nullptr; }
+// the pointer is good until the next ksfd_step (an accepted step moves the state to the handle's other buffer); handing it out ends the
+// floor proof of the values it points at, and only that (handle_state.h: state_handed_out)
+extern "C" double *ksfd_device_state(ksfd_handle *h) { if (h) ksfd_ctl::state_handed_out(h->cur); return h ? h->u : nullptr; }
 extern "C" int64_t ksfd_device_plane_stride(const ksfd_handle *h) { return h ? h->G.plane : 0; }
 extern "C" int64_t ksfd_device_interior_offset(const ksfd_handle *h) { return h ? (int64_t)h->G.ng * h->G.inner : 0; }
 
@@ -280,8 +280,7 @@ extern "C" int ksfd_set_state(ksfd_handle *h, const double *u, int32_t layout)
     if (!h || !u) return KSFD_EINVAL;
     hipSetDevice(h->device);
     int rc = upload(h, u, layout, h->u);
-    h->coef_fresh = false;
-    h->floor_ok = false;
+    ksfd_ctl::state_written(h->cur);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->st));
     return KSFD_OK;
@@ -339,25 +338,20 @@ extern "C" int ksfd_checkpoint(ksfd_handle *h, int32_t op)
 {
     if (!h || op < 0 || op > 1) return KSFD_EINVAL;
     hipSetDevice(h->device);
-    h->dr.valid = false;                                 // a kept Krylov relation never crosses a save or a restore: replays stay bitwise
     if (op == 0) {
         if (!h->ckpt && alloc_d(h, &h->ckpt, h->vlen)) return KSFD_ENOMEM;
         HIPCHK(h, hipMemcpyAsync(h->ckpt, h->u, sizeof(double) * (size_t)h->vlen, hipMemcpyDeviceToDevice, h->st));
         h->ckpt_memo = h->memo;
-        h->ckpt_floor_ok = h->floor_ok;                  // a property of the state being copied
-        for (MGLevel &L : h->mg) L.pv_norm = 0.0;       // the step after a save and the step after a restore both set the hierarchy up cold
+        ksfd_ctl::checkpoint_saved(h->cur);
+        mg_setup_cold(h);                                // the step after a save and the step after a restore both set the hierarchy up cold: replays stay bitwise
         h->ckpt_valid = true;
         return KSFD_OK;
     }
     if (!h->ckpt_valid) return fail(h, KSFD_EINVAL, "no checkpoint has been saved");
     HIPCHK(h, hipMemcpyAsync(h->u, h->ckpt, sizeof(double) * (size_t)h->vlen, hipMemcpyDeviceToDevice, h->st));
-    h->coef_fresh = false;
-    h->floor_ok = h->ckpt_floor_ok;
     h->memo = h->ckpt_memo;
-    h->spec.means_valid = false;
-    h->mg_coef_valid = false; h->mg_shift = -1.0; h->poly_shift = -1.0; h->have_err = false; h->err_pending = false;
-    for (MGLevel &L : h->mg) L.pv_norm = 0.0;
-    rec_reset(h);
+    ksfd_ctl::checkpoint_restored(h->cur);
+    mg_setup_cold(h);
     return KSFD_OK;
 }
 
@@ -371,8 +365,7 @@ extern "C" int ksfd_set_state_random(ksfd_handle *h, const int64_t *nc, const do
         n *= nc[a];
     }
     double *dz = nullptr;
-    h->coef_fresh = false;
-    h->floor_ok = false;
+    ksfd_ctl::state_written(h->cur);
     if (hipMalloc((void **)&dz, sizeof(double) * (size_t)n) != hipSuccess) return fail(h, KSFD_ENOMEM, "hipMalloc of the coarse samples failed");
     hipError_t e = hipMemcpyAsync(dz, z, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->st);
     const KGeom &G = h->G;
@@ -513,7 +506,7 @@ extern "C" int ksfd_groom(ksfd_handle *h)
     Scope sc(h, KC_MISC, vbytes(h, 2));
     hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin);
     HIPCHK(h, hipGetLastError());
-    h->floor_ok = true;
+    ksfd_ctl::state_groomed(h->cur);
     return KSFD_OK;
 }
 
@@ -536,8 +529,7 @@ extern "C" int ksfd_scale_rho(ksfd_handle *h, double factor)
 {
     if (!h) return KSFD_EINVAL;
     hipSetDevice(h->device);
-    h->coef_fresh = false;
-    h->floor_ok = false;
+    ksfd_ctl::state_written(h->cur);
     Scope sc(h, KC_MISC, 16.0 * (double)h->G.nloc);
     hipLaunchKernelGGL(k_mul_rho, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, (const double *)nullptr, factor);
     HIPCHK(h, hipGetLastError());
@@ -549,8 +541,7 @@ extern "C" int ksfd_mul_rho(ksfd_handle *h, const double *fh)
     if (!h || !fh) return KSFD_EINVAL;
     hipSetDevice(h->device);
     HIPCHK(h, hipMemcpyAsync(h->flat, fh, sizeof(double) * (size_t)h->G.nloc, hipMemcpyHostToDevice, h->st));
-    h->coef_fresh = false;
-    h->floor_ok = false;
+    ksfd_ctl::state_written(h->cur);
     Scope sc(h, KC_MISC, 24.0 * (double)h->G.nloc);
     hipLaunchKernelGGL(k_mul_rho, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, (const double *)h->flat, 1.0);
     HIPCHK(h, hipGetLastError());
@@ -639,17 +630,17 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
     const int max_rej = opts->max_reject < 0 ? 0x7fffffff : opts->max_reject;      // PETSc: -ts_max_reject -1 = unlimited
     const bool single = (opts->reserved & 2) != 0;                                   // one attempt per call (the caller owns the reject loop)
     // KSFDTS.solve grooms the global vector before every TS.step (KSFD/ksfdts.py:210)
-    // floor_ok: every owned value is at or above its floor already (the last completion counted none below and nothing has written u or
-    // moved the floors since), so the groom would store the bits it loads and is left out
-    if (!h->floor_ok || h->old_boundary) {
+    // cur.floor_ok: every owned value is at or above its floor already (the last completion counted none below and nothing has written u
+    // or moved the floors since), so the groom would store the bits it loads and is left out
+    if (!h->cur.floor_ok || h->old_boundary) {
         Scope sc(h, KC_MISC, vbytes(h, 2));
         hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin);
         if (hipGetLastError() != hipSuccess) return fail(h, KSFD_EHIP, "k_groom launch failed");
-        h->floor_ok = true;
+        ksfd_ctl::state_groomed(h->cur);
     }
     if ((rc = halo(h, h->u))) return rc;
     if (h->use_frozen && (rc = ensure_coef(h, true))) return rc;      // usually already there: the CFL check after the last step made them
-    h->poly_shift = -1.0;
+    ksfd_ctl::step_begins(h->cur);
     m.nsteps++;
     ksfd_ctl::spec_rho_roll(m);                      // contraction memory of the spectral sweeps
     while (true) {
@@ -657,9 +648,7 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
         if ((rc = plan_attempt(h, opts, hh, direct, dr_on, lam_done, p))) return rc;
         const int its_before = st.linear_its;
         bool spec_failed = false;
-        // the stage solves overwrite Y: an error vector nobody has asked for goes with it, and the query has nothing to return until the
-        // next completion (it fails instead of returning the vector of an older attempt)
-        if (h->err_pending) { h->err_pending = false; h->have_err = false; }
+        ksfd_ctl::attempt_begins(h->cur);
         rc = step_attempt(h, opts, p, spec_failed, st);
         const int its = st.linear_its - its_before;
         if (p.use_spec && opts->pc_type == 2) ksfd_ctl::spec_backoff_update(m, spec_failed, its, m.nsteps);
@@ -687,8 +676,7 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
         prev_accept = next.accept;
         if (next.accept) {
             std::swap(h->u, h->usave);                               // the new state; its ghost rows are stale until the next halo exchange
-            h->coef_fresh = false;
-            h->floor_ok = below == 0.0;
+            ksfd_ctl::state_written(h->cur, below == 0.0);
             st.accepted = 1; st.h_used = hh;
             *t += hh;
             *hstep = next.hnext;
@@ -737,7 +725,7 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
 extern "C" int ksfd_get_last_error_vector(ksfd_handle *h, double *eh, int32_t layout)
 {
     if (!h || !eh) return KSFD_EINVAL;
-    if (!h->have_err) return fail(h, KSFD_EINVAL, "no step has been attempted yet");
+    if (!h->cur.have_err) return fail(h, KSFD_EINVAL, "no step has been attempted yet");
     hipSetDevice(h->device);
     int rc = err_materialize(h);
     if (rc) return rc;
@@ -770,7 +758,7 @@ extern "C" int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_ma
     if (ratio > 1.0) h->mg_ratio = ratio;
     if (coarse_tol > 0.0) h->mg_coarse_tol = coarse_tol;
     h->mg_use_graph = power_its != -7 && !h->ring;     // power_its = -7: eager launches (debug / A-B timing); slab ranks: collectives inside the cycle
-    h->mg_shift = -1.0;
+    ksfd_ctl::vcycle_config_changed(h->cur);
     return KSFD_OK;
 }
 // level the cycle would end on for (kind, max_unknowns), or -1 (mg_coarse_plan.h)
@@ -800,9 +788,7 @@ extern "C" int ksfd_set_mg_coarse(ksfd_handle *h, int32_t kind, int32_t max_unkn
     if (kind == 1) { int rc = mgc_alloc(h, level); if (rc) return rc; }      // before anything changes
     if (kind == h->mgc.kind && level == h->mgc.level) { h->mgc.max_unknowns = kind == 1 ? max_unknowns : 0; return KSFD_OK; }
     h->mgc.kind = kind; h->mgc.level = level; h->mgc.max_unknowns = kind == 1 ? max_unknowns : 0;
-    h->mgc.ready = false;
-    h->mg_shift = -1.0;                                  // the next V cycle sets the hierarchy up again, and with it captures its graph again
-    if (h->mg_graph) { HIPCHK(h, hipStreamSynchronize(h->st)); hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
+    ksfd_ctl::vcycle_config_changed(h->cur);             // the next V cycle sets the hierarchy up again, and with it captures its graph again
     return KSFD_OK;
 }
 extern "C" int ksfd_set_mg_agglomerate(ksfd_handle *h, int64_t max_points)
@@ -823,8 +809,6 @@ extern "C" int ksfd_set_mg_agglomerate(ksfd_handle *h, int64_t max_points)
     auto rebuild = [&](int64_t agg) -> int {
         mg_free(h);
         h->mg_agg = agg;
-        h->mg_coef_valid = false; h->mg_shift = -1.0; h->mg_graph_shift = -1.0;
-        h->dr.valid = false;                             // the recycled subspace belongs to the preconditioner that is gone
         own_rc = mg_build(h);
         own_err = h->err;
         if (!own_rc && !h->mg_ok) own_rc = fail(h, KSFD_EINVAL, "mg_agglomerate: the rebuilt hierarchy has fewer than two levels"), own_err = h->err;
@@ -871,7 +855,7 @@ extern "C" int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, co
     hipSetDevice(h->device);
     int rc;
     if ((rc = ensure_coef(h))) return rc;
-    if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
+    if (!h->cur.mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
     MGLevel &L = h->mg[mg_end(h)];                        // never level 0: b and x are the level's own
     double *const lb = L.v64.b, *const lx = L.v64.x;
     const size_t nb = sizeof(double) * (size_t)L.G.nloc;
@@ -880,11 +864,11 @@ extern "C" int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, co
     if (op == 0) rc = mg_op<double>(h, L, lb, 1, shift, lx, nullptr);
     else {
         bool ok = false;
-        h->mg_shift = -1.0;                              // the coarse factors now belong to this shift: the next cycle sets up again
+        ksfd_ctl::hierarchy_borrowed(h->cur);            // the coarse factors now belong to this shift: the next cycle sets up again
         if ((rc = mgc_setup(h, L, shift, &ok))) return rc;
         if (!ok) return fail(h, KSFD_ELINEAR, "coarse solve: zero or non-finite pivot in column %d of shift*I - J_c (shift %.6g, %lld unknowns)", h->mgc.info_h - 1, shift, (long long)h->mgc.lu.n);
         rc = mgc_apply(h, L, lb, lx);
-        h->mgc.ready = false;
+        ksfd_ctl::hierarchy_borrowed(h->cur);
     }
     if (rc) return rc;
     for (int f = 0; f < L.G.F; f++)
@@ -921,10 +905,10 @@ static int mgp_begin(ksfd_handle *h, bool setup, double shift)
 {
     int rc;
     if ((rc = ensure_coef(h)) || (rc = ensure_coef32(h))) return rc;      // level 0 reads the fp32 copy of the planes where the handle has one (mg_sys)
-    if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
+    if (!h->cur.mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
     if (setup) {
-        for (MGLevel &L : h->mg) L.pv_norm = 0.0;
-        h->mg_shift = -1.0;
+        mg_setup_cold(h);
+        ksfd_ctl::hierarchy_borrowed(h->cur);
         if ((rc = mg_setup_shift(h, shift))) return rc;
     }
     return KSFD_OK;
@@ -932,15 +916,11 @@ static int mgp_begin(ksfd_handle *h, bool setup, double shift)
 // the hierarchy counts as not set up afterwards: the next real set-up starts cold and captures its graph again
 static void mgp_end(ksfd_handle *h)
 {
-    hipStreamSynchronize(h->st);
-    h->mg_shift = -1.0;
-    h->mg_graph_shift = -1.0;
-    if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
-    for (MGLevel &L : h->mg) L.pv_norm = 0.0;
-    h->mgc.ready = false;
+    ksfd_ctl::hierarchy_borrowed(h->cur);
+    mg_setup_cold(h);
 }
 // the level has a smoother after a set-up: it is part of the cycle, and not the level of an exact solve that succeeded
-static bool mgp_smoothed(const ksfd_handle *h, size_t l) { return l <= mg_end(h) && !(l == mg_end(h) && h->mgc.kind == 1 && h->mgc.ready); }
+static bool mgp_smoothed(const ksfd_handle *h, size_t l) { return l <= mg_end(h) && !(l == mg_end(h) && h->mgc.kind == 1 && h->cur.mgc_ready); }
 
 extern "C" int ksfd_mg_level_info(ksfd_handle *h, int32_t level, int32_t setup, double shift, ksfd_mg_level_info_t *info)
 {
@@ -1102,8 +1082,8 @@ extern "C" int ksfd_set_mg_tail(ksfd_handle *h, int64_t max_points)
     h->mgt.max_points = max_points;
     const int rc = mg_tail_replan(h);
     if (rc) { h->mgt = before; return rc; }
-    mgp_end(h);                                          // another cycle: the next one sets the hierarchy up again and captures its graph again
-    h->dr.valid = false;                                 // the recycled subspace belongs to the preconditioner that is gone
+    ksfd_ctl::vcycle_config_changed(h->cur);             // another cycle: the next one sets the hierarchy up again and captures its graph again
+    mg_setup_cold(h);                                    // ... from a cold power iteration, as after this entry it always has
     return KSFD_OK;
 }
 extern "C" int ksfd_get_mg_tail_info(ksfd_handle *h, ksfd_mg_tail_info *info)
@@ -1123,7 +1103,7 @@ extern "C" int ksfd_set_poly_params(ksfd_handle *h, int32_t max_degree, double t
     if (mg_threshold > 0.0) h->mg_threshold = mg_threshold;
     h->poly_max_deg = max_degree;           // 0 disables the polynomial preconditioner
     if (target > 0.0 && target < 1.0) h->poly_target = target;
-    h->poly_shift = -1.0;
+    ksfd_ctl::poly_config_changed(h->cur);
     return KSFD_OK;
 }
 extern "C" int ksfd_spectral_apply(ksfd_handle *h, double shift, const double *vh, double *outh, int32_t layout)
@@ -1167,7 +1147,6 @@ extern "C" int ksfd_set_deflation(ksfd_handle *h, int32_t keep, int32_t carry_st
     if (keep < 0 || keep > 16) return fail(h, KSFD_EINVAL, "deflation: keep = %d outside 0 (off) .. 16", (int)keep);
     h->dr_keep = keep;
     h->dr_carry = carry_stages != 0;
-    h->dr.valid = false;
     return KSFD_OK;
 }
 extern "C" int ksfd_get_deflation_stats(ksfd_handle *h, ksfd_deflation_stats *s)
@@ -1184,8 +1163,7 @@ extern "C" int ksfd_basis_rotate(ksfd_handle *h, int32_t nin, int32_t nout, cons
     if (nin < 1 || nout < 1 || nout > nin || nout > KSFD_ROT_MAXOUT || nin > KSFD_ROT_MAXIN || nin > h->restart_alloc + 1)
         return fail(h, KSFD_EINVAL, "basis_rotate: %d -> %d vectors outside 1 <= nout <= %d, nout <= nin <= min(%d, %d)", (int)nin, (int)nout, KSFD_ROT_MAXOUT, KSFD_ROT_MAXIN, h->restart_alloc + 1);
     hipSetDevice(h->device);
-    h->dr.valid = false;
-    rec_reset(h);
+    ksfd_ctl::krylov_basis_overwritten(h->cur);
     int rc;
     const int64_t nl = (int64_t)h->G.F * h->G.nloc;
     for (int i = 0; i < nin; i++) {
@@ -1226,8 +1204,7 @@ extern "C" int ksfd_krylov_op(ksfd_handle *h, int32_t op, int32_t k, int32_t wan
     if ((need_coef && !coef) || (nvec && (!vecs || !out_vecs)) || (nscal && !scalars)) return fail(h, KSFD_EINVAL, "krylov_op %d: missing buffer", (int)op);
     if (want_norm && op != KSFD_KOP_LINCOMB && op != KSFD_KOP_BASIS_AXPY) return fail(h, KSFD_EINVAL, "krylov_op %d has no norm epilogue", (int)op);
     hipSetDevice(h->device);
-    h->dr.valid = false;
-    rec_reset(h);
+    ksfd_ctl::krylov_basis_overwritten(h->cur);
     int rc;
     const GmDev D = gm_dev_block(h);
     if (op == KSFD_KOP_GMRES_COEF) {
@@ -1320,7 +1297,7 @@ extern "C" int ksfd_set_tuning(ksfd_handle *h, int32_t use_fused, int32_t yseg, 
         h->rhs_dots = !(use_fused & 2097152);
         h->old_boundary = (use_fused & 4194304) != 0;
         h->rhs_gplane = !(use_fused & 8388608);
-        if (h->mg_fuse != !(use_fused & 4096)) { h->mg_fuse = !(use_fused & 4096); h->mg_shift = -1.0; if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; } }
+        if (h->mg_fuse != !(use_fused & 4096)) { h->mg_fuse = !(use_fused & 4096); ksfd_ctl::vcycle_config_changed(h->cur); }
     }
     if (yseg > 0) h->yseg = yseg;
     if (yseg_jvp > 0) h->yseg_jvp = yseg_jvp;
@@ -1370,7 +1347,6 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         case KSFD_BENCH_MGC_FACTOR_COLUMNS: {
             MGLevel &L = h->mg[mg_end(h)];
             const LUSys Y{ &L.G, &L.P, L.coef, (long long)L.G.sloc, 0, KC_MG };
-            h->mgc.ready = false;
             if (!(r = lu_assemble(h, h->mgc.lu, Y, 1.0))) r = lu_factor_blocks(h, h->mgc.lu, KC_MG, false);
         } break;
         default: r = fail(h, KSFD_EINVAL, "bench_kernel: class %d not benchable", cls);
@@ -1379,7 +1355,7 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         return r;
     };
     if ((cls == KSFD_BENCH_ROTATE || cls == KSFD_BENCH_ROTATE_COMPOSED) && (h->restart_alloc < 30 || !h->Zb)) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the rotation benchmark needs 31 basis vectors and the flexible basis"); goto done; }
-    if (cls == KSFD_BENCH_ROTATE || cls == KSFD_BENCH_ROTATE_COMPOSED) { h->dr.valid = false; rec_reset(h); }
+    if (cls == KSFD_BENCH_ROTATE || cls == KSFD_BENCH_ROTATE_COMPOSED) ksfd_ctl::krylov_basis_overwritten(h->cur);
     if (cls == KSFD_BENCH_BAND_FACTOR || cls == KSFD_BENCH_BAND_SOLVE) {
         if ((rc = banded_guard(h))) goto done;
         if (!h->band.valid) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the banded benchmark needs a factorization (ksfd_banded_apply first)"); goto done; }
@@ -1387,8 +1363,8 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
     }
     if (cls >= KSFD_BENCH_MGC_SETUP && cls <= KSFD_BENCH_MGC_FACTOR_COLUMNS) {
         if (h->mgc.kind != 1 || !h->mg_ok) { rc = fail(h, KSFD_EINVAL, "bench_kernel: the coarse-solve benchmark needs ksfd_set_mg_coarse(kind 1)"); goto done; }
-        if ((rc = ensure_coef(h)) || (!h->mg_coef_valid && (rc = mg_restrict_coefs(h)))) goto done;
-        h->mg_shift = -1.0;                                  // the coarse factors no longer belong to the hierarchy's set-up
+        if ((rc = ensure_coef(h)) || (!h->cur.mg_coef_valid && (rc = mg_restrict_coefs(h)))) goto done;
+        ksfd_ctl::hierarchy_borrowed(h->cur);                // the coarse factors no longer belong to the hierarchy's set-up
         if (cls == KSFD_BENCH_MGC_APPLY) { bool ok = false; if ((rc = mgc_setup(h, h->mg[mg_end(h)], 1.0, &ok))) goto done; if (!ok) { rc = fail(h, KSFD_ELINEAR, "bench_kernel: the coarse factorization is flagged"); goto done; } }
     }
     if ((rc = halo(h, h->u))) goto done;

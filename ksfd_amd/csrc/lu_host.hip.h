@@ -244,7 +244,7 @@ static void mgc_free(ksfd_handle *h)
     lu_free(C.lu);
     if (C.inv) hipFree(C.inv);
     C.inv = nullptr;
-    C.ready = false;
+    ksfd_ctl::coarse_factors_ended(h->cur);
 }
 
 // buffers of the exact solve on level `level`: factors, Jacobian staging, inverse
@@ -273,7 +273,7 @@ static int mgc_setup(ksfd_handle *h, MGLevel &L, double shift, bool *ok)
     MGCoarse &C = h->mgc;
     LUState &S = C.lu;
     *ok = false;
-    C.ready = false;
+    ksfd_ctl::coarse_factors_ended(h->cur);
     if (!S.A || !C.inv || S.n != (int64_t)L.G.F * L.G.nloc) return fail(h, KSFD_EINVAL, "coarse solve: no buffers for this level");
     // single rank (ksfd_set_mg_coarse refuses a halo transport): the level is the whole grid, its slow extent the global one
     const LUSys Y{ &L.G, &L.P, L.coef, (long long)L.G.sloc, 0, KC_MG };
@@ -294,7 +294,7 @@ static int mgc_setup(ksfd_handle *h, MGLevel &L, double shift, bool *ok)
     if (C.info_h) return KSFD_OK;
     S.valid = true;
     S.shift = shift;
-    C.ready = true;
+    ksfd_ctl::coarse_factors_ready(h->cur);
     *ok = true;
     return KSFD_OK;
 }
@@ -304,7 +304,7 @@ static int mgc_setup(ksfd_handle *h, MGLevel &L, double shift, bool *ok)
 static int mgc_apply(ksfd_handle *h, MGLevel &L, const double *b, double *x)
 {
     MGCoarse &C = h->mgc;
-    if (!C.ready) return fail(h, KSFD_EINVAL, "coarse solve without a set-up");
+    if (!h->cur.mgc_ready) return fail(h, KSFD_EINVAL, "coarse solve without a set-up");
     const int n = (int)C.lu.n;
     const KLUVec V{ L.G.nloc, L.G.plane, L.kv.off };
     {

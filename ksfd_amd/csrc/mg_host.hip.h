@@ -29,7 +29,8 @@ static void mg_free(ksfd_handle *h)
     mgc_free(h);
     h->mgc = MGCoarse();
     h->mgt.level = -1; h->mgt.nlev = 0; h->mgt.lds = 0;      // max_points stays: mg_build plans the tail again
-    if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
+    if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }      // it recorded the buffers freed below
+    ksfd_ctl::hierarchy_freed(h->cur);
     for (size_t l = 0; l < h->mg.size(); l++) {
         MGLevel &L = h->mg[l];
         void *bufs[] = { L.dinv, l ? L.coef : nullptr, L.coef32, L.Ad, L.dG, L.pv, L.v64.x, L.v64.b, L.v64.r, L.v64.d, L.v32.x, L.v32.b, L.v32.r, L.v32.d };
@@ -306,7 +307,7 @@ static int mg_restrict_coefs(ksfd_handle *h)
         }
     }
     HIPCHK(h, hipGetLastError());
-    h->mg_coef_valid = true;
+    ksfd_ctl::coarse_planes_restricted(h->cur);
     return KSFD_OK;
 }
 
@@ -318,6 +319,10 @@ static void mg_dinv_apply(ksfd_handle *h, MGLevel &L, double bytes, const TR *r,
     Scope sc(h, KC_MG, bytes);
     NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_dinv_apply<NL, TR, TZ>), dim3(point_blocks(L.G)), dim3(KSFD_BLOCK), 0, h->st, L.G.nloc, L.G.plane, (const float *)(L.dinv + off), r + off, scale, z + off, z2 ? z2 + off : (TZ *)nullptr, rcopy ? rcopy + off : (TZ *)nullptr));
 }
+
+// the next set-up starts the power iteration of every level cold, from the hash fill (a checkpoint save and restore, so that replays are
+// bitwise; the test entries, so that what they return does not depend on the steps before)
+static void mg_setup_cold(ksfd_handle *h) { for (MGLevel &L : h->mg) L.pv_norm = 0.0; }
 
 // block-diagonal inverses and Chebyshev upper bounds for this shift
 static int mg_setup_shift(ksfd_handle *h, double shift)
@@ -374,8 +379,7 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
             L.ratio = std::max(30.0, 1.5 * L.lam_max * h->hres[0]);
         }
     }
-    h->mg_shift = shift;
-    h->mg_graph_shift = -1.0;        // Chebyshev bounds changed: the captured coarse cycle is stale
+    ksfd_ctl::shift_setup_done(h->cur, shift);
     return KSFD_OK;
 }
 
@@ -576,7 +580,7 @@ template <typename Body>
 static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool f32, Body body)
 {
     int rc;
-    if (!h->mg_graph || h->mg_graph_shift != shift || h->mg_graph_x != xkey || h->mg_graph_f32 != f32) {
+    if (!h->mg_graph || !ksfd_ctl::graph_current(h->cur, shift, xkey, f32)) {
         if (h->mg_graph) { hipGraphExecDestroy(h->mg_graph); h->mg_graph = nullptr; }
         hipGraph_t g = nullptr;
         const double b0 = h->bytes_acc;
@@ -598,9 +602,7 @@ static int mg_coarse_graph(ksfd_handle *h, double shift, const void *xkey, bool 
         h->mgc.solves = s0;
         h->mgt.graph_launches = h->mgt.launches - t0;
         h->mgt.launches = t0;
-        h->mg_graph_shift = shift;
-        h->mg_graph_x = xkey;
-        h->mg_graph_f32 = f32;
+        ksfd_ctl::graph_captured(h->cur, shift, xkey, f32);
     }
     Scope sc(h, KC_MG, h->mg_graph_bytes);
     HIPCHK(h, hipGraphLaunch(h->mg_graph, h->st));
@@ -629,7 +631,7 @@ static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const T *b, T *x, c
     MGLevel &L = h->mg[l];
     // the level the cycle ends on has fp64 vectors (mg_f32): the exact solve, or Chebyshev sweeps over the whole spectrum
     if constexpr (!f32) if (l == mg_end(h)) {
-        if (h->mgc.kind == 1 && h->mgc.ready) return mgc_apply(h, L, b, x);
+        if (h->mgc.kind == 1 && h->cur.mgc_ready) return mgc_apply(h, L, b, x);
         return mg_smooth(h, L, shift, b, x, mg_coarse_sweeps(h, L), true, L.ratio);
     }
     // nu sweeps before and after the correction; fp32 vectors have the fused V(2,2) pair only
@@ -653,8 +655,8 @@ static int mg_precond(ksfd_handle *h, double shift, const double *in, double *ou
 {
     int rc;
     if ((rc = ensure_coef32(h))) return rc;                  // level 0 reads the fp32 copy of the planes (mg_sys)
-    if (!h->mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
-    if (h->mg_shift != shift && (rc = mg_setup_shift(h, shift))) return rc;
+    if (!h->cur.mg_coef_valid && (rc = mg_restrict_coefs(h))) return rc;
+    if (h->cur.mg_shift != shift && (rc = mg_setup_shift(h, shift))) return rc;
     MGVecs<float> &V = h->mg[0].v32;
     if (h->mg_use32 && mg_cycle32_ok(h)) return mg_vcycle<float>(h, 0, shift, V.b, V.x, in, out);
     return mg_vcycle<double>(h, 0, shift, in, out);

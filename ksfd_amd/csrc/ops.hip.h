@@ -302,7 +302,7 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         for (int j = 0; j < C.nout && carry; j++) carry = C.yin[j] == C.yout[j];
         // first stage of a step: the argument is the resident state itself and G(u) is plane 1 of the frozen coefficients the step has
         // just made of it (same parameters, same clamped inputs): loaded, not evaluated (the rule of the 3-D path below)
-        const bool reuse_G = h->rhs_gplane && C.nin == 0 && C.nout == 0 && u == h->u && h->coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
+        const bool reuse_G = h->rhs_gplane && C.nin == 0 && C.nout == 0 && u == h->u && h->cur.coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
         auto launch = [&](const KStrips &Kx, double frac, double *np) -> int {
             Scope sc(h, KC_RHS, (vbytes(h, 2 + C.nin + (carry ? 0 : C.nout) + D.n) + (reuse_G ? 8.0 * (double)G.nloc : 0.0)) * frac, vbytes(h, 2 + C.nin + C.nout + D.n) * frac);
             if (reuse_G) { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL, false, true>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D, (const double *)(h->coef + G.plane))); }
@@ -330,7 +330,7 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         const double *Gplane = h->Gb;
         // first stage of a step: the argument is the resident state itself and G(u) is plane 1 of the frozen coefficients the step has
         // just made of it (same parameters): nothing to form, no pass
-        const bool reuse_G = C.nin == 0 && u == h->u && h->coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
+        const bool reuse_G = C.nin == 0 && u == h->u && h->cur.coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
         if (reuse_G) Gplane = h->coef + G.plane;
         else {
             Scope sc(h, KC_GFIELD, 8.0 * ((1 + C.nin) * G.F + (C.nin ? G.F : 0) + 1) * (double)G.plane, C.nin ? vbytes(h, 2 + C.nin) : 0.0);
@@ -384,15 +384,12 @@ static bool coef32_alloc(ksfd_handle *h)
 }
 
 // Once per step: C = [rho, G, G_rho, G_U..] of the (ghost-filled) state u
-// want_means: the grid means of the spectral preconditioner come out of the same launch (resident state only)
-static int op_jcoef(ksfd_handle *h, const double *u, bool want_means = false)
+// c32: where the launch stores the fp32 copy of the planes, or NULL.  want_means: the grid means of the spectral preconditioner come out
+// of the same launch (resident state only; the caller has checked that the block partials fit)
+static int op_jcoef(ksfd_handle *h, const double *u, float *c32, bool want_means)
 {
     const KGeom &G = h->G;
     const int nbp = plane_blocks(G);
-    // the fp32 copy is made when a consumer asks for it (ensure_coef32); only the old step boundary has k_jcoef store it
-    float *c32 = h->old_boundary && coef32_alloc(h) ? h->coef32 : nullptr;
-    h->coef32_fresh = c32 != nullptr;
-    want_means = want_means && (long long)(1 + h->P.nlig) * nbp <= part_capacity();
     {
     Scope sc(h, KC_GFIELD, (8.0 * (G.F + 3 + h->P.nlig) + (c32 ? 4.0 * (3 + h->P.nlig) : 0.0)) * (double)G.plane);
     NL_DISPATCH(h->P.nlig, hipLaunchKernelGGL((k_jcoef<NL>), dim3(nbp), dim3(KSFD_BLOCK), 0, h->st, G, h->P, u, h->coef, c32, want_means ? h->part : (double *)nullptr));
@@ -410,16 +407,17 @@ static int op_jcoef(ksfd_handle *h, const double *u, bool want_means = false)
 
 // Coefficient planes of the RESIDENT state, computed once per state: the CFL check after a step and the next step's
 // Jacobian need the same planes (the reference evaluates G twice there: velocity, KSFD/ksfdsym.py:1188-1209, and Jacobian).
-// coef_fresh is cleared by everything that changes h->u.
+// Every event that gives h->u or the parameters new values ends cur.coef_fresh (handle_state.h: state_written, params_changed).
 static int ensure_coef(ksfd_handle *h, bool ghosts_done = false)
 {
-    if (h->coef_fresh) return KSFD_OK;
+    if (h->cur.coef_fresh) return KSFD_OK;
     int rc;
     if (!ghosts_done && (rc = halo(h, h->u))) return rc;
-    if ((rc = op_jcoef(h, h->u, h->spec.ok))) return rc;
-    h->coef_fresh = true;
-    h->mg_coef_valid = false; h->mg_shift = -1.0;
-    h->spec.means_valid = h->spec.ok && (long long)(1 + h->P.nlig) * plane_blocks(h->G) <= part_capacity();
+    // the fp32 copy is made when a consumer asks for it (ensure_coef32); only the old step boundary has k_jcoef store it
+    float *c32 = h->old_boundary && coef32_alloc(h) ? h->coef32 : nullptr;
+    const bool means = h->spec.ok && (long long)(1 + h->P.nlig) * plane_blocks(h->G) <= part_capacity();
+    if ((rc = op_jcoef(h, h->u, c32, means))) return rc;
+    ksfd_ctl::planes_recomputed(h->cur, c32 != nullptr, means);
     return KSFD_OK;
 }
 
@@ -428,14 +426,14 @@ static int ensure_coef(ksfd_handle *h, bool ghosts_done = false)
 // own store rounds, so the readers see the same bits either way.
 static int ensure_coef32(ksfd_handle *h)
 {
-    if (!coef32_alloc(h) || h->coef32_fresh) return KSFD_OK;
+    if (!coef32_alloc(h) || h->cur.coef32_fresh) return KSFD_OK;
     const long long n = (long long)(3 + h->P.nlig) * h->G.plane;
     {
         Scope sc(h, KC_GFIELD, 12.0 * (double)n);
         hipLaunchKernelGGL(k_coef32, dim3(blocks_for(n / 2)), dim3(KSFD_BLOCK), 0, h->st, n, (const double *)h->coef, h->coef32);
     }
     HIPCHK(h, hipGetLastError());
-    h->coef32_fresh = true;
+    ksfd_ctl::coef32_made(h->cur);
     return KSFD_OK;
 }
 

@@ -107,7 +107,7 @@ static int spec_means(ksfd_handle *h)
     const double ntot = (double)h->cfg.n[0] * (double)h->cfg.n[1] * (double)h->cfg.n[2];
     S.a_rr = h->hres[0] / ntot;
     for (int l = 0; l < h->P.nlig; l++) S.a_rU[l] = h->hres[1 + l] / ntot;
-    S.means_valid = true;
+    ksfd_ctl::means_computed(h->cur);
     return KSFD_OK;
 }
 
@@ -220,7 +220,7 @@ static int spec_apply(ksfd_handle *h, double shift, const double *v, double *z, 
     SpecState &S = h->spec;
     const SpecShape &Z = S.shape;
     const KGeom &G = h->G;
-    if (!S.ok || !S.means_valid) return fail(h, KSFD_EINVAL, "spectral preconditioner not available for this handle");
+    if (!S.ok || !h->cur.means_valid) return fail(h, KSFD_EINVAL, "spectral preconditioner not available for this handle");
     SpecRun R;
     memset(&R, 0, sizeof R);
     R.v = v; R.v32 = v32; R.z = z;

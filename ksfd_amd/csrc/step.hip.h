@@ -63,7 +63,6 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
     p.hh = hh; p.direct = direct; p.dr_on = dr_on;
     p.banded = direct && opts->pc_type == 6;
     p.shift = 1.0 / (GAMMA_RA * hh);
-    h->dr.valid = false;                             // every attempt has its own matrix: nothing is carried into it
     p.stiff = ksfd_ctl::stiffness(h->P.s2, h->P.lig_D, h->P.nlig, h->P.inv_h2, h->G.dim, p.shift);
     ksfd_ctl::RegimeIn in;
     in.pc_type = opts->pc_type; in.reserved = opts->reserved; in.stiff = p.stiff;
@@ -79,7 +78,7 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
     p.use_spec = r.spec; p.use_pc = r.mg;
     if (p.use_spec) {
         if (!h->Zb && alloc_d(h, &h->Zb, (int64_t)h->restart_alloc * h->vlen)) return KSFD_ENOMEM;
-        if (!h->spec.means_valid && (rc = spec_means(h))) return rc;
+        if (!h->cur.means_valid && (rc = spec_means(h))) return rc;
     }
     p.use_poly = false;
     if (r.poly_wanted) {
@@ -92,7 +91,7 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
             }
             lam_done = true;
         }
-        if (h->poly_shift != p.shift) poly_setup(h, p.shift);
+        if (h->cur.poly_shift != p.shift) poly_setup(h, p.shift);
         p.use_poly = h->poly_deg >= 1 && h->poly_max_deg >= 1;
     }
     p.use_async = ksfd_ctl::pipelined_allowed(in, r, p.use_poly);
@@ -266,14 +265,14 @@ static int step_attempt(ksfd_handle *h, const ksfd_step_opts *opts, const Attemp
 // outside a step attempt writes the owned points of Y (halo exchanges fill ghost rows only); the next attempt's first stage solve does.
 static int err_materialize(ksfd_handle *h)
 {
-    if (!h->err_pending) return KSFD_OK;
+    if (!h->cur.err_pending) return KSFD_OK;
     {
         Scope sc(h, KC_FINISH, vbytes(h, 5));
         hipLaunchKernelGGL(k_rosw_error, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)h->Y, h->vlen, h->b2t[0] - h->bt[0],
                            h->b2t[1] - h->bt[1], h->b2t[2] - h->bt[2], h->b2t[3] - h->bt[3], h->errv);
     }
     HIPCHK(h, hipGetLastError());
-    h->err_pending = false;
+    ksfd_ctl::error_vector_formed(h->cur);
     return KSFD_OK;
 }
 
@@ -289,8 +288,7 @@ static int step_finish(ksfd_handle *h, const ksfd_step_opts *opts, double *wrms,
                            h->b2t[2] - h->bt[2], h->b2t[3] - h->bt[3], opts->atol, opts->rtol, h->P.rhomin, h->P.Umin,
                            h->old_boundary ? h->errv : (double *)nullptr, h->part);
     }
-    h->have_err = true;
-    h->err_pending = !h->old_boundary;
+    ksfd_ctl::completion_done(h->cur, h->old_boundary);
     if ((rc = reduce_rows(h, 2, h->nblk_vec, 0))) return rc;
     const double ntot = (double)h->G.F * (double)h->cfg.n[0] * (double)h->cfg.n[1] * (double)h->cfg.n[2];
     *wrms = sqrt(h->hres[0] / ntot);
