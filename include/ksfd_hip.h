@@ -470,6 +470,49 @@ enum { KSFD_KOP_LINCOMB = 0, KSFD_KOP_MULTIDOT = 1, KSFD_KOP_MULTIDOT_GRAM = 2, 
        KSFD_KOP_GS_UPDATE_DEV = 5, KSFD_KOP_GMRES_COEF = 6 };
 int ksfd_krylov_op(ksfd_handle *h, int32_t op, int32_t k, int32_t want_norm, const double *coef_host, double alpha, double beta,
                    const double *vecs_host, double *out_vecs_host, double *scalars_out, int32_t layout);
+/* Parity/test entries of the stage right-hand sides and of the frozen Jacobian action, the twins of ksfd_krylov_op and ksfd_mg_part: the
+ * functions the step itself calls (stage_rhs, stage_gram_guess, step_finish, err_materialize, op_jvp_frozen_halo, op_residual32,
+ * poly_apply) run on host vectors, never a kernel launch of the entries' own, so every launch mode, its geometry and its epilogue show.
+ * Both work at the resident state (ghost rows exchanged and coefficient planes made as at the head of a step, but NO groom: the kernels
+ * clamp on load) and leave the state and what the stepper remembers from step to step untouched.  Host vectors: ksfd_local_size doubles
+ * in `layout`.  KSFD_EINVAL before anything is touched on a bad argument.
+ *
+ * ksfd_stage_rhs: the right-hand sides b_0 .. b_{nstages-1} (nstages 1..4) of one attempt with step size hstep whose stage vectors
+ * Y_0 .. Y_{nstages-2} are the caller's (y_host, one after the other; with fin_host: four), formed in order exactly as step_attempt forms
+ * them, with the stage guesses' Gram bookkeeping wherever the attempt would keep it.  regime 0: plain (no norm, no guess); 1: spectral
+ * (||b_i||^2 and, with guesses, <b_i, b_j> from the store epilogue of the 2-D strip kernel); 2: multigrid (guesses, inner products by
+ * a multi-dot).  Whether the stage algebra is fused and whether guesses are on follows the rules of the step (tuning bits 10, 13, 14, 15,
+ * 21, 23 and the handle's solvers).  b_host receives nstages vectors.  fin_host != NULL (nstages = 4, four Y vectors): step_finish with
+ * atol / rtol, then err_materialize; fin_host receives the new state (from the completion's output buffer; the state is not advanced) and
+ * the embedded error vector, info wrms and below.  The stage vectors, the stored right-hand sides and the error vector buffer are
+ * overwritten: ksfd_get_last_error_vector afterwards answers as after a step that completed no attempt. */
+typedef struct ksfd_stage_info {
+    int32_t fuse_stage, guess_on;      /* AttemptPlan of the run */
+    int32_t path;                      /* kernel path of the grid: 0 2-D strip, 1 3-D second generation (k_jvp3d_lds), 2 3-D first generation, 3 generic */
+    int32_t rhs_strip;                 /* the RHS ran on a strip kernel (2-D: k_rhs2d_fused, 3-D: k_rhs3d_strip) */
+    int32_t seg, nseg, nstrips, rows;  /* RHS launch geometry: rows (2-D) or planes (3-D) per segment, segments, strips, y rows per block (3-D) */
+    int32_t overlap;                   /* launches with a stage vector whose ghost rows travel: interior + boundary launches with split partials */
+    int32_t dots_done[4];              /* per stage: <b_i, b_j> came from the RHS epilogue */
+    int32_t guess_n[4];                /* per stage: vectors of the stage guess */
+    double bnorm2[4];                  /* per stage: ||b_i||^2 as the stage solve would get it, -1 where none */
+    double gb[16];                     /* Gram matrix of the right-hand sides, row-major 4 x 4; NaN where the attempt never forms the entry */
+    double guess_c[16];                /* [4 i + j]: coefficient of Y_j in the guess of stage i */
+    double wrms, below;                /* of the completion (fin_host) */
+} ksfd_stage_info;
+int ksfd_stage_rhs(ksfd_handle *h, int32_t regime, int32_t nstages, double hstep, double atol, double rtol, const double *y_host,
+                   double *b_host, double *fin_host, ksfd_stage_info *info, int32_t layout);
+/* ksfd_stage_jvp: one frozen Jacobian action at the resident state.
+ *   op 0: out = op_jvp_frozen_halo(v, mode, shift, yadd = y, alpha, beta); mode 0: J v, 1: A v = shift v - J v, 2: y - A v,
+ *         3: alpha y + beta A v, 4: alpha v + beta A v (y_host needed for modes 2 and 3)
+ *   op 1: op_residual32(x = v, shift, b = y): out = the fp32 values of b - A x widened to double, scalars[0] = ||r||^2 from the store
+ *         epilogue; KSFD_EINVAL where the spectral solver would not take the fused residual (no strip kernel on the grid)
+ *   op 2: out = poly_apply(v) with the polynomial sum_i coef[i] (A/shift)^i, i = 0 .. deg (deg 1..7), installed for the call and put back
+ *         afterwards; fp32 or fp64 Horner temporaries exactly as the handle would take them (tuning bit 9)
+ * scalars (8 doubles): [0] see op 1; [1] path as in ksfd_stage_info; [2] rows (2-D) or planes (3-D) per segment of the launch, [3] segments,
+ * [4] strips, [5] 1 where op 2 took the fp32 path, [6] 1 where the launches were interior + boundary (ghost rows of v travelling), [7] y rows
+ * per block (3-D).  Needs the frozen action (tuning bit 1 clear), else KSFD_EINVAL. */
+int ksfd_stage_jvp(ksfd_handle *h, int32_t op, int32_t mode, double shift, double alpha, double beta, int32_t deg, const double *coef,
+                   const double *v_host, const double *y_host, double *out_host, double *scalars, int32_t layout);
 /* ksfd_bench_kernel classes beyond the profile's kernel classes: the rotation kernel on 31 -> 11 vectors in one pass, and the same
  * rotation composed from 11 basis combinations of 31 vectors (out of place); one factorization of the banded direct solver (assembly
  * and the read-back of info included, at the shift of the last ksfd_banded_apply or pc_type 6 attempt) and one of its solves */

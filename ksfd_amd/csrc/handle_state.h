@@ -117,6 +117,24 @@ static inline void attempt_begins(Current &c)
 // k_rosw_finish ran.  stored: it wrote the error vector itself (old step boundary); else the vector is formed on demand from Y
 static inline void completion_done(Current &c, bool stored) { c.have_err = true; c.err_pending = !stored; }
 static inline void error_vector_formed(Current &c) { c.err_pending = false; }         // err_materialize
+// the test entry ksfd_stage_rhs runs the stages of an attempt of its own on the caller's vectors: Y and the stored right-hand sides are
+// overwritten, which is what an attempt that begins does to them.  completed: it also ran the completion and formed the error vector,
+// of vectors that belong to no step -- nothing is left to hand out, as after a step that completed no attempt
+static inline void stage_vectors_borrowed(Current &c, bool completed)
+{
+    attempt_begins(c);
+    if (completed) { c.have_err = false; c.err_pending = false; }
+}
+
+// a test entry (ksfd_stage_rhs, ksfd_stage_jvp) made the planes, their fp32 copy or the means for itself: what was not current when it
+// began (`before`: the record as the entry found it) is not current when it returns, so the step that follows makes it again, launch for
+// launch as on a handle the entry never touched.  Only ends; what was current before and still is stays
+static inline void derived_given_back(Current &c, const Current &before)
+{
+    c.coef_fresh = c.coef_fresh && before.coef_fresh;
+    c.coef32_fresh = c.coef32_fresh && before.coef32_fresh;
+    c.means_valid = c.means_valid && before.means_valid;
+}
 
 // ---- checkpoint -------------------------------------------------------------------------------------------------------------------
 // save: the floor proof is a property of the state being copied

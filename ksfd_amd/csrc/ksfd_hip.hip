@@ -1260,6 +1260,166 @@ extern "C" int ksfd_krylov_op(ksfd_handle *h, int32_t op, int32_t k, int32_t wan
         if ((rc = download(h, h->V + (int64_t)i * vs, layout, out_vecs + (int64_t)i * nl))) return rc;
     return KSFD_OK;
 }
+// ---- parity/test entries of the stage right-hand sides and the frozen Jacobian action (include/ksfd_hip.h has the contract) -------------
+// Everything goes through the functions the step calls, on the vectors the step uses; the entries only upload, download and report.
+static int stage_rhs_run(ksfd_handle *h, int regime, int nstages, int ny, double hstep, double atol, double rtol, const double *y_host,
+                         double *b_host, double *fin_host, ksfd_stage_info *info, int layout)
+{
+    int rc;
+    const int64_t nl = (int64_t)h->G.F * h->G.nloc, vs = h->vlen;
+    // head of step_run without the groom: the kernels clamp on load and the state must stay as it is
+    if ((rc = halo(h, h->u))) return rc;
+    if (h->use_frozen && (rc = ensure_coef(h, true))) return rc;
+    for (int j = 0; j < ny; j++) {
+        if ((rc = upload(h, y_host + (int64_t)j * nl, layout, h->Y + (int64_t)j * vs))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->st));            // the staging buffer of upload() is reused by the next vector
+    }
+    AttemptPlan p = AttemptPlan{};
+    p.hh = hstep;
+    p.shift = 1.0 / (GAMMA_RA * hstep);
+    p.use_spec = regime == 1;
+    p.use_pc = regime == 2;
+    plan_stage_forms(h, p);
+    info->fuse_stage = p.fuse_stage; info->guess_on = p.guess_on;
+    info->path = (int32_t)grid_path(h);
+    if (fused_ok(h)) {
+        const KStrips K = make_strips(h);
+        info->rhs_strip = 1; info->seg = K.yseg; info->nseg = K.nseg; info->nstrips = K.nstrips;
+        info->overlap = h->ring && h->overlap && K.nseg >= 3;
+    } else if (strip3d_ok(h) && h->rhs3d_strip) {
+        const K3D K = make_k3d(h);
+        info->rhs_strip = 1; info->seg = K.zseg; info->nseg = K.nzseg; info->nstrips = K.nstrips; info->rows = K.rows;
+    }
+    double gb[4][4];
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) gb[i][j] = NAN;
+    for (int i = 0; i < nstages; i++) {
+        StageRhs r;
+        SpecGuess sg;
+        sg.n = 0;
+        if ((rc = stage_rhs(h, p, i, r))) return rc;
+        if (p.guess_on && (rc = stage_gram_guess(h, i, r, gb, sg))) return rc;
+        info->bnorm2[i] = r.bnorm2;
+        info->dots_done[i] = r.dots_done ? 1 : 0;
+        info->guess_n[i] = sg.n;
+        for (int q = 0; q < sg.n; q++) info->guess_c[4 * i + (int)((sg.Y[q] - h->Y) / vs)] = sg.c[q];
+        if ((rc = download(h, r.b, layout, b_host + (int64_t)i * nl))) return rc;
+    }
+    for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) info->gb[4 * i + j] = gb[i][j];
+    if (fin_host) {
+        ksfd_step_opts o;
+        ksfd_default_step_opts(&o);
+        o.atol = atol; o.rtol = rtol;
+        if ((rc = step_finish(h, &o, &info->wrms, &info->below))) return rc;
+        if ((rc = download(h, h->usave, layout, fin_host))) return rc;       // the new state; h->u is as it was (nothing swaps)
+        if ((rc = err_materialize(h)) || (rc = download(h, h->errv, layout, fin_host + nl))) return rc;
+    }
+    return KSFD_OK;
+}
+extern "C" int ksfd_stage_rhs(ksfd_handle *h, int32_t regime, int32_t nstages, double hstep, double atol, double rtol, const double *y_host,
+                              double *b_host, double *fin_host, ksfd_stage_info *info, int32_t layout)
+{
+    if (!h || !b_host || !info) return KSFD_EINVAL;
+    if (layout < 0 || layout > 2) return fail(h, KSFD_EINVAL, "bad layout %d", layout);
+    if (regime < 0 || regime > 2) return fail(h, KSFD_EINVAL, "stage_rhs: regime %d is none of 0 (plain), 1 (spectral), 2 (multigrid)", (int)regime);
+    if (nstages < 1 || nstages > 4) return fail(h, KSFD_EINVAL, "stage_rhs: %d stages outside 1 .. 4", (int)nstages);
+    if (!(hstep > 0.0) || !isfinite(hstep)) return fail(h, KSFD_EINVAL, "stage_rhs: step size %.6g is not positive and finite", hstep);
+    if (fin_host && nstages != 4) return fail(h, KSFD_EINVAL, "stage_rhs: the completion needs all four stages (got %d)", (int)nstages);
+    if (fin_host && !(atol >= 0.0 && rtol >= 0.0 && atol + rtol > 0.0 && isfinite(atol + rtol)))
+        return fail(h, KSFD_EINVAL, "stage_rhs: tolerances atol %.6g, rtol %.6g of the completion are not usable", atol, rtol);
+    const int ny = fin_host ? 4 : nstages - 1;
+    if (ny > 0 && !y_host) return fail(h, KSFD_EINVAL, "stage_rhs: missing buffer");
+    hipSetDevice(h->device);
+    memset(info, 0, sizeof *info);
+    for (int i = 0; i < 4; i++) info->bnorm2[i] = -1.0;
+    const ksfd_ctl::Current before = h->cur;
+    ksfd_ctl::stage_vectors_borrowed(h->cur, false);       // Y and bstore are about to hold the caller's vectors
+    const int rc = stage_rhs_run(h, regime, nstages, ny, hstep, atol, rtol, y_host, b_host, fin_host, info, layout);
+    if (fin_host) ksfd_ctl::stage_vectors_borrowed(h->cur, true);     // ... and the error vector, if the completion got that far, is no step's
+    ksfd_ctl::derived_given_back(h->cur, before);          // planes made here only: the next step makes its own, launch for launch
+    return rc;
+}
+// the fused fp32 residual as spec_solve decides it
+static bool residual32_ok(ksfd_handle *h) { return fused_ok(h) || (strip3d_ok(h) && k3d_waves(h) <= part_capacity()); }
+static int stage_jvp_run(ksfd_handle *h, int op, int mode, double shift, double alpha, double beta, int deg, const double *coef,
+                         const double *v_host, const double *y_host, double *out_host, double *scalars, int layout);
+extern "C" int ksfd_stage_jvp(ksfd_handle *h, int32_t op, int32_t mode, double shift, double alpha, double beta, int32_t deg, const double *coef,
+                              const double *v_host, const double *y_host, double *out_host, double *scalars, int32_t layout)
+{
+    if (!h) return KSFD_EINVAL;
+    if (layout < 0 || layout > 2) return fail(h, KSFD_EINVAL, "bad layout %d", layout);
+    if (op < 0 || op > 2) return fail(h, KSFD_EINVAL, "stage_jvp: unknown operation %d", (int)op);
+    if (!isfinite(shift) || !isfinite(alpha) || !isfinite(beta)) return fail(h, KSFD_EINVAL, "stage_jvp: non-finite shift, alpha or beta");
+    if (op == 0 && (mode < 0 || mode > 4)) return fail(h, KSFD_EINVAL, "stage_jvp: mode %d outside 0 .. 4", (int)mode);
+    if (op == 2 && (deg < 1 || deg > ksfd_krylov::CHEB_MAX_DEG)) return fail(h, KSFD_EINVAL, "stage_jvp: degree %d outside 1 .. %d", (int)deg, ksfd_krylov::CHEB_MAX_DEG);
+    if (op == 2 && !(shift != 0.0)) return fail(h, KSFD_EINVAL, "stage_jvp: the polynomial needs a shift other than zero");
+    const bool need_y = op == 1 || (op == 0 && (mode == 2 || mode == 3));
+    if (!v_host || !out_host || !scalars || (need_y && !y_host) || (op == 2 && !coef)) return fail(h, KSFD_EINVAL, "stage_jvp %d: missing buffer", (int)op);
+    if (!h->use_frozen) return fail(h, KSFD_EINVAL, "stage_jvp: the frozen Jacobian action is switched off (tuning bit 1)");
+    hipSetDevice(h->device);
+    if (op == 1 && !residual32_ok(h)) return fail(h, KSFD_EINVAL, "stage_jvp: no fused fp32 residual on this handle (it needs a strip kernel)");
+    const ksfd_ctl::Current before = h->cur;
+    const int rc = stage_jvp_run(h, op, mode, shift, alpha, beta, deg, coef, v_host, y_host, out_host, scalars, layout);
+    ksfd_ctl::derived_given_back(h->cur, before);          // planes and fp32 copy made here only: the next step makes its own
+    return rc;
+}
+static int stage_jvp_run(ksfd_handle *h, int op, int mode, double shift, double alpha, double beta, int deg, const double *coef,
+                         const double *v_host, const double *y_host, double *out_host, double *scalars, int layout)
+{
+    int rc;
+    if ((rc = ensure_coef(h))) return rc;
+    // operands where the solvers have theirs: x in a work vector, b in bvec, the residual (fp32 or fp64) in Z; t1 and t2 are poly_apply's
+    double *const v = h->t3, *const y = h->bvec, *const out = h->Z;
+    if ((rc = upload(h, v_host, layout, v))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    if (y_host) {
+        if ((rc = upload(h, y_host, layout, y))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->st));
+    }
+    for (int i = 0; i < 8; i++) scalars[i] = 0.0;
+    const JvpPath path = grid_path(h);
+    scalars[1] = (double)path;
+    if (path == JP_STRIP2D) {
+        const KStrips K = make_strips(h, true);
+        scalars[2] = K.yseg; scalars[3] = K.nseg; scalars[4] = K.nstrips;
+        scalars[6] = (h->ring && h->overlap && K.nseg >= 3) ? 1.0 : 0.0;
+    } else if (path == JP_LDS3D || path == JP_STRIP3D) {
+        const K3D K = path == JP_LDS3D ? make_k3d_lds(h) : make_k3d(h);
+        scalars[2] = K.zseg; scalars[3] = K.nzseg; scalars[4] = K.nstrips; scalars[7] = K.rows;
+    }
+    if (op == 0) {
+        if ((rc = op_jvp_frozen_halo(h, v, mode, shift, out, y_host ? y : nullptr, alpha, beta))) return rc;
+        return download(h, out, layout, out_host);
+    }
+    if (op == 1) {
+        // as spec_residual: the 2-D fused residual exchanges the ghost rows of x itself, behind its interior rows
+        if (h->ring && h->G.dim != 2 && (rc = halo(h, v))) return rc;
+        float *const r32 = reinterpret_cast<float *>(out);
+        if ((rc = op_residual32(h, v, shift, y, r32))) return rc;
+        scalars[0] = h->hres[0];
+        // widened on the host, then through the layout kernel like every other vector
+        std::vector<float> f((size_t)h->vlen);
+        std::vector<double> d((size_t)h->vlen);
+        HIPCHK(h, hipMemcpyAsync(f.data(), r32, sizeof(float) * f.size(), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
+        for (size_t i = 0; i < f.size(); i++) d[i] = (double)f[i];
+        HIPCHK(h, hipMemcpyAsync(h->t1, d.data(), sizeof(double) * d.size(), hipMemcpyHostToDevice, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
+        return download(h, h->t1, layout, out_host);
+    }
+    // op 2: the caller's polynomial in place of the handle's for this one application.  poly_apply reads poly_deg and poly_alpha only; the
+    // record of which shift they were made for (cur.poly_shift) is not touched and holds again once they are back
+    const int deg0 = h->poly_deg;
+    double alpha0[8];
+    memcpy(alpha0, h->poly_alpha, sizeof alpha0);
+    h->poly_deg = deg;
+    for (int i = 0; i < 8; i++) h->poly_alpha[i] = i <= deg ? coef[i] : 0.0;
+    rc = poly_apply(h, shift, v, out);
+    h->poly_deg = deg0;
+    memcpy(h->poly_alpha, alpha0, sizeof alpha0);
+    if (rc) return rc;
+    scalars[5] = (h->poly_fp32 && h->coef32 && fused_ok(h)) ? 1.0 : 0.0;
+    return download(h, out, layout, out_host);
+}
 extern "C" int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enable)
 {
     if (!h) return KSFD_EINVAL;

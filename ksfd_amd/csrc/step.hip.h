@@ -55,6 +55,17 @@ static void stats_end(ksfd_handle *h, const StepCounters &c0, ksfd_step_stats &s
     st.residual_evals = (int32_t)(h->n_residual - c0.resid);
 }
 
+// How the stages of an attempt are formed once its regime (use_spec, use_pc) is known; shared with the test entry ksfd_stage_rhs
+static void plan_stage_forms(const ksfd_handle *h, AttemptPlan &p)
+{
+    p.fuse_stage = (fused_ok(h) || (strip3d_ok(h) && h->rhs3d_strip)) && h->P.nlig <= 4 && h->fuse_stage;
+    // Initial guesses for the spectral stage solves from the earlier stages of the step (A Y_j = b_j is known): the right-hand
+    // sides of a step are nearly dependent -- b_1 = c b_0 to ~1e-3, later ones to a few per cent (CPU experiment with the oracle)
+    // -- so x0 = sum c_j Y_j, c = argmin ||b_i - sum c_j b_j||, starts the defect correction 1-3 digits ahead for one small
+    // multi-dot.  The b_j are kept in bstore (three vectors); stage_gram_guess keeps their Gram matrix.
+    p.guess_on = (p.use_spec || p.use_pc) && p.fuse_stage && h->spec_guess && h->bstore;
+}
+
 // Regime of one attempt with step size hh.  lam_done: the eigenvalue estimate of the polynomial is looked at once per step, not per attempt.
 static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, bool direct, bool dr_on, bool &lam_done, AttemptPlan &p)
 {
@@ -96,12 +107,7 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
     }
     p.use_async = ksfd_ctl::pipelined_allowed(in, r, p.use_poly);
     h->mg_use32 = opts->ksp_rtol >= 1e-7;          // fp32 level vectors inside the V cycle (mg_vcycle<float>); tight tolerances keep fp64
-    p.fuse_stage = (fused_ok(h) || (strip3d_ok(h) && h->rhs3d_strip)) && h->P.nlig <= 4 && h->fuse_stage;
-    // Initial guesses for the spectral stage solves from the earlier stages of the step (A Y_j = b_j is known): the right-hand
-    // sides of a step are nearly dependent -- b_1 = c b_0 to ~1e-3, later ones to a few per cent (CPU experiment with the oracle)
-    // -- so x0 = sum c_j Y_j, c = argmin ||b_i - sum c_j b_j||, starts the defect correction 1-3 digits ahead for one small
-    // multi-dot.  The b_j are kept in bstore (three vectors); stage_gram_guess keeps their Gram matrix.
-    p.guess_on = (p.use_spec || p.use_pc) && p.fuse_stage && h->spec_guess && h->bstore;
+    plan_stage_forms(h, p);
     return KSFD_OK;
 }
 

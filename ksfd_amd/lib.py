@@ -91,6 +91,18 @@ class MGLevelInfo(C.Structure):
                 ('ratio', C.c_double)]
 
 
+class StageInfo(C.Structure):
+    _fields_ = [('fuse_stage', C.c_int32), ('guess_on', C.c_int32), ('path', C.c_int32), ('rhs_strip', C.c_int32),
+                ('seg', C.c_int32), ('nseg', C.c_int32), ('nstrips', C.c_int32), ('rows', C.c_int32), ('overlap', C.c_int32),
+                ('dots_done', C.c_int32 * 4), ('guess_n', C.c_int32 * 4), ('bnorm2', C.c_double * 4), ('gb', C.c_double * 16),
+                ('guess_c', C.c_double * 16), ('wrms', C.c_double), ('below', C.c_double)]
+
+
+# regimes of ksfd_stage_rhs, operations of ksfd_stage_jvp, and the kernel paths both report
+STAGE_PLAIN, STAGE_SPECTRAL, STAGE_MULTIGRID = range(3)
+SJ_ACTION, SJ_RESIDUAL32, SJ_POLY = range(3)
+JP_STRIP2D, JP_LDS3D, JP_STRIP3D, JP_GENERIC = range(4)
+
 # parts of ksfd_mg_part (KSFD_MGP_*) and the kernel paths ksfd_mg_level_info reports
 MGP_COEF, MGP_RESTRICT, MGP_PROLONG_ADD, MGP_OPERATOR, MGP_DINV, MGP_DINV_APPLY, MGP_SMOOTH, MGP_CYCLE = range(8)
 MGP_TAIL = 8                                        # the coarse tail of set_mg_tail, at its first level
@@ -117,7 +129,7 @@ ABI_SYMBOLS = [
     'ksfd_spectral_apply', 'ksfd_set_spectral_params', 'ksfd_direct_apply', 'ksfd_banded_apply',
     'ksfd_set_deflation', 'ksfd_get_deflation_stats', 'ksfd_basis_rotate', 'ksfd_basis_capacity', 'ksfd_krylov_op',
     'ksfd_set_mg_agglomerate', 'ksfd_set_mg_coarse', 'ksfd_get_mg_coarse_info', 'ksfd_mg_coarse_apply', 'ksfd_mg_level_info', 'ksfd_mg_part',
-    'ksfd_set_mg_tail', 'ksfd_get_mg_tail_info',
+    'ksfd_set_mg_tail', 'ksfd_get_mg_tail_info', 'ksfd_stage_rhs', 'ksfd_stage_jvp',
 ]
 
 
@@ -196,6 +208,8 @@ def load():
     L.ksfd_mg_coarse_apply.argtypes = [vp, C.c_double, C.c_int32, dp, dp]
     L.ksfd_mg_level_info.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.POINTER(MGLevelInfo)]
     L.ksfd_mg_part.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp]
+    L.ksfd_stage_rhs.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, dp, dp, dp, C.POINTER(StageInfo), C.c_int32]
+    L.ksfd_stage_jvp.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, dp, dp, dp, dp, dp, C.c_int32]
     _lib = L
     return L
 
@@ -587,6 +601,45 @@ class KSFDHip:
         self._chk(self.L.ksfd_krylov_op(self.h, op, k, int(bool(want_norm)), _dp(c), float(alpha), float(beta), _dp(vecs), _dp(out), _dp(sc), layout))
         n = {KOP_MULTIDOT: k + 1, KOP_MULTIDOT_GRAM: 2 * k + 1}.get(op, 1 if want_norm else 0)
         return out, sc[:n]
+
+    def stage_rhs(self, regime, hstep, Y=None, nstages=4, finish=None, layout=SOA):
+        """the stage right-hand sides of one attempt through the functions the step calls (test entry, ksfd_stage_rhs): Y (nstages - 1,
+        nlocal) the caller's stage vectors, four of them with finish = (atol, rtol).  Returns (b (nstages, nlocal), info dict, fin) with
+        fin = None or (new state, error vector); info: fuse_stage, guess_on, path, rhs_strip, seg, nseg, nstrips, rows, overlap,
+        dots_done[4], guess_n[4], bnorm2[4], gb (4, 4), guess_c (4, 4), wrms, below."""
+        nstages = int(nstages)
+        ny = 4 if finish is not None else max(nstages - 1, 0)
+        yv = None
+        if Y is not None:
+            yv = np.ascontiguousarray(Y, dtype=np.float64).reshape(-1)
+            if 1 <= nstages <= 4 and yv.size != ny * self.nlocal:
+                raise ValueError('stage_rhs: expected %d stage vectors of %d doubles, got %d doubles' % (ny, self.nlocal, yv.size))
+        b = np.full((max(nstages, 1), self.nlocal), np.nan)
+        fin = np.full((2, self.nlocal), np.nan) if finish is not None else None
+        atol, rtol = finish if finish is not None else (0.0, 0.0)
+        s = StageInfo()
+        p = lambda a: None if a is None else _dp(a)
+        self._chk(self.L.ksfd_stage_rhs(self.h, int(regime), nstages, float(hstep), float(atol), float(rtol), p(yv), _dp(b), p(fin),
+                                        C.byref(s), layout))
+        info = dict(fuse_stage=bool(s.fuse_stage), guess_on=bool(s.guess_on), path=s.path, rhs_strip=bool(s.rhs_strip), seg=s.seg, nseg=s.nseg,
+                    nstrips=s.nstrips, rows=s.rows, overlap=bool(s.overlap), dots_done=[bool(x) for x in s.dots_done], guess_n=list(s.guess_n),
+                    bnorm2=list(s.bnorm2), gb=np.array(s.gb).reshape(4, 4), guess_c=np.array(s.guess_c).reshape(4, 4), wrms=s.wrms, below=s.below)
+        return b, info, (None if fin is None else (fin[0], fin[1]))
+
+    def stage_jvp(self, op, v, y=None, mode=1, shift=1.0, alpha=0.0, beta=0.0, coef=None, layout=SOA):
+        """one frozen Jacobian action at the resident state through the functions the solvers call (test entry, ksfd_stage_jvp).
+        SJ_ACTION: modes 0..4 of op_jvp_frozen_halo; SJ_RESIDUAL32: the fp32 residual y - A v with ||r||^2 from its epilogue;
+        SJ_POLY: sum_i coef[i] (A/shift)^i v by poly_apply.  Returns (out, dict(norm2, path, seg, nseg, nstrips, fp32, overlap, rows))."""
+        v = self._vec(v)
+        yv = self._vec(y) if y is not None else None
+        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1) if coef is not None else None
+        out = np.full(self.nlocal, np.nan)
+        sc = np.full(8, np.nan)
+        p = lambda a: None if a is None else _dp(a)
+        self._chk(self.L.ksfd_stage_jvp(self.h, int(op), int(mode), float(shift), float(alpha), float(beta), (c.size - 1) if c is not None else 0,
+                                        p(c), _dp(v), p(yv), _dp(out), _dp(sc), layout))
+        return out, dict(norm2=sc[0], path=int(sc[1]), seg=int(sc[2]), nseg=int(sc[3]), nstrips=int(sc[4]), fp32=bool(sc[5]),
+                         overlap=bool(sc[6]), rows=int(sc[7]))
 
     def set_spectral_params(self, from_stiffness=0.0, enable=-1):
         self._chk(self.L.ksfd_set_spectral_params(self.h, float(from_stiffness), int(enable)))

@@ -72,6 +72,9 @@ int main(int argc, char **argv)
         case 27: checkpoint_restored(c); break;
         case 28: q = graph_current(c, a, key(b), d != 0) ? 1 : 0; break;
         case 29: c = Current(); break;           /* a new handle */
+        case 30: stage_vectors_borrowed(c, a != 0); break;
+        case 31: { Current was; was.coef_fresh = ((int)a & 1) != 0; was.coef32_fresh = ((int)a & 2) != 0; was.means_valid = ((int)a & 4) != 0;
+                   derived_given_back(c, was); } break;
         default: return 4;
         }
         printf("%d %d %d %d %d %d %.17g %d %.17g %lld %d %.17g %d %d %d %d %d %d %d %d %d %d\n", c.coef_fresh, c.coef32_fresh, c.floor_ok, c.ckpt_floor_ok,
@@ -87,7 +90,7 @@ FIELDS = ('coef_fresh', 'coef32_fresh', 'floor_ok', 'ckpt_floor_ok', 'means_vali
 (START, STATE_WRITTEN, STATE_HANDED_OUT, STATE_GROOMED, PARAMS_CHANGED, PLANES_RECOMPUTED, COEF32_MADE, MEANS_COMPUTED, COARSE_PLANES_RESTRICTED,
  SHIFT_SETUP_DONE, COARSE_FACTORS_READY, COARSE_FACTORS_ENDED, GRAPH_CAPTURED, VCYCLE_CONFIG_CHANGED, HIERARCHY_FREED, HIERARCHY_BORROWED, POLY_SET_UP,
  POLY_CONFIG_CHANGED, KRYLOV_BASIS_OVERWRITTEN, RECYCLED_SPACES_DROPPED, RECYCLED_SPACE_KEPT, DR_RELATION_KEPT, STEP_BEGINS, ATTEMPT_BEGINS,
- COMPLETION_DONE, ERROR_VECTOR_FORMED, CHECKPOINT_SAVED, CHECKPOINT_RESTORED, GRAPH_CURRENT, NEW_HANDLE) = range(30)
+ COMPLETION_DONE, ERROR_VECTOR_FORMED, CHECKPOINT_SAVED, CHECKPOINT_RESTORED, GRAPH_CURRENT, NEW_HANDLE, STAGE_VECTORS_BORROWED, DERIVED_GIVEN_BACK) = range(32)
 
 
 def _cxx():
@@ -164,6 +167,11 @@ TABLE = [
     ((ERROR_VECTOR_FORMED,), dict(err_pending=0)),
     ((CHECKPOINT_SAVED,), dict()),
     ((CHECKPOINT_RESTORED,), dict(coef_fresh=0, have_err=0, err_pending=0)),    # floor_ok: the checkpoint's proof, true here
+    ((STAGE_VECTORS_BORROWED, 0), dict(dr_valid=0, have_err=0, err_pending=0)), # ksfd_stage_rhs: as an attempt that begins
+    ((STAGE_VECTORS_BORROWED, 1), dict(dr_valid=0, have_err=0, err_pending=0)), # ... with its own completion: no vector, stored or pending
+    ((DERIVED_GIVEN_BACK, 7), dict()),                                          # ksfd_stage_rhs / ksfd_stage_jvp found everything current: it stays
+    ((DERIVED_GIVEN_BACK, 6), dict(coef_fresh=0)),                              # ... found no planes: the ones it made are not the next step's
+    ((DERIVED_GIVEN_BACK, 1), dict(coef32_fresh=0, means_valid=0)),
     ((GRAPH_CURRENT, S0, 1, 0), dict(query=1)),
     ((GRAPH_CURRENT, 4.0, 1, 0), dict(query=0)),
     ((GRAPH_CURRENT, S0, 2, 0), dict(query=0)),
@@ -179,7 +187,7 @@ def _table_rows():
 
 
 def _check_table(out):
-    assert {ev[0] for ev, _ in TABLE} == set(range(1, 29)), 'an event has no row in the table'
+    assert {ev[0] for ev, _ in TABLE} == set(range(1, 29)) | {STAGE_VECTORS_BORROWED, DERIVED_GIVEN_BACK}, 'an event has no row in the table'
     for k, (ev, diff) in enumerate(TABLE):
         assert out[2 * k] == ALL_CURRENT, ev
         assert out[2 * k + 1] == {**ALL_CURRENT, **diff}, (ev, {f: v for f, v in out[2 * k + 1].items() if ALL_CURRENT[f] != v})
@@ -196,12 +204,16 @@ def test_events_that_depend_on_what_the_record_held(driver):
         (START, S0), (STATE_WRITTEN, 0), (CHECKPOINT_SAVED,), (STATE_GROOMED,), (CHECKPOINT_RESTORED,),     # 8: the proof of the saved state, not of the groomed one
         (START, S0), (CHECKPOINT_SAVED,), (PARAMS_CHANGED,), (STATE_GROOMED,), (CHECKPOINT_RESTORED,),      # 13: moved floors end the proof in the slot
         (START, S0), (STATE_HANDED_OUT,), (PLANES_RECOMPUTED, 0, 1),               # 16: pins the exception: the hand-out alone never makes ensure_coef run
+        (START, S0), (COMPLETION_DONE, 1), (STAGE_VECTORS_BORROWED, 0),            # 19: the test entry's stages alone leave a stored vector, as an attempt does
+        (START, S0), (COMPLETION_DONE, 1), (STAGE_VECTORS_BORROWED, 1),            # 22: its completion overwrote the stored vector: nothing to hand out
     ], 'cases')
     assert out[0] == {**{f: 0 for f in FIELDS}, 'mg_shift': -1, 'mg_graph_shift': -1, 'poly_shift': -1, 'query': -1}
     assert (out[3]['have_err'], out[3]['err_pending'], out[3]['dr_valid']) == (1, 0, 0)
     assert (out[6]['ckpt_floor_ok'], out[7]['floor_ok'], out[8]['floor_ok'], out[8]['coef_fresh']) == (0, 1, 0, 0)
     assert (out[11]['ckpt_floor_ok'], out[12]['floor_ok'], out[13]['floor_ok']) == (0, 1, 0)
     assert (out[15]['coef_fresh'], out[15]['floor_ok']) == (1, 0)
+    assert (out[19]['have_err'], out[19]['err_pending'], out[19]['dr_valid']) == (1, 0, 0)
+    assert (out[22]['have_err'], out[22]['err_pending'], out[22]['dr_valid']) == (0, 0, 0)
 
 
 # ---- (b) the model ------------------------------------------------------------------------------------------------------------------
@@ -248,7 +260,7 @@ def _sequence(rng, nev):
     coarse_ok = lambda: planes_ok() and m.is_current('coarse')
     setup_ok = lambda: coarse_ok() and 'setup' in m.built and m.is_current('setup', shift=m.built['setup']['shift'])
     for _ in range(nev):
-        k = int(rng.integers(0, 26))
+        k = int(rng.integers(0, 28))
         if k == 0:
             emit((STATE_WRITTEN, int(rng.integers(0, 2))), lambda: m.bump('state'))
         elif k == 1:
@@ -321,6 +333,10 @@ def _sequence(rng, nev):
             emit((CHECKPOINT_RESTORED,), lambda: m.bump('state'))
         elif k == 25:
             emit((ERROR_VECTOR_FORMED,))
+        elif k == 26:                                                        # ksfd_stage_rhs: an attempt of the entry's own
+            emit((STAGE_VECTORS_BORROWED, int(rng.integers(0, 2))), lambda: m.bump('attempt'))
+        elif k == 27:                                                        # ... which only ends what it made for itself
+            emit((DERIVED_GIVEN_BACK, int(rng.integers(0, 8))))
     return rows, checks
 
 
