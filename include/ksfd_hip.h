@@ -243,40 +243,57 @@ int ksfd_synchronize(ksfd_handle *h);
 /* raw kernel benchmark used by bench.py/profiles: run `reps` launches of one kernel class on the state,
  * timed with HIP events on the compute stream; returns average ms per launch. */
 int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, double *avg_ms, double *bytes_per_launch);
-/* use_fused: bit0 fused kernels, bit1 set = recompute (non-frozen) Jacobian action, bit2 set = no halo/compute overlap,
- * bit3 set = pipelined GMRES with device-resident Hessenberg/Givens state (off by default); its cycles are at most 32 iterations long,
- * which is what its kernels hold: a longer ksp_restart (and restart growth) runs as cycles of 32;
- * bit4 set = no Krylov recycling across the four stage systems of a step, bit5 set = recycle from every earlier stage
- * (default: from the stages measured to matter: 1 for 2 and 3, 1 and 3 for 4), bits 6-8 = leading Arnoldi vectors kept
- * per stage (1..4, 0 keeps the default 3); bit9 set = keep the polynomial preconditioner's temporaries and coefficient
- * copy in fp64 (default: fp32 storage inside p(A) only; the Krylov vectors, A z_j and the solution are fp64 always);
- * bit10 set = form the stage vectors with separate passes instead of inside the RHS kernel;
- * bit11 set = fetch reduction results with a stream synchronisation + copy instead of spinning on a flag the
- * reduction kernel raises in mapped host memory;
- * bit12 set = multigrid smoother as separate kernels instead of inside the Jacobian-action epilogues;
- * bit14 set = spectral stage solves start from zero instead of from the span of the earlier stage solutions of the step;
- * bit13 set = 3-D RHS through the generic one-thread-per-point stencil pass instead of the z-marching strip kernel;
- * bit15 set = the stage RHS kernel re-reads the stage vectors it adds at the store instead of carrying their combination along from
- * the window load; bit16 set = the spectral defect correction verifies every solve with a residual evaluation (no predicted last sweep);
- * bit17 set = GMRES keeps the restart length it was given (default: a cycle that ends without convergence is followed by one of twice
- * the length, up to the 30 ... 120 basis vectors ksfd_create found room for);
- * bit18 set = every multigrid set-up estimates the Chebyshev bound of a level by a cold power iteration (default: warm start from the
- * vector of the previous set-up, at most three iterations);
- * bit21 set = the inner products of a new stage right-hand side with the earlier ones (stage guesses) are a pass of their own instead of
- * part of the RHS kernel's store epilogue;
- * bit20 set = multigrid-preconditioned stage solves keep the whole first GMRES cycle of every stage and project the later stages of the step
- * on it first (experiment, measured slower: krylov.hip.h);
- * bit19 set = the V cycle keeps its level vectors in fp64 at every tolerance (default: fp32 level vectors when ksp_rtol >= 1e-7, 2-D);
- * bit22 set = the step boundary as it was before the passes nobody reads were taken out: groom at the head of every step (default: only
- * when a value can be under its floor), the embedded error vector stored by every completion (default: formed from the stage vectors
- * when ksfd_get_last_error_vector asks), the fp32 coefficient copy stored with the fp64 planes (default: converted when the polynomial
- * preconditioner or the V cycle first reads it).  Same results bit for bit; for tests and A/B timing;
- * bit23 set = the first stage's right-hand side evaluates G(u) itself (default, 2-D strip path: it loads G from the coefficient planes
- * the step has just made of the same state, which may differ from its own evaluation in the last bit);
- * yseg_*: rows per wave segment; <=0 keeps */
-int ksfd_set_tuning(ksfd_handle *h, int32_t use_fused, int32_t yseg_rhs, int32_t yseg_jvp);
+/* -- the tuning word of ksfd_set_tuning: one macro per bit or field, in bit order.  The encoding is frozen (callers pass stored words).
+ * Defaults: KSFD_TUNE_FUSED set, every other bit clear, three vectors kept per stage. */
+#define KSFD_TUNE_FUSED (1 << 0)             /* fused 2-D / strip kernels */
+#define KSFD_TUNE_RECOMPUTE_JVP (1 << 1)     /* recompute (non-frozen) Jacobian action */
+#define KSFD_TUNE_NO_OVERLAP (1 << 2)        /* no halo/compute overlap */
+#define KSFD_TUNE_ASYNC_GMRES (1 << 3)       /* pipelined GMRES with device-resident Hessenberg/Givens state; its cycles are at most 32 iterations
+                                              * long, which is what its kernels hold: a longer ksp_restart (and restart growth) runs as cycles of 32 */
+#define KSFD_TUNE_NO_RECYCLE (1 << 4)        /* no Krylov recycling across the four stage systems of a step (wins over the next bit) */
+#define KSFD_TUNE_RECYCLE_ALL (1 << 5)       /* recycle from every earlier stage (default: from the stages measured to matter: 1 for 2 and 3,
+                                              * 1 and 3 for 4) */
+#define KSFD_TUNE_REC_KEEP_MASK (7 << 6)     /* field: leading Arnoldi vectors kept per stage, KSFD_TUNE_REC_KEEP(1..4); 5..7 give 4; 0 keeps the
+                                              * count in force (3 on a new handle), unlike every other bit, which a word always replaces */
+#define KSFD_TUNE_REC_KEEP(v) (((v) & 7) << 6)
+#define KSFD_TUNE_POLY_FP64 (1 << 9)         /* the polynomial preconditioner's temporaries and coefficient copy in fp64 (default: fp32 storage
+                                              * inside p(A) only; the Krylov vectors, A z_j and the solution are fp64 always) */
+#define KSFD_TUNE_UNFUSED_STAGE (1 << 10)    /* stage vectors formed with separate passes instead of inside the RHS kernel */
+#define KSFD_TUNE_NO_ZERO_COPY (1 << 11)     /* reduction results fetched with a stream synchronisation + copy instead of spinning on a flag the
+                                              * reduction kernel raises in mapped host memory */
+#define KSFD_TUNE_UNFUSED_SMOOTHER (1 << 12) /* multigrid smoother as separate kernels instead of inside the Jacobian-action epilogues */
+#define KSFD_TUNE_GENERIC_RHS3D (1 << 13)    /* 3-D RHS through the generic one-thread-per-point stencil pass instead of the z-marching strip kernel */
+#define KSFD_TUNE_NO_SPEC_GUESS (1 << 14)    /* spectral stage solves start from zero instead of from the span of the earlier stage solutions */
+#define KSFD_TUNE_NO_RHS_CARRY (1 << 15)     /* the stage RHS kernel re-reads the stage vectors it adds at the store instead of carrying their
+                                              * combination along from the window load */
+#define KSFD_TUNE_NO_SPEC_PREDICT (1 << 16)  /* the spectral defect correction verifies every solve with a residual evaluation (no predicted last sweep) */
+#define KSFD_TUNE_NO_RESTART_GROWTH (1 << 17) /* GMRES keeps the restart length it was given (default: a cycle that ends without convergence is
+                                              * followed by one of twice the length, up to the 30 ... 120 basis vectors ksfd_create found room for) */
+#define KSFD_TUNE_COLD_POWER (1 << 18)       /* every multigrid set-up estimates the Chebyshev bound of a level by a cold power iteration (default:
+                                              * warm start from the vector of the previous set-up, at most three iterations) */
+#define KSFD_TUNE_MG_FP64 (1 << 19)          /* the V cycle keeps its level vectors in fp64 at every tolerance (default: fp32 level vectors when
+                                              * ksp_rtol >= 1e-7, 2-D) */
+#define KSFD_TUNE_REC_MG (1 << 20)           /* multigrid-preconditioned stage solves keep the whole first GMRES cycle of every stage and project the
+                                              * later stages of the step on it first (experiment, measured slower: krylov.hip.h) */
+#define KSFD_TUNE_OWN_DOTS (1 << 21)         /* the inner products of a new stage right-hand side with the earlier ones (stage guesses) are a pass of
+                                              * their own instead of part of the RHS kernel's store epilogue */
+#define KSFD_TUNE_OLD_BOUNDARY (1 << 22)     /* the step boundary as it was before the passes nobody reads were taken out: groom at the head of every
+                                              * step (default: only when a value can be under its floor), the embedded error vector stored by every
+                                              * completion (default: formed from the stage vectors when ksfd_get_last_error_vector asks), the fp32
+                                              * coefficient copy stored with the fp64 planes (default: converted when the polynomial preconditioner or
+                                              * the V cycle first reads it).  Same results bit for bit; for tests and A/B timing */
+#define KSFD_TUNE_NO_GPLANE (1 << 23)        /* the first stage's right-hand side evaluates G(u) itself (default, 2-D strip path: it loads G from the
+                                              * coefficient planes the step has just made of the same state, which may differ in the last bit) */
+/* word < 0 changes no switch.  Any other word replaces EVERY switch above: a clear bit means its default, not "keep" -- except the
+ * KSFD_TUNE_REC_KEEP field, where 0 keeps.  A word that toggles KSFD_TUNE_UNFUSED_SMOOTHER ends the multigrid shift set-up; no other bit
+ * invalidates anything.  KSFD_TUNE_NO_ZERO_COPY clear has an effect only where the handle could map its result buffer.
+ * yseg_*: rows per wave segment; <= 0 keeps */
+int ksfd_set_tuning(ksfd_handle *h, int32_t word, int32_t yseg_rhs, int32_t yseg_jvp);
 /* multigrid knobs (<=0 keeps): smoothing sweeps per side, cap on coarsest-grid sweeps, power iterations for the
- * Chebyshev bound, smoothing interval ratio lambda_max/lambda_min, coarsest-grid reduction target */
+ * Chebyshev bound, smoothing interval ratio lambda_max/lambda_min, coarsest-grid reduction target.
+ * power_its = KSFD_MG_EAGER keeps the count and launches the coarse part of the V cycle kernel by kernel (debug / A-B timing); EVERY other
+ * call of this entry, whatever it sets, goes back to replaying the captured graph (handles with a halo transport never capture) */
+#define KSFD_MG_EAGER (-7)
 int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_max, int32_t power_its, double ratio, double coarse_tol);
 /* Coarse solve of the multigrid V cycle.
  * kind 0: Chebyshev on the coarsest level (default, bit-for-bit the cycle without this call; max_unknowns is ignored);
@@ -356,7 +373,7 @@ int ksfd_mg_coarse_apply(ksfd_handle *h, double shift, int32_t op, const double 
  * the level of an exact coarse solve).
  *   path: 0 2-D strip kernel, 2 3-D strip kernel, 3 generic kernel (what mg_path picks)
  *   f32: the level has fp32 level vectors;  coef32: bit 0 = the operator of the fp64 cycle reads an fp32 coefficient copy (level 0, unless
- *   tuning bit 9 is set), bit 1 = the level has such a copy (the fp32 cycle reads it);  can_fuse: mg_can_fuse holds
+ *   KSFD_TUNE_POLY_FP64 is set), bit 1 = the level has such a copy (the fp32 cycle reads it);  can_fuse: mg_can_fuse holds
  *
  * ksfd_mg_part: `level` is the level the part runs on; transfers run between `level` (fine) and level + 1.
  *   COEF         out0 = the 3 + nlig coefficient planes the level's operator reads, after ensure_coef + mg_restrict_coefs; out1 (may be
@@ -419,8 +436,8 @@ int ksfd_banded_apply(ksfd_handle *h, double shift, const double *v, double *out
  * keep > ksp_restart - 3.  carry_stages != 0: the relation kept at the end of a stage solve also serves the later stage systems of the
  * same step attempt (same matrix); it never crosses an attempt, a step or ksfd_checkpoint.
  * With deflation on, the solves pc_type selects as plain, multigrid-preconditioned or polynomial-preconditioned GMRES run deflated: the
- * restart length is ksp_restart and stays fixed (no restart growth), Krylov recycling across stages and the pipelined solver (tuning bits
- * 3-8, 20) are bypassed, the V cycle preconditions flexibly like the polynomial (z_j kept: the cycle is not a linear operator), and a
+ * restart length is ksp_restart and stays fixed (no restart growth), Krylov recycling across stages and the pipelined solver (the tuning
+ * word's KSFD_TUNE_ASYNC_GMRES ... KSFD_TUNE_REC_KEEP_MASK and KSFD_TUNE_REC_MG) are bypassed, the V cycle preconditions flexibly like the polynomial (z_j kept: the cycle is not a linear operator), and a
  * solve returns KSFD_OK only on the TRUE residual b - A x, never on the recurrence alone: it must meet the tolerance, or -- unpreconditioned
  * solves only -- exceed it by no more than an estimate of the rounding error of evaluating it, nnz_row * u * ||A|| ||x||, and by no more than
  * a quarter of the tolerance; such solves are counted in rounding_passes and report their residual in ksp_resid.  The spectral defect correction with its fallbacks and the direct solver (pc_type 5) are untouched. */
@@ -481,8 +498,8 @@ int ksfd_krylov_op(ksfd_handle *h, int32_t op, int32_t k, int32_t want_norm, con
  * Y_0 .. Y_{nstages-2} are the caller's (y_host, one after the other; with fin_host: four), formed in order exactly as step_attempt forms
  * them, with the stage guesses' Gram bookkeeping wherever the attempt would keep it.  regime 0: plain (no norm, no guess); 1: spectral
  * (||b_i||^2 and, with guesses, <b_i, b_j> from the store epilogue of the 2-D strip kernel); 2: multigrid (guesses, inner products by
- * a multi-dot).  Whether the stage algebra is fused and whether guesses are on follows the rules of the step (tuning bits 10, 13, 14, 15,
- * 21, 23 and the handle's solvers).  b_host receives nstages vectors.  fin_host != NULL (nstages = 4, four Y vectors): step_finish with
+ * a multi-dot).  Whether the stage algebra is fused and whether guesses are on follows the rules of the step (KSFD_TUNE_UNFUSED_STAGE,
+ * _GENERIC_RHS3D, _NO_SPEC_GUESS, _NO_RHS_CARRY, _OWN_DOTS, _NO_GPLANE and the handle's solvers).  b_host receives nstages vectors.  fin_host != NULL (nstages = 4, four Y vectors): step_finish with
  * atol / rtol, then err_materialize; fin_host receives the new state (from the completion's output buffer; the state is not advanced) and
  * the embedded error vector, info wrms and below.  The stage vectors, the stored right-hand sides and the error vector buffer are
  * overwritten: ksfd_get_last_error_vector afterwards answers as after a step that completed no attempt. */
@@ -507,10 +524,10 @@ int ksfd_stage_rhs(ksfd_handle *h, int32_t regime, int32_t nstages, double hstep
  *   op 1: op_residual32(x = v, shift, b = y): out = the fp32 values of b - A x widened to double, scalars[0] = ||r||^2 from the store
  *         epilogue; KSFD_EINVAL where the spectral solver would not take the fused residual (no strip kernel on the grid)
  *   op 2: out = poly_apply(v) with the polynomial sum_i coef[i] (A/shift)^i, i = 0 .. deg (deg 1..7), installed for the call and put back
- *         afterwards; fp32 or fp64 Horner temporaries exactly as the handle would take them (tuning bit 9)
+ *         afterwards; fp32 or fp64 Horner temporaries exactly as the handle would take them (KSFD_TUNE_POLY_FP64)
  * scalars (8 doubles): [0] see op 1; [1] path as in ksfd_stage_info; [2] rows (2-D) or planes (3-D) per segment of the launch, [3] segments,
  * [4] strips, [5] 1 where op 2 took the fp32 path, [6] 1 where the launches were interior + boundary (ghost rows of v travelling), [7] y rows
- * per block (3-D).  Needs the frozen action (tuning bit 1 clear), else KSFD_EINVAL. */
+ * per block (3-D).  Needs the frozen action (KSFD_TUNE_RECOMPUTE_JVP clear), else KSFD_EINVAL. */
 int ksfd_stage_jvp(ksfd_handle *h, int32_t op, int32_t mode, double shift, double alpha, double beta, int32_t deg, const double *coef,
                    const double *v_host, const double *y_host, double *out_host, double *scalars, int32_t layout);
 /* ksfd_bench_kernel classes beyond the profile's kernel classes: the rotation kernel on 31 -> 11 vectors in one pass, and the same

@@ -45,8 +45,7 @@ static int banded_alloc(ksfd_handle *h)
     ok = ok && hipMalloc((void **)&S.val, sizeof(double) * (size_t)nnz) == hipSuccess;
     ok = ok && hipMalloc((void **)&S.z, sizeof(double) * (size_t)B.n) == hipSuccess;
     // one wave up to three fields (no barrier between the phases of a column), four waves above; KSFD_BAND_THREADS: timing knob
-    int nt = B.F <= 3 ? 64 : 256;
-    if (getenv("KSFD_BAND_THREADS")) nt = atoi(getenv("KSFD_BAND_THREADS")) >= 256 ? 256 : 64;
+    const int nt = env_knobs().band_threads ? env_knobs().band_threads : (B.F <= 3 ? 64 : 256);
     const size_t lds = sizeof(double) * (size_t)band_factor_lds(B);
     ok = ok && (nt == 64 ? banded_factor_attr<64>(lds) : banded_factor_attr<256>(lds)) == hipSuccess;
     if (!ok) {

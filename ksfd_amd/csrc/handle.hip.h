@@ -3,6 +3,8 @@
 #pragma once
 #include "spectral_plan.h"
 #include "handle_state.h"
+#include "tuning.h"
+#include "krylov_small.h"
 // ------------------------------------------------------------------------------------------------
 // kernel classes for the profile
 enum { KC_RHS = 0, KC_JVP, KC_MULTIDOT, KC_GSUPDATE, KC_LINCOMB, KC_BASISAXPY, KC_FINISH, KC_REDUCE,
@@ -137,7 +139,6 @@ struct ksfd_handle {
     hipStream_t st = nullptr;
     hipStream_t st_comm = nullptr;            // halo exchange stream (overlapped with interior rows)
     hipEvent_t ev_ready = nullptr, ev_halo = nullptr;
-    bool overlap = true;
     Transport *tr = nullptr;
     std::string err;
 
@@ -149,12 +150,7 @@ struct ksfd_handle {
     // either pointer across a step
     double *ckpt = nullptr;                 // ksfd_checkpoint slot (allocated on first save)
     double *bstore = nullptr;               // right-hand sides of stages 0..2 of the current step (initial guesses of the spectral solves)
-    bool spec_guess = true;
-    // earlier stages a stage guess is built from (the most recent ones).  Measured on the pinned window at 4096^2: 3 vectors 9.80 ms per step,
-    // 2 vectors 9.67 (same sweep counts, two full-vector reads and a multi-dot operand less for stage 4), 1 vector 9.75 (one more sweep)
-    int guess_max = getenv("KSFD_GUESS_MAX") ? std::max(1, std::min(atoi(getenv("KSFD_GUESS_MAX")), 3)) : 2;
-    bool spec_predict = true;               // predicted last sweep of the defect correction (spec_solve)
-    long long n_predicted = 0;              // ... how many solves ended that way
+    long long n_predicted = 0;              // spectral solves that ended with a predicted last sweep (spec_solve)
     long long n_residual = 0;               // true residuals evaluated by the spectral defect correction
     long long n_host_sync = 0;              // host waits on the device so far (reduction results, stream synchronisations)
     SpecState spec;
@@ -165,31 +161,23 @@ struct ksfd_handle {
     bool ckpt_valid = false;
     double *Gb = nullptr, *dGb = nullptr;   // generic-path scratch planes
     double *coef = nullptr;                 // frozen-Jacobian coefficient planes [rho, G, G_rho, G_U..]
-    bool use_frozen = true;
     // which of the derived data below still belongs to the state and the configuration as they are now: handle_state.h, whose events
     // are the only writers
     ksfd_ctl::Current cur;
-    bool old_boundary = false;              // KSFD_TUNE bit 22: groom every step, error vector stored by the completion, fp32 coefficient copy made by k_jcoef
-    bool rhs_gplane = true;                 // stage-0 RHS of the 2-D strip path takes G from plane 1 of coef (KSFD_TUNE bit 23 clears)
     double *flat = nullptr;                 // staging for host layouts: max(F,dim)*nloc
     double *src[4][KSFD_MAXL + 1];          // dense source planes per stage (lazy)
     double *part = nullptr;                 // block partials
     double *dres = nullptr;                 // reduced results (device)
     double *hres = nullptr;                 // pinned host mirror
     // zero-copy hand-over of reduction results: the kernel stores into hres through its device alias and raises pub_flag
-    double *hres_dev = nullptr;
+    double *hres_dev = nullptr;             // NULL: the buffer could not be mapped (zero_copy_on)
     unsigned long long *pub_flag = nullptr, *pub_flag_dev = nullptr, pub_seq = 0;
     unsigned int *pub_count = nullptr;
-    bool zero_copy = true;
     int restart_alloc = 0;                  // basis vectors V / Zb hold (ksfd_create: 30 ... 120 by the free HBM)
-    bool restart_grow = true;               // a GMRES cycle that ends without convergence is followed by one of twice the length (KSFD_TUNE bit 17 switches it off)
     int nblk_vec = 0;                       // grid.x of the BLAS-1 kernels
 
-    // tuning
-    int use_fused = 1;
-    int yseg = 48;        // rows per wave segment, RHS kernel (tools/kbench.py at 4096^2 with the hand-rolled log/exp: 8: 0.253, 16: 0.222, 32: 0.198, 64: 0.190 ms)
-    int yseg_jvp = 16;    // same for the Jacobian-action kernels
-    int zseg = 32;        // planes per wave segment, 3-D z-marching kernel
+    // the switches between code paths (tuning.h): ksfd_set_tuning and ksfd_set_mg_params write them, through tuning_apply / tuning_mg_graph only
+    ksfd_ctl::Tuning tune;
 
     // profile
     bool profiling = false;
@@ -203,8 +191,6 @@ struct ksfd_handle {
     double *gm_dev = nullptr;       // [G (m+1)^2 | H (m+1)m | cs m | sn m | g m+1 | coef MAXDOT | scale 1 | mon 2(m+1)]
     double *gm_host = nullptr;      // pinned: [mon 2(m+1) | H (m+1)m | g m+1]
     std::vector<hipEvent_t> gm_ev;
-    int async_mode = 0;             // 0 off (default: measured no gain on one GPU, tools/async_bench.py), 1 whenever legal,
-                                    // 2 when the local problem is small
 
     // polynomial (Chebyshev) preconditioner + flexible GMRES (see poly_setup / gmres)
     double *Zb = nullptr;           // preconditioned basis z_j = p(A) v_j (allocated on first use)
@@ -215,11 +201,8 @@ struct ksfd_handle {
     double mg_threshold = 75.0;      // stiffness above which pc_type 2 switches from the polynomial to multigrid
     double poly_target = 0.02;      // wanted reduction per outer iteration (picks the degree)
     float *coef32 = nullptr;        // fp32 copy of the frozen coefficient planes (2-D strip path only)
-    bool rhs_carry = true;          // stage vectors that enter both sides of a stage RHS are read once (k_rhs2d_fused<NL, true>); KSFD_TUNE bit 15 switches it off
-    bool fuse_stage = true;         // stage-vector algebra inside the RHS kernel (2-D strip path; 3-D: inside the G pass + strip kernel)
+    bool coef32_failed = false;     // its allocation failed: coef32_alloc does not try again until ksfd_set_tuning passes a word
     bool j3l_attr_set = false, j3l_usable = false;   // k_jvp3d_lds: dynamic LDS size registered / usable (ops.hip.h: j3l_ok)
-    bool rhs3d_strip = true;        // 3-D RHS: G pass + z-marching strip kernel (false: generic one-thread-per-point stencil pass)
-    bool poly_fp32 = true;          // Horner temporaries and coefficients of p(A) in fp32 storage (the outer A z_j stays fp64)
 
     // asynchronous snapshots for writers (ksfd_snapshot_begin / _wait): layout transform on the compute stream into a
     // device staging slot, D2H on a third stream into pinned memory while the stepper carries on
@@ -232,10 +215,6 @@ struct ksfd_handle {
     // Krylov recycling across the four stage systems of one step (same matrix): see gmres()
     struct RecSpace { int vb = 0, zb = 0, k = 0, pc = 0; std::vector<double> H; };   // leading (k+1) x k raw Hessenberg, ld = k+1; in force while cur.rec_valid[stage]
     RecSpace rec[4];
-    int rec_mode = 1;                // 0 off, 1 selected earlier stages (default), 2 every earlier stage
-    int rec_keep = 3;                // leading vectors kept per stage (<= 4)
-    bool rhs_dots = true;            // inner products for the stage guesses from the RHS kernel's store epilogue (KSFD_TUNE bit 21 clears)
-    bool rec_mg = false;             // multigrid-preconditioned solves: the WHOLE first cycle of every stage is kept for the later stages of the step (KSFD_TUNE bit 20 sets; measured: no gain, see gmres)
 
     // Deflated restart of GMRES (krylov_dr.hip.h; ksfd_set_deflation).  keep = 0: off, every other solver path is as without it.
     int dr_keep = 0;                 // harmonic Ritz vectors kept across a restart (1..16)
@@ -253,16 +232,12 @@ struct ksfd_handle {
 
     // multigrid preconditioner
     std::vector<MGLevel> mg;
-    bool sf_auto = true;         // online search for memo.mg_shift_floor (shift_floor_update); KSFD_PC_SIGMA fixes the floor instead
-    bool mg_fp32 = true;         // V cycle with fp32 level vectors when the solve tolerance allows (KSFD_TUNE bit 19 clears); see mg_vcycle
-    bool mg_use32 = false;       // ... decided per step by ksfd_step (ksp_rtol >= 1e-7)
-    bool mg_warm_power = true;   // power iteration of a level starts from the vector of the previous set-up (KSFD_TUNE bit 18 clears)
-    bool mg_fuse = true;         // smoother algebra inside the Jacobian-action epilogues (modes 5/6)
+    bool mg_use32 = false;       // V cycle with fp32 level vectors: decided per step by ksfd_step (tune.mg_fp32 and ksp_rtol >= 1e-7)
     bool mg_ok = false;          // hierarchy exists (2-D, single rank, >= 2 levels)
     int64_t mg_agg = 0;          // slab ranks: 0 = every level distributed; > 0: coarse levels replicated (mg_agglomerate_plan.h)
     hipGraphExec_t mg_graph = nullptr;   // captured coarse part of the V cycle (levels >= 1) under the key in cur (graph_current)
     double mg_graph_bytes = 0.0;
-    bool capturing = false, mg_use_graph = true;
+    bool capturing = false;
     int mg_nu = 2, mg_ncoarse = 400, mg_power_its = 8;   // smoothing sweeps, cap on coarsest-grid sweeps, power iterations
     double mg_ratio = 6.0, mg_coarse_tol = 0.3;    // coarsest-grid reduction target: 0.3 is enough (tools/mg_longrun_tune.py: 24.3 -> 19.9 ms/step at 384^2, same iterations)
 
@@ -271,6 +246,52 @@ struct ksfd_handle {
 };
 
 #define GAMMA_RA 4.3586652150845900e-01
+
+// a switch of tune that also takes a fact about the handle.  Reduction results through the mapped flag: the buffer is mapped
+static inline bool zero_copy_on(const ksfd_handle *h) { return h->tune.zero_copy && h->hres_dev; }
+// fp32 copy of the coefficient planes read by the polynomial and by level 0 of the V cycle: the buffer exists (ops.hip.h: coef32_alloc)
+static inline bool coef32_on(const ksfd_handle *h) { return h->tune.poly_fp32 && h->coef32; }
+// coarse part of the V cycle from a captured graph: not on slab ranks, whose cycle has collectives inside
+static inline bool mg_graph_on(const ksfd_handle *h) { return h->tune.mg_use_graph && !h->ring; }
+
+// The environment knobs outside the spectral planner's (spec_knobs, spectral_host.hip.h) and the transport's KSFD_VRED_MAX (transport.h,
+// per transport), read here and nowhere else, once per process at first use.  All are experiment or diagnostic knobs
+struct EnvKnobs {
+    long long waves_jvp = 4096, waves_rhs = 6144;   // KSFD_WAVES_JVP / _RHS: wave target of the 2-D strip launches (tools/yseg_sweep.py)
+    int rows3d = 0;                 // KSFD_ROWS3D = 8: eight y rows per block of the 3-D strip kernels (one ligand), else four
+    int sync3d = 1;                 // KSFD_SYNC3D = 0: no barrier per plane in the 3-D strip kernels
+    int j3l = 1;                    // KSFD_J3L = 0: the first-generation 3-D Jacobian action where k_jvp3d_lds would serve
+    int spec_verify = 0;            // KSFD_SPEC_VERIFY: 1 checks the predicted sweeps, 2 switches them off (step_control.h: spec_predict_on)
+    bool spec_trace = false;        // KSFD_SPEC_TRACE: residual history of the defect correction on stderr
+    bool stage_trace = false;       // KSFD_STAGE_TRACE: iterations per stage system on stderr
+    int restart_cap = ksfd_krylov::RESTART_MAX;     // KSFD_RESTART_MAX: cap on the basis vectors ksfd_create sizes V / Zb for
+    // KSFD_GUESS_MAX (1..3): earlier stages a stage guess is built from (the most recent ones).  Measured on the pinned window at 4096^2: 3 vectors 9.80 ms
+    // per step, 2 vectors 9.67 (same sweep counts, two full-vector reads and a multi-dot operand less for stage 4), 1 vector 9.75 (one more sweep)
+    int guess_max = 2;
+    bool pc_sigma_set = false;      // KSFD_PC_SIGMA: fixed shift floor of the multigrid preconditioner instead of the online search
+    double pc_sigma = 0.0;
+    int band_threads = 0;           // KSFD_BAND_THREADS: workgroup of k_band_factor, 256 (>= 256) or 64; 0: banded_factor's own choice
+};
+static const EnvKnobs &env_knobs()
+{
+    static const EnvKnobs K = [] {
+        EnvKnobs E;
+        if (const char *v = getenv("KSFD_WAVES_JVP")) E.waves_jvp = atoll(v);
+        if (const char *v = getenv("KSFD_WAVES_RHS")) E.waves_rhs = atoll(v);
+        if (const char *v = getenv("KSFD_ROWS3D")) E.rows3d = atoi(v);
+        if (const char *v = getenv("KSFD_SYNC3D")) E.sync3d = atoi(v);
+        if (const char *v = getenv("KSFD_J3L")) E.j3l = atoi(v);
+        if (const char *v = getenv("KSFD_SPEC_VERIFY")) E.spec_verify = atoi(v);
+        E.spec_trace = getenv("KSFD_SPEC_TRACE") != nullptr;
+        E.stage_trace = getenv("KSFD_STAGE_TRACE") != nullptr;
+        if (const char *v = getenv("KSFD_RESTART_MAX")) E.restart_cap = ksfd_krylov::restart_cap(atoi(v));
+        if (const char *v = getenv("KSFD_GUESS_MAX")) E.guess_max = std::max(1, std::min(atoi(v), 3));
+        if (const char *v = getenv("KSFD_PC_SIGMA")) { E.pc_sigma_set = true; E.pc_sigma = atof(v); }
+        if (const char *v = getenv("KSFD_BAND_THREADS")) E.band_threads = atoi(v) >= 256 ? 256 : 64;
+        return E;
+    }();
+    return K;
+}
 
 static int fail(ksfd_handle *h, int code, const char *fmt, ...)
 {

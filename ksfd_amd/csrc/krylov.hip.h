@@ -53,7 +53,7 @@ static int poly_apply(ksfd_handle *h, double shift, double *v, double *z)
     const int d = h->poly_deg;
     const double *al = h->poly_alpha;
     if ((rc = ensure_coef32(h))) return rc;                  // first application since the planes were made: the fp32 copy is formed here
-    if (h->poly_fp32 && h->coef32 && fused_ok(h)) {
+    if (coef32_on(h) && fused_ok(h)) {
         // mixed precision: the Horner temporaries and the coefficient planes live in fp32 (half the traffic of every
         // application but the arithmetic stays fp64); v is read and z written in fp64.  p(A) becomes a slightly
         // different fixed linear operator, which flexible GMRES does not care about: w_j = A z_j is computed in fp64
@@ -112,7 +112,7 @@ static int apply_AMinv(ksfd_handle *h, const double *ustate, double shift, doubl
         if ((rc = pcmode == 1 ? mg_precond(h, shift_pc, vj, z) : pcmode == 3 ? spec_apply(h, shift, vj, z) : poly_apply(h, shift, vj, z))) return rc;
         return op_jvp_frozen_halo(h, z, 1, shift, w);
     }
-    if (h->use_frozen) return op_jvp_frozen_halo(h, vj, 1, shift, w);
+    if (h->tune.use_frozen) return op_jvp_frozen_halo(h, vj, 1, shift, w);
     return (rc = halo(h, vj)) ? rc : op_jvp(h, ustate, vj, 1, shift, w);
 }
 
@@ -187,7 +187,7 @@ static int rhs_norm(ksfd_handle *h, GmresRun &R, const double *b)
     int rc;
     if (R.rec_on && R.stage > 0)
         for (int q = 0; q < R.stage; q++)
-            if (ksfd_krylov::recycle_uses(R.stage, q, h->rec_mode, R.rec_full) && h->cur.rec_valid[q] && h->rec[q].pc == R.pcmode) R.spaces.push_back(q);
+            if (ksfd_krylov::recycle_uses(R.stage, q, h->tune.rec_mode, R.rec_full) && h->cur.rec_valid[q] && h->rec[q].pc == R.pcmode) R.spaces.push_back(q);
     if (R.spaces.empty()) {
         if ((rc = op_multidot(h, b, R.V, 0))) return rc;
         R.bn = sqrt(h->hres[0]);
@@ -290,7 +290,7 @@ static int update_x(ksfd_handle *h, GmresRun &R, double *x, int j, const double 
 static void recycle_keep(ksfd_handle *h, const GmresRun &R, int j, const double *Hraw, int ld)
 {
     ksfd_handle::RecSpace &S = h->rec[R.stage];
-    S.k = R.rec_full ? j : std::min(j, std::min(h->rec_keep, 4));
+    S.k = R.rec_full ? j : std::min(j, std::min(h->tune.rec_keep, 4));
     S.vb = R.vb; S.zb = R.zb; S.pc = R.pcmode;
     S.H.assign((size_t)(S.k + 1) * S.k, 0.0);
     for (int c = 0; c < S.k; c++)
@@ -316,7 +316,7 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
     const int m_opt = std::min(o->ksp_restart > 0 ? o->ksp_restart : 30, h->restart_alloc);
     const int maxit = o->ksp_max_it > 0 ? o->ksp_max_it : 2000;
     const int64_t vs = h->vlen;
-    const ksfd_krylov::RecycleChoice rcy = ksfd_krylov::recycle_decide(pcmode, stage, h->rec_mode, h->rec_mg, h->use_frozen, h->restart_alloc, h->cur.rec_vtop);
+    const ksfd_krylov::RecycleChoice rcy = ksfd_krylov::recycle_decide(pcmode, stage, h->tune.rec_mode, h->tune.rec_mg, h->tune.use_frozen, h->restart_alloc, h->cur.rec_vtop);
     // this solve builds in V: a relation kept by the deflated solver (krylov_dr.hip.h) is gone, the recycled spaces unless it builds behind them
     ksfd_ctl::krylov_basis_overwritten(h->cur, !rcy.reset);
     R.rec_on = rcy.rec_on; R.rec_full = rcy.rec_full;
@@ -350,7 +350,7 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
         // V0 = r / beta
         if (first) { const double *xs[1] = { R.rsrc }; double a[1] = { 1.0 / R.beta }; if ((rc = op_lincomb(h, 1, xs, a, V))) return rc; }
         else {
-            if ((rc = halo(h, x)) || (rc = h->use_frozen ? op_jvp_frozen(h, x, 1, shift, V) : op_jvp(h, ustate, x, 1, shift, V))) return rc;     // V0 = A x
+            if ((rc = halo(h, x)) || (rc = h->tune.use_frozen ? op_jvp_frozen(h, x, 1, shift, V) : op_jvp(h, ustate, x, 1, shift, V))) return rc;     // V0 = A x
             const double *xs[2] = { b, V }; double a[2] = { 1.0, -1.0 };
             if ((rc = op_lincomb(h, 2, xs, a, V))) return rc;                                  // r = b - A x
             if ((rc = op_multidot(h, V, V, 0))) return rc;
@@ -386,7 +386,7 @@ static int gmres(ksfd_handle *h, const double *ustate, double shift, const doubl
         first = false;
         if (done || total >= maxit) break;
         restarted = true;
-        m_cur = ksfd_krylov::cycle_next(m_cur, m, h->restart_grow);
+        m_cur = ksfd_krylov::cycle_next(m_cur, m, h->tune.restart_grow);
     }
     if (!R.x_set) HIPCHK(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)vs, h->st));
     ls->its = total;
@@ -447,8 +447,8 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
     // result (a Jacobian action, 40 % of a sweep, whose only purpose would be to confirm a number 1-2 decades below the tolerance).  Every
     // other residual is the true fp64 one, as before.  Off for tight tolerances (ksp_rtol < 1e-8: the parity tests verify every solve),
     // with opts.reserved bit 3, and with KSFD_SPEC_VERIFY=1, which also evaluates and reports the residual the prediction stood in for.
-    static const int verify_env = getenv("KSFD_SPEC_VERIFY") ? atoi(getenv("KSFD_SPEC_VERIFY")) : 0;
-    const bool predict = ksfd_ctl::spec_predict_on(h->spec_predict, o->reserved, o->ksp_rtol, verify_env);
+    const int verify_env = env_knobs().spec_verify;
+    const bool predict = ksfd_ctl::spec_predict_on(h->tune.spec_predict, o->reserved, o->ksp_rtol, verify_env);
     bool final_sweep = false, slow = false;
     for (int k = 0; k < maxit && !slow; k++) {
         if (k == 0) rc = spec_apply(h, shift, b, x, nullptr, nullptr, guess);
@@ -470,8 +470,7 @@ static int spec_solve(ksfd_handle *h, double shift, const double *b, double *x, 
         h->n_residual++;
         rn = sqrt(h->hres[0]);
         {
-            static const bool trace = getenv("KSFD_SPEC_TRACE") != nullptr;        // residual history of the defect correction (diagnostics)
-            if (trace) fprintf(stderr, "[spec] sweep %d rel %.3e%s\n", k, rn / bn, (k == 0 && guess) ? " (guess)" : "");
+            if (env_knobs().spec_trace) fprintf(stderr, "[spec] sweep %d rel %.3e%s\n", k, rn / bn, (k == 0 && guess) ? " (guess)" : "");
         }
         switch (ksfd_ctl::spec_sweep(k, maxit, rn, rprev, tol, guess != nullptr, predict, h->memo)) {
         case ksfd_ctl::SPEC_NOT_FINITE: return fail(h, KSFD_ENAN, "spectral solve: residual is not finite");

@@ -62,7 +62,7 @@ static int gmres_dr(ksfd_handle *h, const double *ustate, double shift, const do
     auto true_residual = [&](double *r) -> int {           // r = b - A x
         int q;
         if ((q = halo(h, x))) return q;
-        if (h->use_frozen) return op_jvp_frozen(h, x, 2, shift, r, b);
+        if (h->tune.use_frozen) return op_jvp_frozen(h, x, 2, shift, r, b);
         if ((q = op_jvp(h, ustate, x, 1, shift, r))) return q;
         const double *xs[2] = { b, r }; double a[2] = { 1.0, -1.0 };
         return op_lincomb(h, 2, xs, a, r);

@@ -123,7 +123,7 @@ static inline bool recycle_uses(int stage, int q, int rec_mode, bool rec_full)
 }
 
 // With the multigrid preconditioner the LEADING vectors of an earlier stage buy nothing (measured on the 600-step 384^2 run:
-// 20.4 s with, 18.9 s without).  Round 3 tried the other end (rec_full, KSFD_TUNE bit 20, off by default): keep the WHOLE first
+// 20.4 s with, 18.9 s without).  Round 3 tried the other end (rec_full, KSFD_TUNE_REC_MG, off by default): keep the WHOLE first
 // cycle of every stage -- the slow modes of shift*I - J that take the iterations late in a run sit in the tail of the Krylov
 // space -- and project a later stage's right-hand side on A M^-1 V_k = V_k+1 H_k first (one multi-dot, one basis combination,
 // ONE V cycle for all spaces together).  Measured: it does NOT pay -- aggregated state at 4096^2 x 3 (h = 4.4) 25 instead of 26

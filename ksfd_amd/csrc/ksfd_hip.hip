@@ -139,8 +139,7 @@ extern "C" int ksfd_create(const ksfd_config *cfg, const ksfd_dist *dist, ksfd_h
     {
         size_t mfree = 0, mtotal = 0;
         if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree > 0) {
-            static const int cap = getenv("KSFD_RESTART_MAX") ? ksfd_krylov::restart_cap(atoi(getenv("KSFD_RESTART_MAX"))) : ksfd_krylov::RESTART_MAX;
-            fit_local = ksfd_krylov::restart_fit((double)mfree, 8.0 * (double)h->vlen, cap);
+            fit_local = ksfd_krylov::restart_fit((double)mfree, 8.0 * (double)h->vlen, env_knobs().restart_cap);
         }
     }
     if (alloc_d(h, &h->dres, 128)) CFAIL(KSFD_ENOMEM, "%s", h->err.c_str());
@@ -181,7 +180,7 @@ extern "C" int ksfd_create(const ksfd_config *cfg, const ksfd_dist *dist, ksfd_h
     h->pub_flag = reinterpret_cast<unsigned long long *>(h->hres + 128);
     *h->pub_flag = 0;
     if (hipHostGetDevicePointer((void **)&h->hres_dev, h->hres, 0) != hipSuccess || hipMalloc((void **)&h->pub_count, sizeof(unsigned int)) != hipSuccess ||
-        hipMemset(h->pub_count, 0, sizeof(unsigned int)) != hipSuccess) { h->zero_copy = false; h->hres_dev = nullptr; }
+        hipMemset(h->pub_count, 0, sizeof(unsigned int)) != hipSuccess) h->hres_dev = nullptr;          // zero_copy_on is false from here on
     else h->pub_flag_dev = reinterpret_cast<unsigned long long *>(h->hres_dev + 128);
     {
         const int m = h->restart_alloc;
@@ -195,11 +194,11 @@ extern "C" int ksfd_create(const ksfd_config *cfg, const ksfd_dist *dist, ksfd_h
 
     spec_build(h);                                            // leaves spec.ok = false where it does not apply (1-D, extents other than 2^k or 3 * 2^k, other rank counts, ...)
     if (mg_build(h)) { mg_free(h); h->mg_ok = false; }        // out of memory for the hierarchy: run without the multigrid preconditioner
-    if ((h->spec.ok || h->mg_ok) && alloc_d(h, &h->bstore, 3 * h->vlen)) { h->bstore = nullptr; h->spec_guess = false; h->err.clear(); }
+    if ((h->spec.ok || h->mg_ok) && alloc_d(h, &h->bstore, 3 * h->vlen)) { h->bstore = nullptr; h->err.clear(); }     // no stage guesses (plan_stage_forms asks for the buffer)
     if (h->ring) {
         // which solvers exist decides the sequence of collectives of every step: all ranks must agree (an allocation that failed
         // on one rank only would otherwise leave the others waiting in an all-reduce)
-        double flags[3] = { h->spec.ok ? 1.0 : 0.0, h->mg_ok ? 1.0 : 0.0, (h->spec_guess && h->bstore) ? 1.0 : 0.0 };
+        double flags[3] = { h->spec.ok ? 1.0 : 0.0, h->mg_ok ? 1.0 : 0.0, h->bstore ? 1.0 : 0.0 };
         for (double &f : flags) f = -f;                       // MIN through the transport's MAX
         if (hipMemcpyAsync(h->dres, flags, sizeof flags, hipMemcpyHostToDevice, h->st) != hipSuccess || h->tr->allreduce(h->dres, 3, 1, h->st))
             CFAIL(KSFD_ECOMM, "agreeing on the available solvers failed: %s", h->tr->error().c_str());
@@ -208,7 +207,7 @@ extern "C" int ksfd_create(const ksfd_config *cfg, const ksfd_dist *dist, ksfd_h
             CFAIL(KSFD_EHIP, "reading the agreed solver flags failed");
         if (flags[0] > -0.5 && h->spec.ok) spec_free(h);
         if (flags[1] > -0.5 && h->mg_ok) { mg_free(h); h->mg_ok = false; }
-        if (flags[2] > -0.5) h->spec_guess = false;
+        if (flags[2] > -0.5 && h->bstore) { hipFree(h->bstore); h->bstore = nullptr; }
     }
     if (hipStreamSynchronize(h->st) != hipSuccess) CFAIL(KSFD_EHIP, "stream sync failed in create");
 #undef CFAIL
@@ -428,7 +427,7 @@ extern "C" int ksfd_jvp(ksfd_handle *h, const double *uh, const double *vh, doub
     if (uh) { if ((rc = upload(h, uh, layout, h->t1))) return rc; uin = h->t1; }
     if ((rc = upload(h, vh, layout, h->t2))) return rc;
     if ((rc = halo(h, uin)) || (rc = halo(h, h->t2))) return rc;
-    if (!uh && h->use_frozen) {
+    if (!uh && h->tune.use_frozen) {
         // the path the stepper uses: coefficients of the stored state once, then the frozen-coefficient kernels
         if ((rc = ensure_coef(h, true))) return rc;
         if ((rc = op_jvp_frozen(h, h->t2, 0, 0.0, h->t3))) return rc;
@@ -441,7 +440,7 @@ static int velocity_common(ksfd_handle *h, const double *uin, double *vel_dev, d
     const KGeom &G = h->G;
     int rc;
     const double *Gplane = h->Gb;
-    if (uin == h->u && h->use_frozen) {
+    if (uin == h->u && h->tune.use_frozen) {
         // the G plane of the resident state is plane 1 of the frozen coefficient planes; the next step reuses them
         if ((rc = ensure_coef(h))) return rc;
         Gplane = h->coef + G.plane;
@@ -632,14 +631,14 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
     // KSFDTS.solve grooms the global vector before every TS.step (KSFD/ksfdts.py:210)
     // cur.floor_ok: every owned value is at or above its floor already (the last completion counted none below and nothing has written u
     // or moved the floors since), so the groom would store the bits it loads and is left out
-    if (!h->cur.floor_ok || h->old_boundary) {
+    if (!h->cur.floor_ok || h->tune.old_boundary) {
         Scope sc(h, KC_MISC, vbytes(h, 2));
         hipLaunchKernelGGL(k_groom, vgrid(h), dim3(KSFD_BLOCK), 0, h->st, h->kv, h->u, h->P.rhomin, h->P.Umin);
         if (hipGetLastError() != hipSuccess) return fail(h, KSFD_EHIP, "k_groom launch failed");
         ksfd_ctl::state_groomed(h->cur);
     }
     if ((rc = halo(h, h->u))) return rc;
-    if (h->use_frozen && (rc = ensure_coef(h, true))) return rc;      // usually already there: the CFL check after the last step made them
+    if (h->tune.use_frozen && (rc = ensure_coef(h, true))) return rc;      // usually already there: the CFL check after the last step made them
     ksfd_ctl::step_begins(h->cur);
     m.nsteps++;
     ksfd_ctl::spec_rho_roll(m);                      // contraction memory of the spectral sweeps
@@ -652,7 +651,8 @@ static int step_run(ksfd_handle *h, double *t, double *hstep, const ksfd_step_op
         rc = step_attempt(h, opts, p, spec_failed, st);
         const int its = st.linear_its - its_before;
         if (p.use_spec && opts->pc_type == 2) ksfd_ctl::spec_backoff_update(m, spec_failed, its, m.nsteps);
-        if (!rc && p.use_pc && h->sf_auto) ksfd_ctl::shift_floor_update(m, (double)its, p.shift);
+        if (!rc && p.use_pc && !env_knobs().pc_sigma_set)      // online search for the shift floor, unless KSFD_PC_SIGMA fixes it
+            ksfd_ctl::shift_floor_update(m, (double)its, p.shift);
         if (rc == KSFD_ELINEAR && opts->adapt && !single && rejects < max_rej && hh * 0.25 >= opts->dt_min) {
             // PETSc's -ts_adapt_scale_solve_failed (0.25): a failed solve rejects the step and quarters it.  The
             // reference disables that by setMaxSNESFailures(1) (KSFD/ksfdts.py:135) because its LU cannot fail this
@@ -710,7 +710,7 @@ extern "C" int ksfd_step(ksfd_handle *h, double *t, double *hstep, const ksfd_st
         if (h->dr_keep > m_dr - 3) return fail(h, KSFD_EINVAL, "deflation: keep = %d needs a restart length of at least %d (ksp_restart %d, basis vectors allocated %d)", h->dr_keep, h->dr_keep + 3, (int)opts->ksp_restart, h->restart_alloc);
     }
     memset(&h->dr_stats, 0, sizeof h->dr_stats);
-    if (getenv("KSFD_PC_SIGMA")) { h->memo.mg_shift_floor = atof(getenv("KSFD_PC_SIGMA")); h->sf_auto = false; }      // experiment knob: fixed floor
+    if (env_knobs().pc_sigma_set) h->memo.mg_shift_floor = env_knobs().pc_sigma;      // experiment knob: fixed floor
     ksfd_step_stats st;
     memset(&st, 0, sizeof st);
     const StepCounters c0 = stats_begin(h);
@@ -757,7 +757,7 @@ extern "C" int ksfd_set_mg_params(ksfd_handle *h, int32_t nu, int32_t ncoarse_ma
     if (power_its > 0) h->mg_power_its = power_its;
     if (ratio > 1.0) h->mg_ratio = ratio;
     if (coarse_tol > 0.0) h->mg_coarse_tol = coarse_tol;
-    h->mg_use_graph = power_its != -7 && !h->ring;     // power_its = -7: eager launches (debug / A-B timing); slab ranks: collectives inside the cycle
+    ksfd_ctl::tuning_mg_graph(h->tune, power_its);
     ksfd_ctl::vcycle_config_changed(h->cur);
     return KSFD_OK;
 }
@@ -980,7 +980,7 @@ extern "C" int ksfd_mg_part(ksfd_handle *h, int32_t part, int32_t level, int32_t
     }
     if (!ok) return fail(h, KSFD_EINVAL, "mg_part %d: level %d has no variant %d", (int)part, (int)level, (int)variant);
     if (part == KSFD_MGP_CYCLE && variant == 1 && !mg_cycle32_ok(h))
-        return fail(h, KSFD_EINVAL, "mg_part: this handle has no cycle with fp32 level vectors (2-D strip kernel on level 0, nu = 2, fused smoother, tuning bit 19 clear)");
+        return fail(h, KSFD_EINVAL, "mg_part: this handle has no cycle with fp32 level vectors (2-D strip kernel on level 0, nu = 2, fused smoother, KSFD_TUNE_MG_FP64 clear)");
     if (part == KSFD_MGP_SMOOTH && (nu < 1 || nu > 5)) return fail(h, KSFD_EINVAL, "mg_part: nu = %d outside 1 .. 5", (int)nu);
     if (part == KSFD_MGP_SMOOTH && !(ratio > 1.0)) return fail(h, KSFD_EINVAL, "mg_part: smoothing ratio %.6g not above 1", ratio);
     if ((part != KSFD_MGP_COEF && part != KSFD_MGP_DINV && !in0) || (need1 && !in1) || !out0 || (need_o1 && !out1))
@@ -1269,7 +1269,7 @@ static int stage_rhs_run(ksfd_handle *h, int regime, int nstages, int ny, double
     const int64_t nl = (int64_t)h->G.F * h->G.nloc, vs = h->vlen;
     // head of step_run without the groom: the kernels clamp on load and the state must stay as it is
     if ((rc = halo(h, h->u))) return rc;
-    if (h->use_frozen && (rc = ensure_coef(h, true))) return rc;
+    if (h->tune.use_frozen && (rc = ensure_coef(h, true))) return rc;
     for (int j = 0; j < ny; j++) {
         if ((rc = upload(h, y_host + (int64_t)j * nl, layout, h->Y + (int64_t)j * vs))) return rc;
         HIPCHK(h, hipStreamSynchronize(h->st));            // the staging buffer of upload() is reused by the next vector
@@ -1285,8 +1285,8 @@ static int stage_rhs_run(ksfd_handle *h, int regime, int nstages, int ny, double
     if (fused_ok(h)) {
         const KStrips K = make_strips(h);
         info->rhs_strip = 1; info->seg = K.yseg; info->nseg = K.nseg; info->nstrips = K.nstrips;
-        info->overlap = h->ring && h->overlap && K.nseg >= 3;
-    } else if (strip3d_ok(h) && h->rhs3d_strip) {
+        info->overlap = h->ring && h->tune.overlap && K.nseg >= 3;
+    } else if (strip3d_ok(h) && h->tune.rhs3d_strip) {
         const K3D K = make_k3d(h);
         info->rhs_strip = 1; info->seg = K.zseg; info->nseg = K.nzseg; info->nstrips = K.nstrips; info->rows = K.rows;
     }
@@ -1354,7 +1354,7 @@ extern "C" int ksfd_stage_jvp(ksfd_handle *h, int32_t op, int32_t mode, double s
     if (op == 2 && !(shift != 0.0)) return fail(h, KSFD_EINVAL, "stage_jvp: the polynomial needs a shift other than zero");
     const bool need_y = op == 1 || (op == 0 && (mode == 2 || mode == 3));
     if (!v_host || !out_host || !scalars || (need_y && !y_host) || (op == 2 && !coef)) return fail(h, KSFD_EINVAL, "stage_jvp %d: missing buffer", (int)op);
-    if (!h->use_frozen) return fail(h, KSFD_EINVAL, "stage_jvp: the frozen Jacobian action is switched off (tuning bit 1)");
+    if (!h->tune.use_frozen) return fail(h, KSFD_EINVAL, "stage_jvp: the frozen Jacobian action is switched off (KSFD_TUNE_RECOMPUTE_JVP)");
     hipSetDevice(h->device);
     if (op == 1 && !residual32_ok(h)) return fail(h, KSFD_EINVAL, "stage_jvp: no fused fp32 residual on this handle (it needs a strip kernel)");
     const ksfd_ctl::Current before = h->cur;
@@ -1381,7 +1381,7 @@ static int stage_jvp_run(ksfd_handle *h, int op, int mode, double shift, double 
     if (path == JP_STRIP2D) {
         const KStrips K = make_strips(h, true);
         scalars[2] = K.yseg; scalars[3] = K.nseg; scalars[4] = K.nstrips;
-        scalars[6] = (h->ring && h->overlap && K.nseg >= 3) ? 1.0 : 0.0;
+        scalars[6] = (h->ring && h->tune.overlap && K.nseg >= 3) ? 1.0 : 0.0;
     } else if (path == JP_LDS3D || path == JP_STRIP3D) {
         const K3D K = path == JP_LDS3D ? make_k3d_lds(h) : make_k3d(h);
         scalars[2] = K.zseg; scalars[3] = K.nzseg; scalars[4] = K.nstrips; scalars[7] = K.rows;
@@ -1417,7 +1417,7 @@ static int stage_jvp_run(ksfd_handle *h, int op, int mode, double shift, double 
     h->poly_deg = deg0;
     memcpy(h->poly_alpha, alpha0, sizeof alpha0);
     if (rc) return rc;
-    scalars[5] = (h->poly_fp32 && h->coef32 && fused_ok(h)) ? 1.0 : 0.0;
+    scalars[5] = (coef32_on(h) && fused_ok(h)) ? 1.0 : 0.0;
     return download(h, out, layout, out_host);
 }
 extern "C" int ksfd_set_spectral_params(ksfd_handle *h, double from_stiffness, int32_t enable)
@@ -1435,32 +1435,13 @@ extern "C" int ksfd_synchronize(ksfd_handle *h)
     HIPCHK(h, hipStreamSynchronize(h->st));
     return KSFD_OK;
 }
-extern "C" int ksfd_set_tuning(ksfd_handle *h, int32_t use_fused, int32_t yseg, int32_t yseg_jvp)
+extern "C" int ksfd_set_tuning(ksfd_handle *h, int32_t word, int32_t yseg, int32_t yseg_jvp)
 {
     if (!h) return KSFD_EINVAL;
-    if (use_fused >= 0) {
-        h->use_fused = use_fused & 1; h->use_frozen = !(use_fused & 2); h->overlap = !(use_fused & 4);
-        h->async_mode = (use_fused & 8) ? 1 : 0;
-        h->rec_mode = (use_fused & 16) ? 0 : ((use_fused & 32) ? 2 : 1);
-        if ((use_fused >> 6) & 7) h->rec_keep = std::min((use_fused >> 6) & 7, 4);
-        h->poly_fp32 = !(use_fused & 512);
-        h->fuse_stage = !(use_fused & 1024);
-        h->zero_copy = !(use_fused & 2048) && h->hres_dev;
-        h->rhs3d_strip = !(use_fused & 8192);
-        h->spec_guess = !(use_fused & 16384);
-        h->rhs_carry = !(use_fused & 32768);
-        h->spec_predict = !(use_fused & 65536);
-        h->restart_grow = !(use_fused & 131072);
-        h->mg_warm_power = !(use_fused & 262144);
-        h->mg_fp32 = !(use_fused & 524288);
-        h->rec_mg = (use_fused & 1048576) != 0;
-        h->rhs_dots = !(use_fused & 2097152);
-        h->old_boundary = (use_fused & 4194304) != 0;
-        h->rhs_gplane = !(use_fused & 8388608);
-        if (h->mg_fuse != !(use_fused & 4096)) { h->mg_fuse = !(use_fused & 4096); ksfd_ctl::vcycle_config_changed(h->cur); }
-    }
-    if (yseg > 0) h->yseg = yseg;
-    if (yseg_jvp > 0) h->yseg_jvp = yseg_jvp;
+    const bool mg_fuse = h->tune.mg_fuse;
+    ksfd_ctl::tuning_apply(h->tune, word, yseg, yseg_jvp);
+    if (word >= 0) h->coef32_failed = false;               // a word that asks for the fp32 copy has its allocation tried once more
+    if (h->tune.mg_fuse != mg_fuse) ksfd_ctl::vcycle_config_changed(h->cur);       // the only switch a set-up depends on ("Switches")
     return KSFD_OK;
 }
 
@@ -1483,7 +1464,7 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         double coef[KSFD_MAXDOT] = { 0 };
         switch (cls) {
         case KC_RHS: r = op_rhs(h, h->u, -1, h->t3); break;
-        case KC_JVP: r = h->use_frozen ? op_jvp_frozen(h, h->Y, 1, 1.0, h->t3) : op_jvp(h, h->u, h->Y, 1, 1.0, h->t3); break;
+        case KC_JVP: r = h->tune.use_frozen ? op_jvp_frozen(h, h->Y, 1, 1.0, h->t3) : op_jvp(h, h->u, h->Y, 1, 1.0, h->t3); break;
         case KC_MULTIDOT: {
             Scope sc(h, KC_MULTIDOT, vbytes(h, 9));
             VW_DISPATCH(h, hipLaunchKernelGGL((k_multidot<8, VW>), dim3(vec2(h) ? (h->nblk_vec + 1) / 2 : h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)h->t3, (const double *)h->V, h->vlen, 8, h->part));
@@ -1528,7 +1509,7 @@ extern "C" int ksfd_bench_kernel(ksfd_handle *h, int32_t cls, int32_t reps, doub
         if (cls == KSFD_BENCH_MGC_APPLY) { bool ok = false; if ((rc = mgc_setup(h, h->mg[mg_end(h)], 1.0, &ok))) goto done; if (!ok) { rc = fail(h, KSFD_ELINEAR, "bench_kernel: the coarse factorization is flagged"); goto done; } }
     }
     if ((rc = halo(h, h->u))) goto done;
-    if (h->use_frozen && (cls == KC_JVP || cls == KC_SPECTRAL) && (rc = ensure_coef(h, true))) goto done;
+    if (h->tune.use_frozen && (cls == KC_JVP || cls == KC_SPECTRAL) && (rc = ensure_coef(h, true))) goto done;
     if (cls == KC_SPECTRAL && (rc = spec_means(h))) goto done;
     for (int i = 0; i < 3 && !rc; i++) rc = one();
     if (rc) goto done;

@@ -20,7 +20,7 @@ static inline bool mg_f32(const ksfd_handle *h, size_t l)
 static JvpSys mg_sys(const ksfd_handle *h, const MGLevel &L)
 {
     const bool l0 = &L == &h->mg[0];
-    return { &L.G, &L.P, L.coef, l0 ? (h->poly_fp32 ? h->coef32 : nullptr) : L.coef32, L.dG, l0 ? KC_JVP : KC_MG };
+    return { &L.G, &L.P, L.coef, l0 ? (coef32_on(h) ? h->coef32 : nullptr) : L.coef32, L.dG, l0 ? KC_JVP : KC_MG };
 }
 static JvpPath mg_path(const ksfd_handle *h, const MGLevel &L) { const JvpPath p = jvp_path(h, L.G, h->P.nlig, JVP_NX_LEVEL); return p == JP_LDS3D ? JP_STRIP3D : p; }
 
@@ -114,7 +114,6 @@ static int mg_build(ksfd_handle *h)
     }
     h->mg_ok = h->mg.size() >= 2;
     h->mgc.level = (int)h->mg.size() - 1;
-    if (h->ring) h->mg_use_graph = false;           // collectives inside the cycle: keep eager launches
     // fp32 level vectors (mg_vcycle<float>): 2-D, levels the strip kernel serves, never the coarsest one (its many Chebyshev sweeps
     // stay in fp64 with the kernels they have)
     if (h->mg_ok) {
@@ -228,7 +227,7 @@ static int mg_halo(ksfd_handle *h, MGLevel &L, T *v, int np)
 }
 
 // smoother algebra in the epilogue of the Jacobian action: the 2-D strip kernel and the generic kernel have it
-static bool mg_can_fuse(const ksfd_handle *h, const MGLevel &L) { return h->mg_fuse && mg_path(h, L) != JP_STRIP3D; }
+static bool mg_can_fuse(const ksfd_handle *h, const MGLevel &L) { return h->tune.mg_fuse && mg_path(h, L) != JP_STRIP3D; }
 
 // Which coefficient planes the strip kernel reads on the level of Y when the level vectors are stored in T.  fp64 vectors: the fp32 copy
 // on level 0 only (the V cycle is a preconditioner: see poly_apply; the coarse levels keep their fp64 planes).  fp32 vectors: the fp32
@@ -254,14 +253,14 @@ static int mg_op(ksfd_handle *h, MGLevel &L, const T *v, int mode, double shift,
     const double by = ((c32 ? 4.0 : 8.0) * (3 + h->P.nlig) + s * G.F * (1 + (mode == 1 ? 1 : mode == 2 ? 2 : 3)) + (mode >= 5 ? 4.0 * G.F * G.F : 0.0) +
                        ((mode == 6 && sm && sm->x64) ? (8.0 - s) * G.F : 0.0)) * (double)G.nloc;
     if (path == JP_STRIP2D) {
-        const KStrips K = strips_for(G, h->yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
+        const KStrips K = strips_for(G, h->tune.yseg_jvp, 4096);       // the levels do not follow KSFD_WAVES_JVP
         Scope sc(h, Y.cls, by);
         auto launch = [&](auto *C) { sm ? jvp2d_launch<true>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, *sm, nullptr) : jvp2d_launch<false>(h, Y, K, C, v, mode, shift, out, yadd, 0.0, 0.0, KSmooth{}, nullptr); };
         if (c32) launch(c32); else launch(Y.coef);
     } else if constexpr (std::is_same<T, double>::value) {
         Scope sc(h, Y.cls, by + 8.0 * G.plane);
         dg_pass(h, Y, v, -1);
-        if (path == JP_STRIP3D) jvp3d_launch<double>(h, Y, k3d_for(G, 4, 0, h->zseg, 1024), v, mode, shift, out, yadd, 0.0, 0.0, nullptr);
+        if (path == JP_STRIP3D) jvp3d_launch<double>(h, Y, k3d_for(G, 4, 0, h->tune.zseg, 1024), v, mode, shift, out, yadd, 0.0, 0.0, nullptr);
         else jvpgen_launch(h, Y, plane_blocks(G), v, mode, shift, out, yadd, 0.0, 0.0, sm ? *sm : KSmooth{});
     }
     HIPCHK(h, hipGetLastError());
@@ -352,7 +351,7 @@ static int mg_setup_shift(ksfd_handle *h, double shift)
         // (4096^2 x 3 fields: 9.4 -> 2.9 ms of set-up per step).
         double *v = L.pv, *w = L.v64.r;
         double nv = L.pv_norm, lam = 2.0, lam_prev = 0.0;
-        const bool warm = nv > 0.0 && h->mg_warm_power;
+        const bool warm = nv > 0.0 && h->tune.mg_warm_power;
         if (!warm) {
             hipLaunchKernelGGL(k_hash_fill, dim3(nb), dim3(KSFD_BLOCK), 0, h->st, (long long)L.vlen, v);
             if ((rc = mg_norm(h, L, v, &nv))) return rc;
@@ -641,14 +640,14 @@ static int mg_vcycle(ksfd_handle *h, size_t l, double shift, const T *b, T *x, c
     };
     if ((rc = smooth(true))) return rc;
     if ((rc = mg_op<T>(h, L, x, 2, shift, L.vecs<T>().r, b))) return rc;
-    if (l == 0 && h->mg_use_graph && !h->capturing) {
+    if (l == 0 && mg_graph_on(h) && !h->capturing) {
         if ((rc = mg_coarse_graph(h, shift, x, f32, [&]() { return mg_coarse_correction(h, 0, shift, x); }))) return rc;
     } else if ((rc = mg_coarse_correction(h, l, shift, x))) return rc;
     return smooth(false);
 }
 
 // this handle has a cycle with fp32 level vectors: they exist on level 0, and the V(2,2) pair with the fused smoother is what runs on them
-static bool mg_cycle32_ok(const ksfd_handle *h) { return h->mg_fp32 && h->mg[0].f32 && h->mg_nu == 2 && mg_can_fuse(h, h->mg[0]); }
+static bool mg_cycle32_ok(const ksfd_handle *h) { return h->tune.mg_fp32 && h->mg[0].f32 && h->mg_nu == 2 && mg_can_fuse(h, h->mg[0]); }
 
 // out = M^-1 in  (one V cycle)
 static int mg_precond(ksfd_handle *h, double shift, const double *in, double *out)

@@ -35,7 +35,7 @@ static int reduce_rows(ksfd_handle *h, int rows, int nblk, int op, bool local = 
 {
     // several ranks with a device-side all-reduce (RCCL): a one-block k_publish behind the all-reduce hands the result over
     // the same way; ksfd_amd.dist.open_handle checks that path end to end on a new handle and clears zero_copy if it fails
-    const bool zc = h->zero_copy && !h->capturing && rows <= 128 && (!h->ring || (h->tr->device_allreduce() && !local));
+    const bool zc = zero_copy_on(h) && !h->capturing && rows <= 128 && (!h->ring || (h->tr->device_allreduce() && !local));
     const bool zc_here = zc && !h->ring;
     h->n_host_sync++;
     const unsigned long long seq = zc ? ++h->pub_seq : 0;
@@ -104,9 +104,7 @@ static KStrips strips_for(const KGeom &G, int yseg, long long wave_target)
 }
 static KStrips make_strips(const ksfd_handle *h, bool jvp = false)
 {
-    static const long long t_jvp = getenv("KSFD_WAVES_JVP") ? atoll(getenv("KSFD_WAVES_JVP")) : 4096;       // experiments (tools/yseg_sweep.py)
-    static const long long t_rhs = getenv("KSFD_WAVES_RHS") ? atoll(getenv("KSFD_WAVES_RHS")) : 6144;
-    return strips_for(h->G, jvp ? h->yseg_jvp : h->yseg, jvp ? t_jvp : t_rhs);
+    return strips_for(h->G, jvp ? h->tune.yseg_jvp : h->tune.yseg, jvp ? env_knobs().waves_jvp : env_knobs().waves_rhs);
 }
 
 // launch geometry of the 3-D z-marching strip kernels: blocks of `rows` y rows, z segments of at most zseg planes, shorter when that
@@ -127,14 +125,12 @@ static K3D k3d_for(const KGeom &G, int rows, int sync, int zseg, long long block
 // barrier per plane 107.8, 8 rows 111.9, 8 rows + barrier 115.5 -- so 4 rows marching in step; KSFD_ROWS3D=8 / KSFD_SYNC3D=0 for measurements
 static int rows3d(const ksfd_handle *h)
 {
-    static const int env = getenv("KSFD_ROWS3D") ? atoi(getenv("KSFD_ROWS3D")) : 0;
-    return (env == 8 && h->P.nlig == 1) ? 8 : 4;
+    return (env_knobs().rows3d == 8 && h->P.nlig == 1) ? 8 : 4;
 }
 static K3D make_k3d(const ksfd_handle *h)
 {
-    static const int sync_env = getenv("KSFD_SYNC3D") ? atoi(getenv("KSFD_SYNC3D")) : 1;
     const int rows = rows3d(h);
-    return k3d_for(h->G, rows, sync_env && (h->G.ny % rows == 0), h->zseg, rows == 8 ? 512 : 1024);
+    return k3d_for(h->G, rows, env_knobs().sync3d && (h->G.ny % rows == 0), h->tune.zseg, rows == 8 ? 512 : 1024);
 }
 
 // ---- frozen Jacobian action shift*v - J v: where it runs and which kernel serves it ---------------
@@ -147,21 +143,20 @@ struct JvpSys {
     double *dG;                              // scratch plane of the dG pass (3-D strip and generic kernels)
     int cls;                                 // kernel class the launches are booked under
 };
-static JvpSys jvp_sys(const ksfd_handle *h) { return { &h->G, &h->P, h->coef, h->poly_fp32 ? h->coef32 : nullptr, h->dGb, KC_JVP }; }
+static JvpSys jvp_sys(const ksfd_handle *h) { return { &h->G, &h->P, h->coef, coef32_on(h) ? h->coef32 : nullptr, h->dGb, KC_JVP }; }
 
 enum JvpPath { JP_STRIP2D, JP_LDS3D, JP_STRIP3D, JP_GENERIC };     // k_jvp2d_frozen, k_jvp3d_lds, dG pass + k_jvp3d_frozen, dG pass + k_jvp_generic
 // fewest columns the strip kernels serve
 static const int JVP_NX_GRID = 4;         // the handle's grid: what the five-point window of a periodic row needs
 static const int JVP_NX_LEVEL = 16;       // multigrid levels: coarse levels of 8..14 columns should not march 124-column strips
-// The one rule.  use_fused = 0, an odd nx, fewer than min_nx columns, more than 4 ligands or a 1-D grid: generic.  2-D: the strip kernel
+// The one rule.  tune.use_fused off, an odd nx, fewer than min_nx columns, more than 4 ligands or a 1-D grid: generic.  2-D: the strip kernel
 // (4 slow units at least: every level of a hierarchy has them, mg_build).  3-D: the second generation for one or two ligands where ny is
 // a multiple of its 8 rows per block (KSFD_J3L=0 keeps the first generation), else the first-generation strip kernel
 static JvpPath jvp_path(const ksfd_handle *h, const KGeom &G, int nlig, int min_nx)
 {
-    static const int j3l_env = getenv("KSFD_J3L") ? atoi(getenv("KSFD_J3L")) : 1;
-    if (!h->use_fused || G.dim < 2 || (G.nx % 2) || G.nx < min_nx || nlig > 4) return JP_GENERIC;
+    if (!h->tune.use_fused || G.dim < 2 || (G.nx % 2) || G.nx < min_nx || nlig > 4) return JP_GENERIC;
     if (G.dim == 2) return G.sloc >= 4 ? JP_STRIP2D : JP_GENERIC;
-    return (j3l_env && nlig <= 2 && G.ny % KSFD_J3L_ROWS == 0) ? JP_LDS3D : JP_STRIP3D;
+    return (env_knobs().j3l && nlig <= 2 && G.ny % KSFD_J3L_ROWS == 0) ? JP_LDS3D : JP_STRIP3D;
 }
 // the handle's own grid: strip kernels of the RHS and of the Jacobian action alike (k_rhs2d_fused / k_rhs3d_strip follow the same rule)
 static bool fused_ok(const ksfd_handle *h) { return jvp_path(h, h->G, h->P.nlig, JVP_NX_GRID) == JP_STRIP2D; }
@@ -183,7 +178,7 @@ static JvpPath grid_path(ksfd_handle *h)
 }
 static bool j3l_ok(ksfd_handle *h) { return grid_path(h) == JP_LDS3D; }
 // (one block per CU: four rounds of blocks at least)
-static K3D make_k3d_lds(const ksfd_handle *h) { return k3d_for(h->G, KSFD_J3L_ROWS, 0, h->zseg, 1024); }
+static K3D make_k3d_lds(const ksfd_handle *h) { return k3d_for(h->G, KSFD_J3L_ROWS, 0, h->tune.zseg, 1024); }
 
 // wave counts of the strip launches: the fused norms leave one partial per wave in h->part
 static inline long long part_capacity() { return (long long)(2 * KSFD_MAXDOT + 4) * 4096; }      // of h->part in doubles (ksfd_create)
@@ -255,7 +250,7 @@ static JvpBytes jvp_bytes(const KGeom &G, int mode, double ncoef, double extra =
 // A strip launch whose input needs its ghost rows exchanged first (slab ranks), with the exchange hidden behind the interior rows:
 //   compute stream: [interior segments]                      [two boundary segments]
 //   comm stream   :   wait(input ready) -> ghost rows <- ring neighbours -> signal
-// Interior segments read owned rows only; the first and last segment are the only readers of ghost rows.  Without h->overlap or
+// Interior segments read owned rows only; the first and last segment are the only readers of ghost rows.  Without h->tune.overlap or
 // with fewer than 3 segments: exchange on the compute stream, then one launch of everything.
 // exchange(stream) -> nonzero on failure; launch(strips, share of the work, normpart) -> KSFD error code.  normpart: per-wave
 // partials numbered over ALL segments of K (interior launch first, then the two boundary segments)
@@ -263,7 +258,7 @@ template <typename Exchange, typename Launch>
 static int with_halo_overlap(ksfd_handle *h, const KStrips &K, double *normpart, Exchange exchange, Launch launch)
 {
     int rc;
-    const bool ovl = h->overlap && K.nseg >= 3;
+    const bool ovl = h->tune.overlap && K.nseg >= 3;
     if (ovl) {
         HIPCHK(h, hipEventRecord(h->ev_ready, h->st));
         if ((rc = launch(strips_sub(K, 1, 1, K.nseg - 2), (double)(K.nseg - 2) / K.nseg, normpart))) return rc;
@@ -298,11 +293,11 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         KDots D = KDots{};
         if (fused_norm && ndots > 0) { D.n = std::min(ndots, 2); D.stride = nwaves; for (int q = 0; q < D.n; q++) D.v[q] = dotv + (int64_t)q * h->vlen; }
         // the vectors added at the store are the ones the stage argument is formed from: one read serves both (k_rhs2d_fused<NL, true>)
-        bool carry = h->rhs_carry && C.nout > 0 && C.nout == C.nin;
+        bool carry = h->tune.rhs_carry && C.nout > 0 && C.nout == C.nin;
         for (int j = 0; j < C.nout && carry; j++) carry = C.yin[j] == C.yout[j];
         // first stage of a step: the argument is the resident state itself and G(u) is plane 1 of the frozen coefficients the step has
         // just made of it (same parameters, same clamped inputs): loaded, not evaluated (the rule of the 3-D path below)
-        const bool reuse_G = h->rhs_gplane && C.nin == 0 && C.nout == 0 && u == h->u && h->cur.coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
+        const bool reuse_G = h->tune.rhs_gplane && C.nin == 0 && C.nout == 0 && u == h->u && h->cur.coef_fresh && h->tune.use_frozen && h->coef && &PP == &h->P;
         auto launch = [&](const KStrips &Kx, double frac, double *np) -> int {
             Scope sc(h, KC_RHS, (vbytes(h, 2 + C.nin + (carry ? 0 : C.nout) + D.n) + (reuse_G ? 8.0 * (double)G.nloc : 0.0)) * frac, vbytes(h, 2 + C.nin + C.nout + D.n) * frac);
             if (reuse_G) { NL_DISPATCH(h->P.nlig, if constexpr (NL <= 4) hipLaunchKernelGGL((k_rhs2d_fused<NL, false, true>), dim3(Kx.nblocks), dim3(KSFD_BLOCK), 0, h->st, G, PP, Kx, u, S, out, C, np, D, (const double *)(h->coef + G.plane))); }
@@ -322,7 +317,7 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         return KSFD_OK;
     }
     if (halo_vec) { int rc = halo(h, halo_vec); if (rc) return rc; }
-    if (strip3d_ok(h) && h->rhs3d_strip) {
+    if (strip3d_ok(h) && h->tune.rhs3d_strip) {
         // 3-D: G plane (+ the stage argument, when the stage algebra rides along), then the z-marching 13-point star
         if (want_norm) return fail(h, KSFD_EINVAL, "op_rhs: fused norm is a 2-D feature");
         KComb C = cmb ? *cmb : KComb{};
@@ -330,7 +325,7 @@ static int op_rhs(ksfd_handle *h, const double *u, int stage, double *out, const
         const double *Gplane = h->Gb;
         // first stage of a step: the argument is the resident state itself and G(u) is plane 1 of the frozen coefficients the step has
         // just made of it (same parameters): nothing to form, no pass
-        const bool reuse_G = C.nin == 0 && u == h->u && h->cur.coef_fresh && h->use_frozen && h->coef && &PP == &h->P;
+        const bool reuse_G = C.nin == 0 && u == h->u && h->cur.coef_fresh && h->tune.use_frozen && h->coef && &PP == &h->P;
         if (reuse_G) Gplane = h->coef + G.plane;
         else {
             Scope sc(h, KC_GFIELD, 8.0 * ((1 + C.nin) * G.F + (C.nin ? G.F : 0) + 1) * (double)G.plane, C.nin ? vbytes(h, 2 + C.nin) : 0.0);
@@ -374,13 +369,13 @@ static int op_jvp(ksfd_handle *h, const double *u, const double *v, int mode, do
 }
 
 // The buffer of the fp32 coefficient copy, allocated when first wanted (2-D strip path only).  false: no copy on this handle (poly_fp32
-// off, another kernel path, or no memory, which switches poly_fp32 off)
+// off, another kernel path, or no memory: coef32_failed keeps the allocation from being tried at every call)
 static bool coef32_alloc(ksfd_handle *h)
 {
     const KGeom &G = h->G;
-    if (!h->coef32 && h->poly_fp32 && fused_ok(h) && h->P.nlig <= 4 && G.plane % 2 == 0 && G.inner % 2 == 0 &&
-        hipMalloc((void **)&h->coef32, sizeof(float) * (size_t)(3 + h->P.nlig) * G.plane) != hipSuccess) { h->coef32 = nullptr; h->poly_fp32 = false; (void)hipGetLastError(); }
-    return h->poly_fp32 && h->coef32;
+    if (!h->coef32 && !h->coef32_failed && h->tune.poly_fp32 && fused_ok(h) && h->P.nlig <= 4 && G.plane % 2 == 0 && G.inner % 2 == 0 &&
+        hipMalloc((void **)&h->coef32, sizeof(float) * (size_t)(3 + h->P.nlig) * G.plane) != hipSuccess) { h->coef32 = nullptr; h->coef32_failed = true; (void)hipGetLastError(); }
+    return coef32_on(h);
 }
 
 // Once per step: C = [rho, G, G_rho, G_U..] of the (ghost-filled) state u
@@ -414,7 +409,7 @@ static int ensure_coef(ksfd_handle *h, bool ghosts_done = false)
     int rc;
     if (!ghosts_done && (rc = halo(h, h->u))) return rc;
     // the fp32 copy is made when a consumer asks for it (ensure_coef32); only the old step boundary has k_jcoef store it
-    float *c32 = h->old_boundary && coef32_alloc(h) ? h->coef32 : nullptr;
+    float *c32 = h->tune.old_boundary && coef32_alloc(h) ? h->coef32 : nullptr;
     const bool means = h->spec.ok && (long long)(1 + h->P.nlig) * plane_blocks(h->G) <= part_capacity();
     if ((rc = op_jcoef(h, h->u, c32, means))) return rc;
     ksfd_ctl::planes_recomputed(h->cur, c32 != nullptr, means);
@@ -492,7 +487,7 @@ static int op_jvp_frozen(ksfd_handle *h, const double *v, int mode, double shift
 static int op_jvp_frozen_halo(ksfd_handle *h, double *v, int mode, double shift, double *out, const double *yadd = nullptr, double alpha = 0.0, double beta = 0.0)
 {
     if (!h->ring) return op_jvp_frozen(h, v, mode, shift, out, yadd, alpha, beta);
-    if (!h->overlap || !fused_ok(h) || make_strips(h, true).nseg < 3 || h->P.nlig > 4) {
+    if (!h->tune.overlap || !fused_ok(h) || make_strips(h, true).nseg < 3 || h->P.nlig > 4) {
         const int rc = halo(h, v);
         return rc ? rc : op_jvp_frozen(h, v, mode, shift, out, yadd, alpha, beta);
     }

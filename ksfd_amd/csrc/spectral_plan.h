@@ -166,7 +166,7 @@ static std::vector<float> spec_symbol_table(int n, double inv_h2)
 }
 
 // ------------------------------------------------------------------------------------------------
-// The shape planner: every integer decision of the host side, from the grid and the knobs alone (no handle, no HIP call, no getenv),
+// The shape planner: every integer decision of the host side, from the grid and the knobs alone (no handle, no HIP call, no environment read),
 // so that all of it runs on a CPU (tests/test_spectral_shape_cpu.py).  spec_build (spectral_host.hip.h) turns its answer into
 // allocations, kernel instances and all-to-all lists; tools/spec_lab.hip takes its launch shape from here too.
 struct SpecKnobs {                 // the KSFD_SPEC_* experiment knobs (read by spec_knobs, spectral_host.hip.h); these defaults = none set

@@ -58,12 +58,12 @@ static void stats_end(ksfd_handle *h, const StepCounters &c0, ksfd_step_stats &s
 // How the stages of an attempt are formed once its regime (use_spec, use_pc) is known; shared with the test entry ksfd_stage_rhs
 static void plan_stage_forms(const ksfd_handle *h, AttemptPlan &p)
 {
-    p.fuse_stage = (fused_ok(h) || (strip3d_ok(h) && h->rhs3d_strip)) && h->P.nlig <= 4 && h->fuse_stage;
+    p.fuse_stage = (fused_ok(h) || (strip3d_ok(h) && h->tune.rhs3d_strip)) && h->P.nlig <= 4 && h->tune.fuse_stage;
     // Initial guesses for the spectral stage solves from the earlier stages of the step (A Y_j = b_j is known): the right-hand
     // sides of a step are nearly dependent -- b_1 = c b_0 to ~1e-3, later ones to a few per cent (CPU experiment with the oracle)
     // -- so x0 = sum c_j Y_j, c = argmin ||b_i - sum c_j b_j||, starts the defect correction 1-3 digits ahead for one small
     // multi-dot.  The b_j are kept in bstore (three vectors); stage_gram_guess keeps their Gram matrix.
-    p.guess_on = (p.use_spec || p.use_pc) && p.fuse_stage && h->spec_guess && h->bstore;
+    p.guess_on = (p.use_spec || p.use_pc) && p.fuse_stage && h->tune.spec_guess && h->bstore;
 }
 
 // Regime of one attempt with step size hh.  lam_done: the eigenvalue estimate of the polynomial is looked at once per step, not per attempt.
@@ -79,12 +79,12 @@ static int plan_attempt(ksfd_handle *h, const ksfd_step_opts *opts, double hh, b
     in.pc_type = opts->pc_type; in.reserved = opts->reserved; in.stiff = p.stiff;
     in.direct = direct; in.dr_on = dr_on;
     in.spec_ok = h->spec.ok; in.user_off = h->spec.user_off;
-    in.use_frozen = h->use_frozen; in.fused2d = fused_ok(h);
+    in.use_frozen = h->tune.use_frozen; in.fused2d = fused_ok(h);
     in.mg_ok = h->mg_ok; in.mg_threshold = h->mg_threshold; in.spec_from = h->spec_from;
     in.nsteps = m.nsteps; in.bad_until = m.spec_bad_until;
     in.unknowns = (double)h->G.F * (double)h->G.nloc;
     in.ring = h->ring; in.device_allreduce = h->ring && h->tr->device_allreduce();
-    in.async_mode = h->async_mode;
+    in.async_mode = h->tune.async_mode;
     const ksfd_ctl::Regime r = ksfd_ctl::choose_regime(in);
     p.use_spec = r.spec; p.use_pc = r.mg;
     if (p.use_spec) {
@@ -125,7 +125,7 @@ static int stage_rhs(ksfd_handle *h, const AttemptPlan &p, int i, StageRhs &r)
         }
         // ||b||^2 from the store epilogue (2-D strip kernel), and with it the inner products of b_i with the right-hand sides the stage
         // guess is built from (the multi-dot of stage_gram_guess would read all of them again)
-        const int gdot_j0 = std::max(0, i - h->guess_max), gdot_n = (p.guess_on && i > 0 && h->rhs_dots) ? i - gdot_j0 : 0;
+        const int gdot_j0 = std::max(0, i - env_knobs().guess_max), gdot_n = (p.guess_on && i > 0 && h->tune.rhs_dots) ? i - gdot_j0 : 0;
         const bool rhs_norm = p.use_spec && fused_ok(h) && (!(p.guess_on && i > 0) || (gdot_n > 0 && gdot_n <= 2 && strip_waves(h) * (1 + gdot_n) <= part_capacity()));
         r.dots_done = rhs_norm && gdot_n > 0;
         // ghosts of the newest stage vector (earlier ones done): exchanged behind the interior rows of the RHS (op_rhs)
@@ -167,9 +167,9 @@ static int stage_gram_guess(ksfd_handle *h, int i, StageRhs &r, double gb[4][4],
         return KSFD_OK;
     }
     // <b_i, b_j> (j0 <= j < i) and <b_i, b_i> in one pass.
-    // j0 > 0 (h->guess_max): only the most recent stages enter -- every vector of the guess costs two more full-vector
+    // j0 > 0 (env_knobs().guess_max): only the most recent stages enter -- every vector of the guess costs two more full-vector
     // reads in the first sweep (b_j in the forward row kernel, Y_j in the inverse one) and one in this multi-dot
-    const int j0 = std::max(0, i - h->guess_max), ng = i - j0;
+    const int j0 = std::max(0, i - env_knobs().guess_max), ng = i - j0;
     if (r.dots_done) {
         for (int j = 0; j < ng; j++) gb[i][j0 + j] = gb[j0 + j][i] = r.dot[j];
         gb[i][i] = r.bnorm2;
@@ -234,10 +234,10 @@ static int stage_solve(ksfd_handle *h, const ksfd_step_opts *opts, const Attempt
     st.linear_its += ls.its;
     st.ksp_resid = ls.rel;
     {
-        static const bool stage_trace = getenv("KSFD_STAGE_TRACE") != nullptr;     // iterations per stage system (diagnostics)
+        const bool stage_trace = env_knobs().stage_trace;          // iterations per stage system (diagnostics)
         if (stage_trace) fprintf(stderr, "[stage %d] its %d rel %.2e guess %d\n", i, ls.its, ls.rel, sg.n);
     }
-    if (rc == KSFD_ELINEAR && !p.direct && !p.use_pc && h->mg_ok && h->use_frozen && opts->pc_type) {
+    if (rc == KSFD_ELINEAR && !p.direct && !p.use_pc && h->mg_ok && h->tune.use_frozen && opts->pc_type) {
         // unpreconditioned GMRES ran out of iterations: the multigrid-preconditioned solve of the same system
         // is the remedy (the stiffness estimate only knows the diffusion part of J)
         rc = gmres(h, h->u, shift, r.b, xi, opts, &ls, 1);
@@ -288,13 +288,13 @@ static int step_finish(ksfd_handle *h, const ksfd_step_opts *opts, double *wrms,
 {
     int rc;
     {
-        Scope sc(h, KC_FINISH, vbytes(h, h->old_boundary ? 7 : 6));
+        Scope sc(h, KC_FINISH, vbytes(h, h->tune.old_boundary ? 7 : 6));
         hipLaunchKernelGGL(k_rosw_finish, dim3(h->nblk_vec), dim3(KSFD_BLOCK), 0, h->st, h->kv, (const double *)h->u, h->usave, h->Y, h->vlen,
                            h->bt[0], h->bt[1], h->bt[2], h->bt[3], h->b2t[0] - h->bt[0], h->b2t[1] - h->bt[1],
                            h->b2t[2] - h->bt[2], h->b2t[3] - h->bt[3], opts->atol, opts->rtol, h->P.rhomin, h->P.Umin,
-                           h->old_boundary ? h->errv : (double *)nullptr, h->part);
+                           h->tune.old_boundary ? h->errv : (double *)nullptr, h->part);
     }
-    ksfd_ctl::completion_done(h->cur, h->old_boundary);
+    ksfd_ctl::completion_done(h->cur, h->tune.old_boundary);
     if ((rc = reduce_rows(h, 2, h->nblk_vec, 0))) return rc;
     const double ntot = (double)h->G.F * (double)h->cfg.n[0] * (double)h->cfg.n[1] * (double)h->cfg.n[2];
     *wrms = sqrt(h->hres[0] / ntot);

@@ -165,7 +165,7 @@ const double SPEC_SLOW_RATIO = 0.25;        // a sweep that leaves more than thi
 const double SPEC_PRED_SAFETY = 4.0;        // predicted last sweep: SAFETY * rho_hat * ||r_k|| <= tol
 const double SPEC_PRED_MIN_RTOL = 1e-8;     // ... off below this ksp_rtol (the parity tests verify every solve)
 
-// Predicted last sweep on?  spec_predict: the handle's switch (KSFD_TUNE bit 16); reserved bit 3: the caller's; verify_env: KSFD_SPEC_VERIFY
+// Predicted last sweep on?  spec_predict: the handle's switch (KSFD_TUNE_NO_SPEC_PREDICT); reserved bit 3: the caller's; verify_env: KSFD_SPEC_VERIFY
 // (2 = off, 1 = on and every skipped residual evaluated anyway).
 static inline bool spec_predict_on(bool spec_predict, int reserved, double ksp_rtol, int verify_env)
 {

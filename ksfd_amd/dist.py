@@ -333,7 +333,7 @@ def open_handle(cfg, rank, size, device, transport='auto', group=None, host_grou
                     return False
             ok = _agree(red_ok(), g, device)
             if not ok:
-                ks.set_tuning(use_fused=1 | 2048)          # bit 11: stream synchronisation + copy instead of the mapped-memory flag
+                ks.set_tuning(use_fused=klib.TUNE_FUSED | klib.TUNE_NO_ZERO_COPY)     # stream synchronisation + copy instead of the mapped-memory flag
                 ks.zero_copy_disabled = True
                 ok = _agree(red_ok(), g, device)
                 why = '' if ok else 'RCCL all-reduce self-test failed'

@@ -116,6 +116,20 @@ ASYNC_MAXK = 32
 BENCH_MGC_SETUP, BENCH_MGC_APPLY, BENCH_MGC_FACTOR_COLUMNS = 104, 105, 106    # ... set-up / apply of the exact coarse solve, per-column factorization of the same matrix
 BENCH_BAND_FACTOR, BENCH_BAND_SOLVE = 102, 103      # ... one factorization (assembly included) / one solve of the banded direct solver
 
+# the tuning word of set_tuning: KSFD_TUNE_* of include/ksfd_hip.h, name for name (tests/test_tuning_cpu.py), where each bit is described.
+# A word replaces every switch, so a word that is to change one switch of a default handle is TUNE_FUSED | that bit
+TUNE_FUSED, TUNE_RECOMPUTE_JVP, TUNE_NO_OVERLAP, TUNE_ASYNC_GMRES, TUNE_NO_RECYCLE, TUNE_RECYCLE_ALL = (1 << b for b in range(6))
+TUNE_REC_KEEP_MASK = 7 << 6
+(TUNE_POLY_FP64, TUNE_UNFUSED_STAGE, TUNE_NO_ZERO_COPY, TUNE_UNFUSED_SMOOTHER, TUNE_GENERIC_RHS3D, TUNE_NO_SPEC_GUESS, TUNE_NO_RHS_CARRY,
+ TUNE_NO_SPEC_PREDICT, TUNE_NO_RESTART_GROWTH, TUNE_COLD_POWER, TUNE_MG_FP64, TUNE_REC_MG, TUNE_OWN_DOTS, TUNE_OLD_BOUNDARY,
+ TUNE_NO_GPLANE) = (1 << b for b in range(9, 24))
+MG_EAGER = -7           # KSFD_MG_EAGER: power_its of set_mg_params that launches the coarse cycle kernel by kernel
+
+
+def TUNE_REC_KEEP(v):
+    """KSFD_TUNE_REC_KEEP(v): the field of the tuning word that keeps v leading Arnoldi vectors per stage (0: the count in force)"""
+    return (v & 7) << 6
+
 _lib = None
 
 # every symbol include/ksfd_hip.h declares (checked by tests/test_abi.py without a GPU)
@@ -645,5 +659,6 @@ class KSFDHip:
         self._chk(self.L.ksfd_set_spectral_params(self.h, float(from_stiffness), int(enable)))
 
     def set_tuning(self, use_fused=-1, yseg=0, yseg_jvp=None):
-        """use_fused: bit0 = fused 2-D kernels, bit1 = recompute (non-frozen) Jacobian action."""
+        """use_fused: the tuning word, an OR of the TUNE_* constants of this module (the default handle is TUNE_FUSED).  Negative:
+        no switch changes; any other word replaces every switch.  yseg / yseg_jvp: rows per wave segment, <= 0 keeps."""
         self._chk(self.L.ksfd_set_tuning(self.h, use_fused, yseg, yseg if yseg_jvp is None else yseg_jvp))

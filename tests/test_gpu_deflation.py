@@ -15,8 +15,6 @@ from test_gpu_random_sweep import random_problem
 pytestmark = pytest.mark.gpu
 
 GAMMA = 0.43586652150845900
-NO_RESTART_GROWTH = 1 << 17          # ksfd_set_tuning bit 17
-ASYNC_GMRES = 1 << 3
 
 
 # ---- 1. rotation kernel -------------------------------------------------------------------------------------------------------
@@ -119,7 +117,7 @@ def test_deflated_gmres_on_indefinite_systems_vs_oracle(case, carry):
 def test_deflation_halves_the_iterations_of_restarted_gmres(case):
     cfg, u, h, un = indefinite_case(case)
     k = klib.KSFDHip(cfg)
-    k.set_tuning(use_fused=1 | NO_RESTART_GROWTH)
+    k.set_tuning(use_fused=klib.TUNE_FUSED | klib.TUNE_NO_RESTART_GROWTH)
     k.set_deflation(0, 1)
     k.set_state(u)
     t, hn, st, rc = k.step(0.0, h, indefinite_opts(), raise_on_error=False)
@@ -239,7 +237,7 @@ def test_guards():
 def test_async_tuning_bit_runs_the_synchronous_deflated_solver():
     cfg, u, h, un = indefinite_case(100)
     rc, state, its, ds, msg = deflated_indefinite_run(100, 1)
-    rc_a, state_a, its_a, ds_a, msg_a = deflated_indefinite_run(100, 1, 1 | ASYNC_GMRES)
+    rc_a, state_a, its_a, ds_a, msg_a = deflated_indefinite_run(100, 1, klib.TUNE_FUSED | klib.TUNE_ASYNC_GMRES)
     assert rc_a == 0 and rc == 0
     assert ds_a['restarts'] >= 1 and its_a == its
     assert np.array_equal(state_a, state)

@@ -152,10 +152,10 @@ def test_direct_manufactured_per_stage_sources_vs_golden():
 
 def test_direct_stage_time_parameters_vs_golden():
     """ksfd_update_params at every step start (the Jacobian's table) and ksfd_set_stage_params (the stage RHS tables); with
-    tuning bit 1 (use_frozen off) as well: the factorization takes its coefficient planes through ensure_coef either way"""
+    TUNE_RECOMPUTE_JVP (use_frozen off) as well: the factorization takes its coefficient planes through ensure_coef either way"""
     from test_gpu_ts import _tdep_cfg
     z = load_golden('step_2d_n1_tdep')
-    for tuning in (1, 3):
+    for tuning in (klib.TUNE_FUSED, klib.TUNE_FUSED | klib.TUNE_RECOMPUTE_JVP):
         k = klib.KSFDHip(_tdep_cfg(z, 0, 0))
         k.set_tuning(use_fused=tuning)
         k.set_state(cijk_to_soa(z['u0']))

@@ -27,8 +27,6 @@ pytestmark = pytest.mark.gpu
 LD = np.longdouble
 U = LD(2.0) ** -53
 STEP_TOL = 1e-10                      # the constant of test_gpu_step.py
-NO_RESTART_GROWTH = 1 << 17           # ksfd_set_tuning bit 17
-ASYNC_GMRES = 1 << 3
 
 
 def gamma(n):
@@ -562,11 +560,11 @@ def test_pipelined_gmres_with_a_restart_beyond_its_kernels():
     kernels ignored the vectors past 32 and the small-algebra kernel wrote past its coefficient array).  Precondition, so that the test
     cannot pass without getting there: the synchronous solver with the restart kept at 64 needs at least 4 * 40 iterations."""
     cfg, u, un = long_case()
-    rc_s, sync, its_s, pc_s, msg_s = long_run(1 | NO_RESTART_GROWTH)
+    rc_s, sync, its_s, pc_s, msg_s = long_run(klib.TUNE_FUSED | klib.TUNE_NO_RESTART_GROWTH)
     assert rc_s == 0, msg_s
     print('long restart: synchronous %d iterations, rel-L2 vs LU %.3e' % (its_s, rel_l2(sync, un)))
     assert its_s >= 4 * 40
-    rc_a, asyn, its_a, pc_a, msg_a = long_run(1 | ASYNC_GMRES | NO_RESTART_GROWTH)
+    rc_a, asyn, its_a, pc_a, msg_a = long_run(klib.TUNE_FUSED | klib.TUNE_ASYNC_GMRES | klib.TUNE_NO_RESTART_GROWTH)
     assert rc_a == 0, msg_a
     print('long restart: pipelined %d iterations, rel-L2 vs LU %.3e, vs synchronous %.3e' % (its_a, rel_l2(asyn, un), rel_l2(asyn, sync)))
     assert pc_a == klib.PC_NONE
@@ -580,7 +578,7 @@ def test_synchronous_gmres_beyond_32_vectors(reserved):
     the ladder).  The stats hold no per-cycle count; what they allow: at least 4 * 40 iterations over four stage solves means one solve of
     at least 40, and a cycle of a solve ends before its 64th column only on convergence -- so that solve's first cycle ran past 32 columns."""
     cfg, u, un = long_case()
-    rc, state, its, pc, msg = long_run(1 | NO_RESTART_GROWTH, reserved)
+    rc, state, its, pc, msg = long_run(klib.TUNE_FUSED | klib.TUNE_NO_RESTART_GROWTH, reserved)
     assert rc == 0, msg
     print('beyond 32 vectors (reserved %d): %d iterations, rel-L2 vs LU %.3e' % (reserved, its, rel_l2(state, un)))
     assert its >= 4 * 40

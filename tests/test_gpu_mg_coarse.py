@@ -155,7 +155,7 @@ STIFF = {'2d': _stiff_2d, '3d': _stiff_3d, '1d-96': lambda: _stiff_1d(96, 5.0), 
 def _one_step(cfg, u, h, kind, ksp_rtol, maxu=0, eager=False):
     k = klib.KSFDHip(cfg)
     if eager:
-        k.set_mg_params(power_its=-7)
+        k.set_mg_params(power_its=klib.MG_EAGER)
     if kind is not None:
         k.set_mg_coarse(kind, maxu)
     k.set_state(u)

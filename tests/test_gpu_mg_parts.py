@@ -31,7 +31,6 @@ MARGIN = 32.0
 S_MILD, S_STIFF = 1.0 / (GAMMA * 0.05), 1.0 / (GAMMA * 50.0)      # shifts of the DINV test
 S_CYCLE = 1.0 / (GAMMA * 5.0)                 # shift of the SMOOTH and CYCLE tests: a stiff step
 MG_RATIO = 6.0                                # the handle's default smoothing interval (mg_ratio)
-NO_COEF32, UNFUSED = 512, 4096                # ksfd_set_tuning bits 9 and 12
 
 #         name        shape       ligands  extents per level                          path per level (0 strip 2-D, 2 strip 3-D, 3 generic)
 CASES = {'32x32': ((32, 32), 1, [(32, 32), (16, 16), (8, 8)], [0, 0, 3]),
@@ -187,10 +186,10 @@ def test_level_info(name):
 def test_level_zero_reads_fp64_planes_with_tuning_bit_9():
     c = case('32x32')
     try:
-        c.k.set_tuning(use_fused=1 | NO_COEF32)
+        c.k.set_tuning(use_fused=klib.TUNE_FUSED | klib.TUNE_POLY_FP64)
         assert c.k.mg_level_info(0)['coef32'] & 1 == 0
     finally:
-        c.k.set_tuning(use_fused=1)
+        c.k.set_tuning(use_fused=klib.TUNE_FUSED)
     assert c.k.mg_level_info(0)['coef32'] & 1 == 1
 
 
@@ -369,10 +368,10 @@ def test_level_operator(name):
 
 
 def test_level_zero_operator_on_fp64_planes():
-    """tuning bit 9: level 0 reads the fp64 planes, and is compared on them"""
+    """TUNE_POLY_FP64: level 0 reads the fp64 planes, and is compared on them"""
     c = case('64x48')
     try:
-        c.k.set_tuning(use_fused=1 | NO_COEF32)
+        c.k.set_tuning(use_fused=klib.TUNE_FUSED | klib.TUNE_POLY_FP64)
         C = c.coef(0)[0].astype(LD)
         for what, v in c.inputs(0, 97):
             ref = mr.op_apply(C, v.astype(LD), c.h(0), c.lig, S_CYCLE)
@@ -383,7 +382,7 @@ def test_level_zero_operator_on_fp64_planes():
             if what == 'random':
                 assert per_field(got, ref32) > 100 * TOL_OP
     finally:
-        c.k.set_tuning(use_fused=1)
+        c.k.set_tuning(use_fused=klib.TUNE_FUSED)
 
 
 @pytest.mark.parametrize('name', FIRST_2D + ['ring-64x48'])
@@ -431,12 +430,12 @@ def test_chebyshev_bound_is_a_power_iteration_quotient(name):
 SMOOTH_RUNS = [(1, True), (2, False), (2, True), (3, False), (5, False)]         # (nu, nonzero guess)
 
 
-@pytest.mark.parametrize('tune', [0, UNFUSED])
+@pytest.mark.parametrize('tune', [0, klib.TUNE_UNFUSED_SMOOTHER])
 @pytest.mark.parametrize('name', SMOOTH_CASES)
 def test_smoother(name, tune):
     c = case(name)
     try:
-        c.k.set_tuning(use_fused=1 | tune)
+        c.k.set_tuning(use_fused=klib.TUNE_FUSED | tune)
         lv64, lvld = c.levels(S_CYCLE, tune), c.levels(S_CYCLE, tune, LD)
         for l in range(c.nlev):
             b = np.random.default_rng(111 + l).standard_normal((c.F,) + c.grid(l))
@@ -457,7 +456,7 @@ def test_smoother(name, tune):
                           (name, l, 'unfused' if tune else 'fused', nu, 'guess' if guess else 'zero', ratio, d_ref, d, bound / max(d, 1e-300)))
                     assert d <= bound, ('SMOOTH', l, nu, guess, ratio, d, d_ref)
     finally:
-        c.k.set_tuning(use_fused=1)
+        c.k.set_tuning(use_fused=klib.TUNE_FUSED)
 
 
 # ---- 7. the cycle ------------------------------------------------------------------------------------------------------------------------
@@ -501,7 +500,7 @@ def test_cycle(name, coarse):
             d_ref = mr.rel_l2(x64, xld)
             got = {}
             for eager in ([True] if ring else [False, True]):  # a handle with a halo transport always launches eagerly
-                c.k.set_mg_params(power_its=-7 if eager else 0)
+                c.k.set_mg_params(power_its=klib.MG_EAGER if eager else 0)
                 g = c.field(c.k.mg_part(klib.MGP_CYCLE, 0, b, variant=0, shift=S_CYCLE), 0)
                 d, bound = mr.rel_l2(g, xld), MARGIN * max(d_ref, TOL_OP)
                 print('mg_parts CYCLE fp64 %s %s %s %s: d_ref %.3e distance %.3e head-room %.1f' %

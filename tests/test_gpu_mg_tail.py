@@ -151,7 +151,7 @@ def test_whole_cycle(name):
                 x32c = mr.vcycle(c._lv['copies'], c.lig, S_CYCLE, b, 2, MG_RATIO, store=mr.store_f32, nstore=nstore)
             got = {}
             for eager in (False, True):
-                c.k.set_mg_params(power_its=-7 if eager else 0)
+                c.k.set_mg_params(power_its=klib.MG_EAGER if eager else 0)
                 n0 = c.k.mg_tail_info()['launches']
                 g = c.field(c.k.mg_part(klib.MGP_CYCLE, 0, b, variant=0, shift=S_CYCLE), 0)
                 assert c.k.mg_tail_info()['launches'] == n0 + 1
@@ -194,7 +194,7 @@ def test_launch_count(name):
     rec = {}
     for on in (False, True):
         k = klib.KSFDHip(cfg)
-        k.set_mg_params(power_its=-7)
+        k.set_mg_params(power_its=klib.MG_EAGER)
         if on:
             k.set_mg_tail(maxp)
         k.set_state(u)

@@ -68,7 +68,7 @@ def test_operators_vs_oracle_seeded(shape, nlig):
     # strips_for caps the segments at two rows on grids this small, so both passes run the same launch; segments of 5 and 32 rows are
     # reached in tests/test_gpu_stage_ops.py::test_long_segments_2d_in_a_fresh_process
     for yseg in (32, 5):
-        k.set_tuning(use_fused=1, yseg=yseg)
+        k.set_tuning(use_fused=klib.TUNE_FUSED, yseg=yseg)
         assert rel_l2(k.rhs(u), o.rhs(u)) < TOL
         assert rel_l2(k.jvp(v, u), o.jvp(u, v)) < TOL
     src = [rng.standard_normal(N) for _ in range(cfg.F)]

@@ -251,7 +251,8 @@ def test_predicted_last_sweep_is_verified_by_the_library_itself():
     evaluating one more residual (ksp_rtol >= 1e-8).  KSFD_SPEC_VERIFY=1 makes the library evaluate that residual anyway and fail the solve
     (KSFD_ELINEAR) if it is above the tolerance: an adaptive run of the bench problem at 1024^2 from dt0 = 1e-8 through the ramp into the
     regime the bench measures must get through it, with most stage solves of the later steps ending on a predicted sweep -- and give the
-    fields of the same run with every solve verified (opts.reserved bit 3) to 1e-9."""
+    fields of the same run with every solve verified (opts.reserved bit 3) to 1e-9.  The handle's own switch (TUNE_NO_SPEC_PREDICT) does
+    what the caller's flag does: no predicted sweep, the residual evaluations and the fields of the verified run."""
     import os
     import subprocess
     import sys
@@ -264,8 +265,9 @@ from ksfd_amd.initial import reference_rng
 cfg = build_problem(1024, 1)
 zc = reference_rng().normal(size=(256, 256)) * 90.0
 out = []
-for flag in (0, 8):
+for flag, tune in ((0, 0), (8, 0), (0, klib.TUNE_NO_SPEC_PREDICT)):
     k = klib.KSFDHip(cfg)
+    k.set_tuning(use_fused=klib.TUNE_FUSED | tune)
     k.set_state_random(zc, 9000.0)
     o = klib.default_step_opts(adapt=1, atol=0.01, rtol=1e-6, reserved=flag)
     t, h, pred, res = 0.0, 1e-8, 0, 0
@@ -275,8 +277,9 @@ for flag in (0, 8):
         res += st.residual_evals
     out.append((k.get_state(), t, pred, res))
     k.close()
-(a, ta, pa, ra), (b, tb, pb, rb) = out
-print('RESULT', pa, ra, pb, rb, abs(ta - tb) / tb, float(np.linalg.norm(a - b) / np.linalg.norm(b)))
+(a, ta, pa, ra), (b, tb, pb, rb), (c, tc, pt, rt) = out
+print('RESULT', pa, ra, pb, rb, abs(ta - tb) / tb, float(np.linalg.norm(a - b) / np.linalg.norm(b)), pt, rt, abs(tc - tb) / tb,
+      float(np.linalg.norm(c - b) / np.linalg.norm(b)))
 ''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KSFD_SPEC_VERIFY='1')
     r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=280)
@@ -288,12 +291,14 @@ print('RESULT', pa, ra, pb, rb, abs(ta - tb) / tb, float(np.linalg.norm(a - b) /
     assert res < res_v                                     # ... and they are what saves residual evaluations
     assert r.stderr.count('predicted final sweep') == pred
     assert dt < 1e-6 and err < 1e-9
+    pred_t, res_t, dt_t, err_t = int(line[7]), int(line[8]), float(line[9]), float(line[10])
+    assert pred_t == 0 and res_t == res_v and dt_t < 1e-6 and err_t < 1e-9
 
 
 @pytest.mark.parametrize('shape,nlig', [((128, 96), 1), ((64, 64), 2), ((96, 48), 1)])
 def test_guess_inner_products_from_the_rhs_epilogue(shape, nlig):
     """The stage guesses need <b_i, b_j> of a new stage right-hand side with the (up to two) before it.  They come out of the RHS kernel's
-    store epilogue (per-wave partials beside ||b_i||^2); KSFD_TUNE bit 21 computes them in a pass of their own as before: same sweeps, same
+    store epilogue (per-wave partials beside ||b_i||^2); KSFD_TUNE_OWN_DOTS computes them in a pass of their own as before: same sweeps, same
     accepted steps, step sizes and states equal to what the rounding of the sums does to the guesses (1e-9 / 1e-10: the solves stop at 1e-6),
     fewer launches."""
     cfg = ProblemConfig.standard(2, shape, L=tuple(n * 4.0 / 1536 for n in shape), nlig=nlig)
@@ -301,7 +306,7 @@ def test_guess_inner_products_from_the_rhs_epilogue(shape, nlig):
     rho = 9000 + 90 * rng.standard_normal(cfg.N)
     u = np.concatenate([rho] + [rho * cfg.lig_s[l] / cfg.lig_gamma[l] for l in range(nlig)])
     out = {}
-    for name, tune in (('epilogue', 1), ('own pass', 1 | 2097152)):
+    for name, tune in (('epilogue', klib.TUNE_FUSED), ('own pass', klib.TUNE_FUSED | klib.TUNE_OWN_DOTS)):
         k = klib.KSFDHip(cfg)
         k.set_tuning(use_fused=tune)
         k.set_state(u)

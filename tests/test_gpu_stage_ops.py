@@ -44,7 +44,6 @@ TOL = 1e-12                                   # tests/test_gpu_operators.py
 TOL_OP = 1e-12
 HSTEP = 0.05
 S_A, S_B = 1.0 / (GAMMA * 0.05), 1.0 / (GAMMA * 5.0)
-NO_OVERLAP, POLY64, UNFUSED, GENERIC3D, NOCARRY, OWNDOTS, NOGPLANE = 1 << 2, 1 << 9, 1 << 10, 1 << 13, 1 << 15, 1 << 21, 1 << 23
 STRIP_OUT, WAVES_RHS, WAVES_JVP, YSEG_RHS, YSEG_JVP, ZSEG, BLOCKS3D = 124, 6144, 4096, 48, 16, 32, 1024
 AT, GINV, BT, B2T, _ = ko.tableau()
 
@@ -66,7 +65,7 @@ CASES = {'6x5': ((6, 5), 1, False, klib.JP_STRIP2D),                  # smallest
          '24x9x40': ((24, 9, 40), 3, False, klib.JP_STRIP3D),
          'ring-36x20': ((36, 20), 1, True, klib.JP_STRIP2D),          # >= 3 segments: interior + boundary launches, split partials
          'ring-64x8': ((64, 8), 2, True, klib.JP_STRIP2D),            # four segments of two rows (strips_for leaves no grid of >= 5 rows fewer than 3
-                                                                      # segments): one launch only with tuning bit 2, or in the long-segment child
+                                                                      # segments): one launch only with TUNE_NO_OVERLAP, or in the long-segment child
          'ring-64x48': ((64, 48), 1, True, klib.JP_STRIP2D),          # ... with a hierarchy: the inner products in split partials
          # the long-segment cases (child process / 3-D test only)
          '130x37': ((130, 37), 2, False, klib.JP_STRIP2D),
@@ -184,7 +183,7 @@ class Case:
     def rhs_geometry(self, yseg=YSEG_RHS, tune=0):
         if self.path == klib.JP_STRIP2D:
             return dict(strips(self.shape[0], self.shape[1], yseg, self.waves[0]), rows=0)
-        if self.path in (klib.JP_LDS3D, klib.JP_STRIP3D) and not tune & GENERIC3D:
+        if self.path in (klib.JP_LDS3D, klib.JP_STRIP3D) and not tune & klib.TUNE_GENERIC_RHS3D:
             return k3d(self.shape, 4)
         return dict(seg=0, nseg=0, nstrips=0, rows=0)
 
@@ -301,19 +300,19 @@ def expected_books(c, tune, info):
         halo_split = info['overlap'] and i > 0 and fused          # the newest stage vector's ghost rows travel behind the interior rows
         if c.path == klib.JP_STRIP2D:
             if fused:
-                gplane = i == 0 and not tune & NOGPLANE
-                carry = i > 0 and not tune & NOCARRY
+                gplane = i == 0 and not tune & klib.TUNE_NO_GPLANE
+                carry = i > 0 and not tune & klib.TUNE_NO_RHS_CARRY
                 rhs_b += vb(2 + nin[i] + (0 if carry or i == 0 else nin[i]) + nd) + (8.0 * N if gplane else 0.0)
                 arms.add('gplane' if gplane else 'carry' if carry else 'plain' if i == 0 else 'yout')
             else:
-                gplane = i == 0 and not tune & NOGPLANE
+                gplane = i == 0 and not tune & klib.TUNE_NO_GPLANE
                 rhs_b += vb(2) + (8.0 * N if gplane else 0.0)
                 lin_l += 2 if i > 0 else 0
                 arms.add('unfused2d')
             rhs_l += 2 if halo_split else 1
             if nd:
                 arms.add('dots-epilogue')
-        elif c.path in (klib.JP_LDS3D, klib.JP_STRIP3D) and not tune & GENERIC3D:
+        elif c.path in (klib.JP_LDS3D, klib.JP_STRIP3D) and not tune & klib.TUNE_GENERIC_RHS3D:
             ni, no = (nin[i], nin[i]) if fused else (0, 0)
             if i > 0:                                              # stage 0 takes G from the coefficient planes: no pass
                 gf_l += 1
@@ -337,7 +336,7 @@ def check_rhs(c, kind, regime, tune, yseg=None, say=None):
     u, Y = c.inputs(kind)
     c.use(kind)
     k = c.k
-    k.set_tuning(use_fused=1 | tune, **({} if yseg is None else dict(yseg=yseg)))
+    k.set_tuning(use_fused=klib.TUNE_FUSED | tune, **({} if yseg is None else dict(yseg=yseg)))
     k.velocity_max()                                       # the CFL check makes the planes, as before a step: the call books the stages alone
     k.profile(reset=True)
     b, info, _ = k.stage_rhs(regime, HSTEP, Y[:3])
@@ -347,9 +346,9 @@ def check_rhs(c, kind, regime, tune, yseg=None, say=None):
     geo = c.rhs_geometry(yseg or YSEG_RHS, tune)
     assert {q: info[q] for q in geo} == geo, (tag, info, geo)
     assert info['path'] == c.path and info['rhs_strip'] == (geo['nseg'] > 0)
-    assert info['overlap'] == (c.ring and c.path == klib.JP_STRIP2D and geo['nseg'] >= 3 and not tune & NO_OVERLAP)
-    strip_ok = c.path in (klib.JP_STRIP2D, klib.JP_STRIP3D, klib.JP_LDS3D) and c.nlig <= 4 and not (c.dim == 3 and tune & GENERIC3D)
-    assert info['fuse_stage'] == (strip_ok and not tune & UNFUSED), tag
+    assert info['overlap'] == (c.ring and c.path == klib.JP_STRIP2D and geo['nseg'] >= 3 and not tune & klib.TUNE_NO_OVERLAP)
+    strip_ok = c.path in (klib.JP_STRIP2D, klib.JP_STRIP3D, klib.JP_LDS3D) and c.nlig <= 4 and not (c.dim == 3 and tune & klib.TUNE_GENERIC_RHS3D)
+    assert info['fuse_stage'] == (strip_ok and not tune & klib.TUNE_UNFUSED_STAGE), tag
     # every right-hand side
     worst = 0.0
     for i, (ref, scale) in enumerate(c.rhs_ref(kind)):
@@ -373,7 +372,7 @@ def check_rhs(c, kind, regime, tune, yseg=None, say=None):
                 s, sa = dot_ld(b[i], b[j])
                 assert abs(LD(info['gb'][i][j]) - s) <= n * EPS * sa, ('gb', tag, i, j, float(abs(LD(info['gb'][i][j]) - s) / sa))
                 assert info['gb'][j][i] == info['gb'][i][j]
-            assert info['dots_done'][i] == (norm_on and i > 0 and not tune & OWNDOTS), (tag, i)
+            assert info['dots_done'][i] == (norm_on and i > 0 and not tune & klib.TUNE_OWN_DOTS), (tag, i)
             assert info['bnorm2'][i] == info['gb'][i][i]
             check_guess(info, i, tag)
     if norm_on:
@@ -422,8 +421,8 @@ def check_guess(info, i, tag):
 
 
 def rhs_variants(c):
-    v = [0, NOCARRY, NOGPLANE, UNFUSED, OWNDOTS]
-    return v + ([GENERIC3D] if c.dim == 3 else [])
+    v = [0, klib.TUNE_NO_RHS_CARRY, klib.TUNE_NO_GPLANE, klib.TUNE_UNFUSED_STAGE, klib.TUNE_OWN_DOTS]
+    return v + ([klib.TUNE_GENERIC_RHS3D] if c.dim == 3 else [])
 
 
 def test_four_by_four_is_refused_at_create():
@@ -451,7 +450,7 @@ def test_stage_rhs_every_variant(name):
                 seen |= arms
                 by_variant[(tune, regime, kind)] = (info, b)
     # epilogue and own-pass inner products: the same numbers within the summation bound, of the same right-hand sides
-    a, b = by_variant[(0, 1, 'clean')], by_variant[(OWNDOTS, 1, 'clean')]
+    a, b = by_variant[(0, 1, 'clean')], by_variant[(klib.TUNE_OWN_DOTS, 1, 'clean')]
     assert np.array_equal(a[1], b[1])
     if a[0]['guess_on'] and c.path == klib.JP_STRIP2D:
         assert any(a[0]['dots_done']) and not any(b[0]['dots_done'])
@@ -459,8 +458,8 @@ def test_stage_rhs_every_variant(name):
             for j in range(max(0, i - 2), i + 1):
                 sa = dot_ld(a[1][i], a[1][j])[1]
                 assert abs(a[0]['gb'][i][j] - b[0]['gb'][i][j]) <= 2 * c.n * EPS * sa, (i, j)
-    # the variants never change what is computed beyond rounding; GPLANE may differ in the last bit of G (ksfd_hip.h, tuning bit 23)
-    for tune in (NOCARRY, UNFUSED):
+    # the variants never change what is computed beyond rounding; GPLANE may differ in the last bit of G (ksfd_hip.h, KSFD_TUNE_NO_GPLANE)
+    for tune in (klib.TUNE_NO_RHS_CARRY, klib.TUNE_UNFUSED_STAGE):
         assert np.array_equal(by_variant[(tune, 0, 'clean')][1][0], by_variant[(0, 0, 'clean')][1][0])
     ALL_ARMS[name] = seen
     want = {klib.JP_STRIP2D: {'gplane', 'carry', 'plain', 'yout', 'unfused2d'}, klib.JP_LDS3D: {'strip3d', 'strip3d-comb', 'generic'},
@@ -482,16 +481,16 @@ def test_stage_rhs_arms_all_seen():
     for name, guess in (('ring-36x20', None), ('ring-64x48', True)):
         c = case(name)
         c.use('clean')
-        c.k.set_tuning(use_fused=1)
+        c.k.set_tuning(use_fused=klib.TUNE_FUSED)
         info = c.k.stage_rhs(1, HSTEP, c.Y[:3])[1]
         assert info['overlap'] and info['nseg'] >= 3 and all(x >= 0 for x in info['bnorm2'])
         if guess:
             assert info['guess_on'] and all(info['dots_done'][1:])
-    # one launch on a ring: with the overlap switched off (tuning bit 2); with fewer than 3 segments in the long-segment child
+    # one launch on a ring: with the overlap switched off (TUNE_NO_OVERLAP); with fewer than 3 segments in the long-segment child
     c = case('ring-64x8')
     info = check_rhs(c, 'clean', 1, 0)[0]
     assert info['overlap'] and info['nseg'] == 4
-    info = check_rhs(c, 'clean', 1, NO_OVERLAP)[0]
+    info = check_rhs(c, 'clean', 1, klib.TUNE_NO_OVERLAP)[0]
     assert not info['overlap'] and all(x >= 0 for x in info['bnorm2'])
     assert case('8x5').rhs_geometry() == dict(seg=2, nseg=3, nstrips=1, rows=0)
     assert case('126x8').rhs_geometry()['nstrips'] == 2 and case('250x9').rhs_geometry()['nstrips'] == 3
@@ -528,7 +527,7 @@ def check_finish(c, tune=0, atol=0.01, rtol=1e-6):
     u[c.n - 1 - c.N // 5] = -3.0
     c.k.set_state(u)
     c.state = None
-    c.k.set_tuning(use_fused=1 | tune)
+    c.k.set_tuning(use_fused=klib.TUNE_FUSED | tune)
     Y = c.Yd
     b, info, (unew, err) = c.k.stage_rhs(0, HSTEP, Y, finish=(atol, rtol))
     terms_u = np.abs(u).astype(LD)
@@ -566,14 +565,14 @@ def check_finish(c, tune=0, atol=0.01, rtol=1e-6):
 def test_completion_norm_and_count(name):
     c = case(name)
     check_finish(c)
-    check_finish(c, tune=1 << 22)                          # the old step boundary: the completion stores the error vector itself
+    check_finish(c, tune=klib.TUNE_OLD_BOUNDARY)                          # the old step boundary: the completion stores the error vector itself
 
 
 # ---- 3. the frozen action ---------------------------------------------------------------------------------------------------------------------
 def check_action(c, kind, yseg=None, tune=0, say=None):
     c.use(kind)
     k = c.k
-    k.set_tuning(use_fused=1 | tune, **({} if yseg is None else dict(yseg=yseg)))
+    k.set_tuning(use_fused=klib.TUNE_FUSED | tune, **({} if yseg is None else dict(yseg=yseg)))
     F = c.F
     geo = c.jvp_geometry(yseg or YSEG_JVP)
     y = np.random.default_rng(23).standard_normal(c.n)
@@ -616,7 +615,7 @@ def test_action_modes(name):
 def check_residual(c, kind, yseg=None, say=None):
     c.use(kind)
     k = c.k
-    k.set_tuning(use_fused=1, **({} if yseg is None else dict(yseg=yseg)))
+    k.set_tuning(use_fused=klib.TUNE_FUSED, **({} if yseg is None else dict(yseg=yseg)))
     b = np.random.default_rng(31).standard_normal(c.n) * 50.0
     for what, x in c.vectors(37):
         Ax = c.A(kind, x, S_A).reshape(-1)
@@ -651,7 +650,7 @@ def test_residual32(name):
 def test_residual32_refused_without_a_strip_kernel(name):
     c = case(name)
     c.use('clean')
-    c.k.set_tuning(use_fused=1)
+    c.k.set_tuning(use_fused=klib.TUNE_FUSED)
     v = np.ones(c.n)
     with pytest.raises(klib.KSFDError) as e:
         c.k.stage_jvp(klib.SJ_RESIDUAL32, v, v, shift=S_A)
@@ -674,7 +673,7 @@ def horner(c, kind, v, coef, shift, fp32_planes=False, store=None):
 def check_poly(c, kind, fp32, yseg=None, say=None):
     c.use(kind)
     k = c.k
-    k.set_tuning(use_fused=1 | (0 if fp32 else POLY64), **({} if yseg is None else dict(yseg=yseg)))
+    k.set_tuning(use_fused=klib.TUNE_FUSED | (0 if fp32 else klib.TUNE_POLY_FP64), **({} if yseg is None else dict(yseg=yseg)))
     rng = np.random.default_rng(41)
     v = c.vectors(43)[0][1]
     for deg in (1, 2, 3, 7):
@@ -785,7 +784,7 @@ def test_long_segments_3d(name):
     c = Case(name)
     try:
         assert c.jvp_geometry()['seg'] >= 4 and c.rhs_geometry()['seg'] >= 4
-        for tune in (0, UNFUSED):
+        for tune in (0, klib.TUNE_UNFUSED_STAGE):
             check_rhs(c, 'clean', 0, tune, say=print)
         check_rhs(c, 'dirty', 2, 0, say=print)
         check_action(c, 'clean', say=print)

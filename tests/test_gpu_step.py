@@ -13,6 +13,7 @@ from oracle import ko
 
 pytestmark = pytest.mark.gpu
 STEP_TOL = 1e-10      # rel-L2 of the state; north_star asks 1e-8
+F = klib.TUNE_FUSED   # the default tuning word; every word below is F | the switches it names (a word replaces all of them)
 
 
 def fixed_opts(z, **kw):
@@ -20,12 +21,15 @@ def fixed_opts(z, **kw):
                                   ksp_max_it=4000, **kw)
 
 
-@pytest.mark.parametrize('orth,tuning', [(0, 1), (1, 1), (0, 3), (0, 0), (0, 1 | 8), (0, 1 | 16), (0, 1 | 8192)])
+@pytest.mark.parametrize('orth,tuning', [(0, F), (1, F), (0, F | klib.TUNE_RECOMPUTE_JVP), (0, 0), (0, F | klib.TUNE_ASYNC_GMRES), (0, F | klib.TUNE_NO_RECYCLE),
+                                         (0, F | klib.TUNE_GENERIC_RHS3D), (0, F | klib.TUNE_REC_KEEP(1)), (0, F | klib.TUNE_REC_KEEP(4)),
+                                         (0, F | klib.TUNE_NO_ZERO_COPY)])
 @pytest.mark.parametrize('name', [n for n in golden_cases('step_') if 'manufactured' not in n and 'tdep' not in n])
 def test_fixed_steps_vs_reference_lu_golden(name, orth, tuning):
-    """orth 0: CGS2 with algebraic second projection, 1: classic CGS2; tuning bit0 fused kernels, bit1 recompute J,
-    bit3 pipelined (device-resident) GMRES forced, bit4 no Krylov recycling, bit13 3-D RHS through the generic stencil pass
-    instead of the z-marching strip kernel (the default)"""
+    """orth 0: CGS2 with algebraic second projection, 1: classic CGS2; tuning: the default word, the recomputed Jacobian action, no
+    fused kernels at all (0), the pipelined (device-resident) GMRES forced, no Krylov recycling, the 3-D RHS through the generic stencil pass
+    instead of the z-marching strip kernel (the default), one and four vectors recycled per stage instead of three, reduction results by
+    synchronise-and-copy instead of the mapped flag"""
     z = load_golden(name)
     cfg = ProblemConfig.from_golden(z)
     k = klib.KSFDHip(cfg)
@@ -259,7 +263,7 @@ def test_krylov_recycling_across_stages_saves_iterations_same_answer():
     k = klib.KSFDHip(cfg)
     k.set_spectral_params(enable=0)                             # this test is about the Krylov path (64^2 would otherwise take the spectral solver)
     res = {}
-    for name, tune in (('on', 1), ('off', 1 | 16), ('all', 1 | 32)):
+    for name, tune in (('on', F), ('off', F | klib.TUNE_NO_RECYCLE), ('all', F | klib.TUNE_RECYCLE_ALL)):
         k.set_tuning(use_fused=tune)
         for tol in (1e-6, 1e-11):
             k.set_state(u)
@@ -285,7 +289,7 @@ def test_stage_guesses_in_the_multigrid_regime_save_iterations_same_answer():
     h = 20.0
     un, _, _, _ = ko.Oracle(cfg).rosw_step(u, h, 0.01, 1e-6, solver='lu')
     res = {}
-    for name, tune in (('on', 1), ('off', 1 | 16384)):
+    for name, tune in (('on', F), ('off', F | klib.TUNE_NO_SPEC_GUESS), ('whole cycle kept', F | klib.TUNE_REC_MG)):
         for tol in (1e-6, 1e-11):
             k = klib.KSFDHip(cfg)            # a handle each: the hierarchy's set-up remembers the previous one (warm power iteration)
             k.set_tuning(use_fused=tune)
@@ -295,7 +299,7 @@ def test_stage_guesses_in_the_multigrid_regime_save_iterations_same_answer():
             res[name, tol] = (st.linear_its, k.get_state())
             k.close()
     assert res['on', 1e-6][0] < res['off', 1e-6][0], (res['on', 1e-6][0], res['off', 1e-6][0])
-    for name in ('on', 'off'):
+    for name in ('on', 'off', 'whole cycle kept'):       # TUNE_REC_MG: another projection in front of the same solve to the same true residual
         assert rel_l2(res[name, 1e-11][1], un) < 1e-9, name
         assert rel_l2(res[name, 1e-6][1], un) < 5e-6, name    # a residual tolerance: the state follows it to a small factor
 
@@ -396,7 +400,7 @@ def test_fused_multigrid_smoother_gives_the_same_iterates(shape):
     u = np.concatenate([rho] + [rho * cfg.lig_s[l] / cfg.lig_gamma[l] for l in range(cfg.nlig)])
     k = klib.KSFDHip(cfg)
     out = {}
-    for name, tune in (('fused', 1 | 262144), ('separate', 1 | 4096 | 262144)):      # bit 18: every set-up from the same cold start
+    for name, tune in (('fused', F | klib.TUNE_COLD_POWER), ('separate', F | klib.TUNE_UNFUSED_SMOOTHER | klib.TUNE_COLD_POWER)):      # every set-up from the same cold start
         k.set_tuning(use_fused=tune)
         k.set_state(u)
         t, hn, st, rc = k.step(0.0, 10.0, klib.default_step_opts(adapt=0, atol=0.01, rtol=1e-6, ksp_rtol=1e-10, pc_type=1))
@@ -409,7 +413,7 @@ def test_fused_multigrid_smoother_gives_the_same_iterates(shape):
 @pytest.mark.parametrize('shape,nlig', [((32, 32), 2), ((64, 48), 1), ((96, 64), 3), ((64, 64), 4), ((36, 36), 2), ((256, 32), 1)])
 def test_multigrid_cycle_with_fp32_level_vectors(shape, nlig):
     """ksp_rtol >= 1e-7: the V cycle keeps its level vectors in fp32 (mg_vcycle<float>; arithmetic fp64, GMRES and its true-residual test fp64).
-    Same step as with the fp64 cycle (KSFD_TUNE bit 19) to the solve tolerance, iteration counts within one per stage, and (32^2, where the
+    Same step as with the fp64 cycle (KSFD_TUNE_MG_FP64) to the solve tolerance, iteration counts within one per stage, and (32^2, where the
     sparse LU takes seconds) the oracle's LU step to 5e-6 -- one to four ligands, a grid whose second level is already the coarsest one (36^2: only level 0 runs in fp32), a slab-shaped one."""
     L = tuple(0.0025 * n for n in shape)
     if nlig <= 2:
@@ -423,7 +427,7 @@ def test_multigrid_cycle_with_fp32_level_vectors(shape, nlig):
     u = np.concatenate([rho] + [rho * cfg.lig_s[l] / cfg.lig_gamma[l] for l in range(nlig)])
     h = 10.0
     out = {}
-    for name, tune in (('fp32', 1), ('fp64', 1 | 524288)):
+    for name, tune in (('fp32', F), ('fp64', F | klib.TUNE_MG_FP64)):
         k = klib.KSFDHip(cfg)
         k.set_tuning(use_fused=tune)
         k.set_state(u)
@@ -440,7 +444,7 @@ def test_multigrid_cycle_with_fp32_level_vectors(shape, nlig):
 
 @pytest.mark.parametrize('shape,nlig', [((32, 16), 1)])
 def test_fp32_cycle_without_the_fp32_coefficient_copy(shape, nlig):
-    """tuning bit 9 takes the fp32 copy of the coefficient planes away: level 0 of the fp32 cycle then reads the fp64 planes with fp32
+    """TUNE_POLY_FP64 takes the fp32 copy of the coefficient planes away: level 0 of the fp32 cycle then reads the fp64 planes with fp32
     level vectors, the one combination of storage types of the 2-D strip kernel that no other test launches.  32x16 is the smallest grid
     with a level below level 0 (16x8).  Bounds of test_multigrid_cycle_with_fp32_level_vectors: the fp64 cycle to 2e-7, the oracle's LU
     step to 5e-6, iteration counts within one per stage."""
@@ -450,7 +454,7 @@ def test_fp32_cycle_without_the_fp32_coefficient_copy(shape, nlig):
     u = np.concatenate([rho] + [rho * cfg.lig_s[l] / cfg.lig_gamma[l] for l in range(nlig)])
     h = 10.0
     out = {}
-    for name, tune in (('fp32', 1 | 512), ('fp64', 1 | 512 | 524288)):
+    for name, tune in (('fp32', F | klib.TUNE_POLY_FP64), ('fp64', F | klib.TUNE_POLY_FP64 | klib.TUNE_MG_FP64)):
         k = klib.KSFDHip(cfg)
         k.set_tuning(use_fused=tune)
         k.set_state(u)

@@ -1,8 +1,8 @@
 """GPU: the boundary of a step -- groom only when it can change a value, completion out of place (no roll-back copy), the embedded
 error vector and the fp32 coefficient copy made when somebody asks for them, the stage-0 right-hand side with G from the coefficient
-planes.  "Old" is a second handle with tuning bit 22 (groom every step, error vector stored by the completion, fp32 copy stored by the
+planes.  "Old" is a second handle with TUNE_OLD_BOUNDARY (groom every step, error vector stored by the completion, fp32 copy stored by the
 coefficient kernel) given the same state and options: everything but the G plane must be invisible bit for bit, so those comparisons
-are np.array_equal with the G plane (bit 23) switched off on both handles."""
+are np.array_equal with the G plane switched off (TUNE_NO_GPLANE) on both handles."""
 import dataclasses
 import os
 import socket
@@ -17,9 +17,8 @@ from oracle import ko
 
 pytestmark = pytest.mark.gpu
 
-NO_GPLANE = 1 << 23
-NEW = 1 | NO_GPLANE               # bit 0: the fused kernels (the default)
-OLD = 1 | NO_GPLANE | (1 << 22)
+NEW = klib.TUNE_FUSED | klib.TUNE_NO_GPLANE               # TUNE_FUSED: the fused kernels (the default)
+OLD = NEW | klib.TUNE_OLD_BOUNDARY
 STEP_TOL = 1e-10                  # tests/test_gpu_step.py: rel-L2 of the state against the oracle's step
 GRIDS = [((64, 32), 1), ((32, 64), 2), ((128, 96), 3)]
 
@@ -331,7 +330,7 @@ def test_stage0_rhs_from_the_g_plane(shape, nlig):
     u = smooth_state(cfg)
     opts = klib.default_step_opts(adapt=0, atol=0.01, rtol=1e-6, ksp_rtol=1e-12, ksp_max_it=4000)
     states = []
-    for tuning in (1, 1 | NO_GPLANE):
+    for tuning in (klib.TUNE_FUSED, klib.TUNE_FUSED | klib.TUNE_NO_GPLANE):
         k = handle(cfg, tuning, u)
         t, hn, st, rc = k.step(0.0, 0.05, opts)
         assert st.accepted and st.rhs_evals == 4

@@ -20,16 +20,19 @@ def _one(pattern, text):
 
 
 def test_geometry_constants_are_those_of_the_sources():
-    ops, stencil, handle = _src('ops.hip.h'), _src('stencil.hip.h'), _src('handle.hip.h')
+    ops, stencil, handle, tuning = _src('ops.hip.h'), _src('stencil.hip.h'), _src('handle.hip.h'), _src('tuning.h')
     assert _one(r'#define KSFD_STRIP_OUT (\d+)', stencil) == T.STRIP_OUT
     assert _one(r'#define KSFD_J3L_ROWS (\d+)', stencil) == 8                       # rows of Case.jvp_geometry on the LDS path
-    assert _one(r'getenv\("KSFD_WAVES_RHS"\)\) : (\d+);', ops) == T.WAVES_RHS
-    assert _one(r'getenv\("KSFD_WAVES_JVP"\)\) : (\d+);', ops) == T.WAVES_JVP
-    assert _one(r'int yseg = (\d+);', handle) == T.YSEG_RHS
-    assert _one(r'int yseg_jvp = (\d+);', handle) == T.YSEG_JVP
-    assert _one(r'int zseg = (\d+);', handle) == T.ZSEG
+    assert _one(r'waves_jvp = \d+, waves_rhs = (\d+);', handle) == T.WAVES_RHS        # EnvKnobs: the defaults of KSFD_WAVES_RHS / _JVP
+    assert _one(r'waves_jvp = (\d+), waves_rhs = \d+;', handle) == T.WAVES_JVP
+    # ... and each environment variable is read into the member of its name, by the one line that names it
+    assert re.findall(r'getenv\("KSFD_WAVES_(\w+)"\)\) E\.(\w+) = atoll\(v\);', handle) == [('JVP', 'waves_jvp'), ('RHS', 'waves_rhs')]
+    assert len(re.findall(r'KSFD_WAVES_\w+"', handle + ops)) == 2 and ops.count('jvp ? env_knobs().waves_jvp : env_knobs().waves_rhs') == 1    # make_strips
+    assert _one(r'int yseg = (\d+);', tuning) == T.YSEG_RHS
+    assert _one(r'int yseg_jvp = (\d+);', tuning) == T.YSEG_JVP
+    assert _one(r'int zseg = (\d+);', tuning) == T.ZSEG
     assert _one(r'rows == 8 \? 512 : (\d+)\)', ops) == T.BLOCKS3D                   # make_k3d, four rows per block
-    assert _one(r'k3d_for\(h->G, KSFD_J3L_ROWS, 0, h->zseg, (\d+)\)', ops) == T.BLOCKS3D
+    assert _one(r'k3d_for\(h->G, KSFD_J3L_ROWS, 0, h->tune.zseg, (\d+)\)', ops) == T.BLOCKS3D
 
 
 def test_python_copies_of_the_geometry_rules():

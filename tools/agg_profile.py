@@ -50,13 +50,13 @@ if os.environ.get('MG_NU'):
 if os.environ.get('MG_RATIO'):
     kb.set_mg_params(ratio=float(os.environ['MG_RATIO']))
 if os.environ.get('KSFD_TUNE_BITS'):
-    kb.set_tuning(use_fused=1 | int(os.environ['KSFD_TUNE_BITS']))
+    kb.set_tuning(use_fused=klib.TUNE_FUSED | int(os.environ['KSFD_TUNE_BITS']))
 if os.environ.get('MG_COARSE'):               # cheb | lu | lu:N  (ksfd_set_mg_coarse: exact coarse solve, N = max_unknowns)
     _kind, _, _max = os.environ['MG_COARSE'].partition(':')
     kb.set_mg_coarse({'cheb': 0, 'lu': 1}[_kind], int(_max or 0))
     print('mg_coarse', kb.mg_coarse_info(), flush=True)
 if os.environ.get('MG_EAGER'):
-    kb.set_mg_params(power_its=-7)          # no hipGraph for the coarse levels (rocprofv3 cannot trace the capture)
+    kb.set_mg_params(power_its=klib.MG_EAGER)          # no hipGraph for the coarse levels (rocprofv3 cannot trace the capture)
 for _ in range(2):
     t, h, st, rc = kb.step(t, h, opts)
 kb.synchronize()

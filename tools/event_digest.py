@@ -41,7 +41,7 @@ def events(k, cfg, tuning):
     return [
         ('first', lambda: None),
         ('mg_params nu 3', lambda: k.set_mg_params(nu=3)), ('mg_params nu 2', lambda: k.set_mg_params(nu=2)),
-        ('mg_fuse off', lambda: k.set_tuning(use_fused=tuning | 4096)), ('mg_fuse on', lambda: k.set_tuning(use_fused=tuning)),
+        ('mg_fuse off', lambda: k.set_tuning(use_fused=tuning | klib.TUNE_UNFUSED_SMOOTHER)), ('mg_fuse on', lambda: k.set_tuning(use_fused=tuning)),
         ('mg_coarse 1', lambda: k.set_mg_coarse(1, 600)), ('mg_coarse 0', lambda: k.set_mg_coarse(0)),
         ('mg_tail 1024', lambda: k.set_mg_tail(1024)), ('mg_tail 0', lambda: k.set_mg_tail(0)),
         ('update_params', lambda: k.update_params(dataclasses.replace(cfg, s2=1.1 * cfg.s2))),

@@ -15,7 +15,7 @@ for yseg in (8, 16, 32, 64):
     for cls in (klib.KC_RHS, klib.KC_JVP):
         ms, by = ks.bench_kernel(cls, 20)
         print('yseg %3d %-10s %.4f ms  %.1f GB/s' % (yseg, names[cls], ms, by / ms / 1e6), flush=True)
-print('--- recompute (non-frozen) JVP'); ks.set_tuning(use_fused=3, yseg=32)
+print('--- recompute (non-frozen) JVP'); ks.set_tuning(use_fused=klib.TUNE_FUSED | klib.TUNE_RECOMPUTE_JVP, yseg=32)
 ms, by = ks.bench_kernel(klib.KC_JVP, 20); print('recompute jvp %.4f ms %.1f GB/s' % (ms, by/ms/1e6), flush=True)
 ks.set_tuning(use_fused=0)
 for cls in (klib.KC_RHS, klib.KC_JVP):

@@ -57,7 +57,7 @@ def cycles(name, shape, nlig, variants, coarse_kinds):
         k.set_mg_coarse(kind)
         for variant in variants:
             for eager in (False, True):
-                k.set_mg_params(power_its=-7 if eager else 0)
+                k.set_mg_params(power_its=klib.MG_EAGER if eager else 0)
                 x = k.mg_part(klib.MGP_CYCLE, 0, b, variant=variant, shift=S_CYCLE)
                 print('cycle %s coarse %s variant %d %s %s' % (name, 'lu' if kind else 'cheb', variant, 'eager' if eager else 'graph', sha(x)))
     k.close()

@@ -119,7 +119,7 @@ def tail_against_its_launches(cfg, u, shift, maxp):
     out = {}
     for on in (False, True):
         k = klib.KSFDHip(cfg)
-        k.set_mg_params(power_its=-7)
+        k.set_mg_params(power_its=klib.MG_EAGER)
         if on:
             k.set_mg_tail(maxp)
         info = k.mg_tail_info()
